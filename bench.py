@@ -11,7 +11,9 @@ driver contract.
     python bench.py --gpus 1 --steps 20 --warmup 3
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (metric/value/... + "roofline" for the dominant kernel + "cpu_baseline").
+Prints ONE JSON line on rank 0 (metric/value/unit/ms_per_step/...).  A plain run sets up, warms up, times the steps and prints the line;
+`--full` adds every secondary measurement ("roofline" for the dominant kernel, the 3DGS legs, the training and data-parallel legs, the
+garden-shaped frame, "cpu_baseline").  `--dump-outputs DIR` writes what the last timed step returned (rank 0) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -80,11 +82,12 @@ def build_c4_scene(device):
     return model, renderer, cam, poses
 
 
-def strong_scaling_frames(renderer, cam, poses, rank, world, steps, warmup, barrier, red_dev):
+def strong_scaling_frames(renderer, cam, poses, rank, world, steps, warmup, barrier, red_dev, last_out=None):
     """`--scaling strong` / the `config_c4` entry: ONE 1600x1060 frame per step, cut into `world` contiguous tile shards
     (parallel.shard_range + render_image_fused(tile_begin, n_tiles): the protocol of scripts/inference.py:63-97 with the frame as the unit),
     followed by the all-gather of the (N / world, 5) pixel blocks (parallel.gather_image_shards) so that every rank holds the frame.
-    Timing contract of the driver: barrier + synchronize on both sides of exactly `steps` frames, max over ranks."""
+    Timing contract of the driver: barrier + synchronize on both sides of exactly `steps` frames, max over ranks.  `last_out` (a dict) receives
+    what the last timed frame returned."""
     import torch
     import torch.distributed as dist
     from nerficg_amd import parallel
@@ -118,6 +121,8 @@ def strong_scaling_frames(renderer, cam, poses, rank, world, steps, warmup, barr
     barrier()
     elapsed = time.perf_counter() - t0
     gather_ms = sum(a.elapsed_time(c) for a, c in ev) / max(steps, 1)
+    if last_out is not None:
+        last_out.update(out)
     finite = bool(torch.isfinite(out['rgb']).all())
     vals = torch.tensor([elapsed, t_local, gather_ms], device=red_dev, dtype=torch.float64)
     tot = torch.tensor([samples], device=red_dev, dtype=torch.int64)
@@ -1012,6 +1017,16 @@ def dp_gs_leg(rank, world, device, n_gaussians=1_000_000, iters=20):
             'bus_GBps_per_gpu': round(2 * (world - 1) / world * nbytes / (coll * 1e-3) / 1e9, 1) if world > 1 and coll > 0 else None, 'replica_drift': drift}
 
 
+def dump_outputs(out_dir: str, out: dict) -> None:
+    """--dump-outputs: what a caller of the timed path received from the LAST timed step -- the (H*W, 3) / (H*W,) rgb, alpha and depth buffers
+    (float32) and the marched sample count (float64) -- as DIR/<name>.npy: 12.8 MB for an 800x800 frame, 34 MB for a 1600x1060 one."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for name in ('rgb', 'alpha', 'depth'):
+        np.save(d / f'{name}.npy', out[name].detach().float().cpu().numpy())
+    np.save(d / 'n_samples.npy', np.array([out['n_samples']], dtype=np.float64))
+
+
 def spawn_ranks(n: int) -> int:
     """Runs this script as n ranks under torch.distributed.run (the driver's own command line) and returns its exit code.  No GPU call has
     happened in this process; the children inherit stdout, so rank 0's JSON line is the output."""
@@ -1031,6 +1046,11 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, every secondary measurement: rooflines of the frame kernels, the 3DGS legs, the training and data-parallel '
+                         'legs, the garden-shaped frame and the CPU baselines (the --no-* options below skip single legs of a --full run)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy (float32 / float64)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-gs', action='store_true', help='skip the secondary 3DGS leg')
     ap.add_argument('--no-train', action='store_true', help='skip the InstantNGP training-iteration leg')
@@ -1043,6 +1063,8 @@ def main():
                     help='weak (default, the headline): every rank renders its own 800x800 frame per step; strong: ONE 1600x1060 garden-shaped frame per step '
                          'cut into contiguous tile shards over the ranks + all-gather of the pixels (BASELINE configs[3])')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit('bench.py: --steps must be at least 1 and --warmup at least 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves (torch.distributed.run, one process per GPU) BEFORE anything in
@@ -1083,7 +1105,10 @@ def main():
     if args.scaling == 'strong':
         c4_model, c4_renderer, c4_cam, c4_poses = build_c4_scene(device)
         gc.collect(); gc.disable()
-        r = strong_scaling_frames(c4_renderer, c4_cam, c4_poses, rank, world, args.steps, args.warmup, barrier, red_dev)
+        last = {}
+        r = strong_scaling_frames(c4_renderer, c4_cam, c4_poses, rank, world, args.steps, args.warmup, barrier, red_dev, last_out=last)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, last)
         if rank == 0:
             elapsed = r.pop('elapsed')
             print(json.dumps({
@@ -1119,7 +1144,8 @@ def main():
     _dbg = []
     for i in range(args.steps):
         _t = time.perf_counter()
-        samples += step(args.warmup + i)['n_samples']
+        out = step(args.warmup + i)
+        samples += out['n_samples']
         _dbg.append(time.perf_counter() - _t)
     barrier()
     elapsed_now = time.perf_counter() - t0
@@ -1133,6 +1159,29 @@ def main():
         s = torch.tensor([samples], device=red_dev, dtype=torch.int64)
         dist.all_reduce(s)
         samples = int(s.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)    # before anything else renders: the buffers are the renderer's workspace
+    del out
+
+    def core_result():
+        """Rank 0: the headline fields, from the timed steps alone."""
+        rays = W * H * args.steps * world
+        return {
+            'metric': 'Mrays/s (INGP lego)', 'value': round(rays / elapsed / 1e6, 4), 'unit': 'Mrays/s', 'n_gpus': world, 'steps': args.steps,
+            'warmup': args.warmup, 'ms_per_step': round(elapsed / args.steps * 1e3, 4), 'higher_is_better': True, 'scaling': 'weak',
+            'vs_baseline': None, 'dtype': 'f16 (tables, weights, activations) / f32 (accumulate, march, composite)', 'data': 'synthetic',
+            'config': {'workload': 'ingp_lego: 800x800 image render per rank per step (640000 rays), solid-sphere occupancy r<0.35, '
+                                   'random-init hash grid (T=2^19, L=16, F=2) + 64-wide MLPs, seed 0, 100 seeded orbit poses',
+                       'rays_per_step_per_gpu': W * H, 'samples_per_ray': round(samples / rays, 3), 'parallelism': f'rays x{world} (weak)'},
+            'msamples_per_s': round(samples / elapsed / 1e6, 3)}
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps({**core_result(), 'full': False}), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- secondary metric: 3DGS rasterizer forward / forward+backward on the 1 M-Gaussian synthetic scene (every rank its own copy)
     gs_res = None
@@ -1163,8 +1212,6 @@ def main():
 
     def headline_result():
         """Rank 0: the line's headline part -- value, rooflines of the frame's two kernels, the 3DGS secondary -- without the training legs."""
-        rays = W * H * args.steps * world
-        value = rays / elapsed / 1e6
         # the dominant kernel, timed on the poses the timed region of THIS rank rendered (all of them up to 20, else an even subset)
         timed_poses = [poses[((args.warmup + i) * world + rank) % N_POSES] for i in range(args.steps)]
         if len(timed_poses) > 20:
@@ -1183,13 +1230,7 @@ def main():
         enc_pmc, enc_pmc_src = pmc_entry(pmc_all, DOMINANT_KERNEL, 'ngp_net.hip')
         mlp_pmc, mlp_pmc_src = pmc_entry(pmc_all, 'k_ngp_mlp<SRC_TILED>', 'ngp_net.hip')
         result = {
-            'metric': 'Mrays/s (INGP lego)', 'value': round(value, 4), 'unit': 'Mrays/s', 'n_gpus': world, 'steps': args.steps,
-            'warmup': args.warmup, 'ms_per_step': round(elapsed / args.steps * 1e3, 4), 'higher_is_better': True, 'scaling': 'weak',
-            'vs_baseline': None, 'dtype': 'f16 (tables, weights, activations) / f32 (accumulate, march, composite)', 'data': 'synthetic',
-            'config': {'workload': 'ingp_lego: 800x800 image render per rank per step (640000 rays), solid-sphere occupancy r<0.35, '
-                                   'random-init hash grid (T=2^19, L=16, F=2) + 64-wide MLPs, seed 0, 100 seeded orbit poses',
-                       'rays_per_step_per_gpu': W * H, 'samples_per_ray': round(samples / rays, 3), 'parallelism': f'rays x{world} (weak)'},
-            'msamples_per_s': round(samples / elapsed / 1e6, 3),
+            **core_result(), 'full': True,
             # dominant kernel on SURVEY 8(d)'s algorithmic bytes (512 B of table reads per live sample) against the HBM peak.  The 24.4 MB table
             # is L2 / Infinity-Cache resident, so HBM is NOT what limits the kernel: `limiter` names the resource that does (L1 tag lookups,
             # from the PMC counters in profiles/), and `traffic` is the memory-side traffic per launch measured there.

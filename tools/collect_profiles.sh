@@ -7,8 +7,8 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/profiles_raw
 mkdir -p $O
-# the driver's command line (bench.py --steps 20 --warmup 5, every leg): the per-kernel averages of the InstantNGP kernels must agree with the bench line
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_stats -- python3 $R/bench.py --steps 20 --warmup 5 > $O/bench_stats.log 2>&1
+# the full bench command (bench.py --full --steps 20 --warmup 5, every leg): the per-kernel averages of the InstantNGP kernels must agree with the bench line
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_stats -- python3 $R/bench.py --full --steps 20 --warmup 5 > $O/bench_stats.log 2>&1
 # the 3DGS kernels at ONE size (the bench command runs 1 M and 6 M Gaussians through the same kernel names)
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/gs_stats -- python3 $R/tools/bench_gs.py 1000000 20 > $O/gs_stats.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/gs6_stats -- python3 $R/tools/bench_gs.py 6000000 5 > $O/gs6_stats.log 2>&1

@@ -34,7 +34,7 @@ if stats:
     durations = {}
     for r in csv.DictReader(open(stats[-1])):
         durations[short(r['Name'])] = {'calls': int(r['Calls']), 'avg_us': round(float(r['AverageNs']) / 1e3, 3), 'total_us': round(float(r['TotalDurationNs']) / 1e3, 1)}
-    durations['_meta'] = {'round': ROUND, 'command': 'python bench.py --steps 20 --warmup 5',
+    durations['_meta'] = {'round': ROUND, 'command': 'python bench.py --full --steps 20 --warmup 5',
                           'csrc_sha': {p.name: _hl.sha256(p.read_bytes()).hexdigest()[:16] for p in sorted((ROOT / 'nerficg_amd' / 'csrc').glob('*.h*'))}}
     (OUT / 'kernel_durations.json').write_text(json.dumps(durations, indent=1, sort_keys=True))
 for tag, name in (('gs_stats', f'{ROUND}_gs_kernel_stats.csv'), ('gs6_stats', f'{ROUND}_gs6m_kernel_stats.csv')):
