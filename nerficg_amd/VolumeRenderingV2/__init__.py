@@ -11,8 +11,6 @@ Python level); the C ABI underneath takes raw pointers.  Differences, all docume
 """
 from __future__ import annotations
 
-import os
-
 import torch
 from torch.amp import custom_bwd, custom_fwd
 
@@ -26,7 +24,6 @@ __all__ = [
 ]
 
 _f32, _i32, _i64, _u8 = torch.float32, torch.int32, torch.int64, torch.uint8
-_PARKED_MARCH = os.environ.get('NRC_TRAIN_PARK', '1') != '0'  # 0: raymarching_train marches twice instead of expanding parked positions
 
 
 def _chk(*pairs) -> None:
@@ -113,7 +110,7 @@ def raymarching_train(rays_o, rays_d, hits_t, density_bitfield, cascades: int, s
     ws = torch.empty(max(int(lib.nrc_raymarching_train_ws_bytes(n, int(max_samples))), 1), dtype=_u8, device=dev)
     args = (_lib.ptr(rays_o), _lib.ptr(rays_d), _lib.ptr(hits_t), _lib.ptr(density_bitfield), int(cascades), float(scale),
             float(exp_step_factor), _lib.ptr(noise), int(grid_size), int(max_samples), n)
-    if sample_capacity is not None and _PARKED_MARCH and 0 < n <= 32768 and int(sample_capacity) > 0:
+    if sample_capacity is not None and 0 < n <= 32768 and int(sample_capacity) > 0:
         # small batch, fixed capacity (a recorded training iteration): count, cut and write as three launches
         total = int(sample_capacity)
         xyzs = torch.empty(total, 3, dtype=_f32, device=dev)
@@ -128,7 +125,7 @@ def raymarching_train(rays_o, rays_d, hits_t, density_bitfield, cascades: int, s
         raise RuntimeError('raymarching_train: sizing the sample buffers reads counter[0] on the host, which a stream capture cannot do -- '
                            'pass sample_capacity (InstantNGPRenderer.sample_capacity / nerficg_amd.graphs.instant_ngp_iteration)')
     total = None
-    mailbox = _lib.HostMailbox.for_device(dev) if (sample_capacity is None and _PARKED_MARCH and COUNT_MAILBOX and 0 < n <= 32768) else None
+    mailbox = _lib.HostMailbox.for_device(dev) if (sample_capacity is None and COUNT_MAILBOX and 0 < n <= 32768) else None
     if mailbox is not None:
         # the count reaches the host through mapped host memory that the scan kernel writes and this thread polls: no device-to-host copy, no
         # stream synchronisation (35 us of idle GPU per training iteration through the copy; the same mechanism as the image pipeline's row count)
@@ -156,7 +153,7 @@ def raymarching_train(rays_o, rays_d, hits_t, density_bitfield, cascades: int, s
         _lib.check(lib.nrc_raymarching_train_cap_overflow(n, total, _lib.ptr(counter), _lib.ptr(rays_a), _lib.ptr(xyzs), _lib.ptr(dirs), _lib.ptr(deltas),
                                                           _lib.ptr(ts), _lib.ptr(overflow), st), 'raymarching_train(cap)')
     _lib.check(lib.nrc_raymarching_train_write(*args, _lib.ptr(rays_a), _lib.ptr(xyzs), _lib.ptr(dirs), _lib.ptr(deltas),
-                                               _lib.ptr(ts), _lib.ptr(ws) if _PARKED_MARCH else None, st), 'raymarching_train(write)')
+                                               _lib.ptr(ts), _lib.ptr(ws), st), 'raymarching_train(write)')
     return [rays_a, xyzs, dirs, deltas, ts, counter] + ([overflow] if overflow is not None and return_overflow else [])
 
 

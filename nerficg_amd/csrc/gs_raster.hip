@@ -174,8 +174,7 @@ __device__ __forceinline__ void tile_rect(const float* p, int radius, int gx, in
 // Splat record: what the two render kernels need of a Gaussian, in ONE 64-byte line (they used to gather xy, conic + opacity and rgb from
 // three arrays = three cache lines per list entry), plus the per-Gaussian part of their block tests precomputed once instead of once per
 // (tile, Gaussian) pair:  q0 = {X, Y, A, B}  q1 = {C, o, ext_x, ext_y}  q2 = {tau / A, det / A^2, B / A, y_off}  q3 = {r, g, b, -}
-// (round 4: the colour has the last vector to itself -- the one part of the record that the SH evaluation produces; the colour pass of the
-// preprocessing (k_preprocess<2>, side stream) writes it with one 16-byte store, the geometry pass (k_preprocess<1>) the other three vectors)
+// (round 4: the colour has the last vector to itself -- the one part of the record that the SH evaluation produces)
 //   alpha >= 1/255  <=>  A dx^2 + 2 B dx dy + C dy^2 <= tau = 2 ln(255 o)   (the ellipse a pixel must be inside to blend the Gaussian)
 //   ext_x, ext_y = half extents of that ellipse's bounding box (margins: x 1.001 + 0.01 px);  ext_x = -1: never blends;  +inf: not an ellipse
 //   y_off = (B / C) sqrt(tau C / det): the ellipse's leftmost / rightmost points lie at Y +- y_off
@@ -196,10 +195,7 @@ __device__ __forceinline__ void write_splat_record(float4 (&rec)[4], float X, fl
     rec[0] = make_float4(X, Y, A, B); rec[1] = make_float4(C, o, ex, ey);
     rec[2] = make_float4(ta, da, ba, yoff); rec[3] = make_float4(col[0], col[1], col[2], 0.f);
 }
-// one Gaussian; sh_row = its SH coefficients (LDS copy, see k_preprocess).  The same computation whatever the template flags; GEOM: the geometry
-// outputs are stored (radii, depths, screen position, conic + opacity, cov3D, tiles_touched, vectors 0..2 of the record), COLOR: the colour outputs
-// (rgb, clamped, vector 3 of the record).  The two passes of a split preprocessing decide a Gaussian's visibility identically (same arithmetic).
-template <bool GEOM, bool COLOR>
+// one Gaussian; sh_row = its SH coefficients (LDS copy, see k_preprocess)
 __device__ __forceinline__ void preprocess_one(int i, const GsCam& cam, const float* __restrict__ means3D, const float* sh_row,
                                                const float* __restrict__ colors_precomp, const float* __restrict__ opacities,
                                                const float* __restrict__ scales, const float* __restrict__ rotations,
@@ -208,17 +204,13 @@ __device__ __forceinline__ void preprocess_one(int i, const GsCam& cam, const fl
                                                float* __restrict__ conic_opacity, float* __restrict__ rgb, uint8_t* __restrict__ clamped,
                                                float* __restrict__ cov3D, uint32_t* __restrict__ tiles_touched,
                                                uint32_t* __restrict__ tile_counts, bool want_record, float4 (&splat)[4]) {
-    if (GEOM) {
-        radii[i] = 0; tiles_touched[i] = 0; depths[i] = 0.f;
-        points_xy[2 * i] = 0.f; points_xy[2 * i + 1] = 0.f;
+    radii[i] = 0; tiles_touched[i] = 0; depths[i] = 0.f;
+    points_xy[2 * i] = 0.f; points_xy[2 * i + 1] = 0.f;
 #pragma unroll
-        for (int k = 0; k < 4; k++) conic_opacity[4 * i + k] = 0.f;
-    }
-    if (COLOR) {
+    for (int k = 0; k < 4; k++) conic_opacity[4 * i + k] = 0.f;
 #pragma unroll
-        for (int k = 0; k < 3; k++) rgb[3 * i + k] = 0.f;
-        clamped[i] = 0;
-    }
+    for (int k = 0; k < 3; k++) rgb[3 * i + k] = 0.f;
+    clamped[i] = 0;
     const float p[3] = {means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2]};
     float pv[3];
     xform43(p, cam.view, pv);
@@ -232,10 +224,8 @@ __device__ __forceinline__ void preprocess_one(int i, const GsCam& cam, const fl
         act_rotation(rotations + 4 * i, cam.raw, q);
         cov3d(s, cam.scale_modifier, q, c3);
     }
-    if (GEOM) {
 #pragma unroll
-        for (int k = 0; k < 6; k++) cov3D[6 * i + k] = c3[k];
-    }
+    for (int k = 0; k < 6; k++) cov3D[6 * i + k] = c3[k];
     if (pv[2] <= 0.2f) return;
     float ph[4];
     xform44(p, cam.proj, ph);
@@ -260,21 +250,18 @@ __device__ __forceinline__ void preprocess_one(int i, const GsCam& cam, const fl
     tile_rect(pix, my_radius, cam.gx, cam.gy, rmin, rmax);
     if ((rmax[0] - rmin[0]) * (rmax[1] - rmin[1]) == 0) return;
     float col[3] = {0.f, 0.f, 0.f};
-    if (COLOR) {
-        if (colors_precomp) {
+    if (colors_precomp) {
 #pragma unroll
-            for (int k = 0; k < 3; k++) col[k] = colors_precomp[3 * i + k];
-        } else {
-            uint8_t cl;
-            sh_color(cam.D, p, cam.campos, sh_row, col, &cl);
-            clamped[i] = cl;
-        }
-#pragma unroll
-        for (int k = 0; k < 3; k++) rgb[3 * i + k] = col[k];
+        for (int k = 0; k < 3; k++) col[k] = colors_precomp[3 * i + k];
+    } else {
+        uint8_t cl;
+        sh_color(cam.D, p, cam.campos, sh_row, col, &cl);
+        clamped[i] = cl;
     }
+#pragma unroll
+    for (int k = 0; k < 3; k++) rgb[3 * i + k] = col[k];
     const float opacity = cam.raw ? act_sigmoid(opacities[i]) : opacities[i];
     if (want_record) write_splat_record(splat, pix[0], pix[1], conic[0], conic[1], conic[2], opacity, col);  // this thread's row of the LDS image
-    if (!GEOM) return;
     depths[i] = pv[2]; radii[i] = my_radius;
     points_xy[2 * i] = pix[0]; points_xy[2 * i + 1] = pix[1];
     conic_opacity[4 * i] = conic[0]; conic_opacity[4 * i + 1] = conic[1]; conic_opacity[4 * i + 2] = conic[2];
@@ -395,12 +382,7 @@ __device__ __forceinline__ void sh_rows_copy(float* s_sh, int pitch, int row_len
 #ifndef PRE_MAXM
 #define PRE_MAXM 16
 #endif
-// PART 0: everything in one pass (tile grids without the span binning, graph captures, armed stage timer).  PART 1: the geometry outputs -- what
-// the depth sort and the binning wait for (44 B read per Gaussian instead of 236).  PART 2: the colour outputs (rgb, clamped, vector 3 of the
-// records): the same per-Gaussian computation, the 192-byte SH rows staged through LDS, on a FEW persistent workgroups (grid-stride over the
-// 128-Gaussian blocks) of a side stream, so that it runs NEXT TO the geometry pass, the depth sort and the binning, whose kernels are
-// latency-bound and leave the memory system idle, without taking their compute units (round 4; joined before nrc_gs_preprocess returns).
-template <int PART, bool SPLIT = false>
+template <bool SPLIT = false>
 __global__ void __launch_bounds__(PRE_BLOCK) k_preprocess(int P, GsCam cam_arg, const float* __restrict__ pose, const float* __restrict__ means3D, const float* __restrict__ shs,
                                                           const float* __restrict__ shs_rest,
                                                           const float* __restrict__ colors_precomp, const float* __restrict__ opacities,
@@ -410,15 +392,15 @@ __global__ void __launch_bounds__(PRE_BLOCK) k_preprocess(int P, GsCam cam_arg, 
                                                           float* __restrict__ conic_opacity, float* __restrict__ rgb, uint8_t* __restrict__ clamped,
                                                           float* __restrict__ cov3D, uint32_t* __restrict__ tiles_touched,
                                                           uint32_t* __restrict__ tile_counts, float4* __restrict__ splat, uint32_t* __restrict__ sort_hdr) {
-    __shared__ __attribute__((aligned(16))) float s_sh[PART == 1 ? PRE_BLOCK * 12 : PRE_BLOCK * (3 * PRE_MAXM + 1)];
-    if (PART != 2 && sort_hdr && blockIdx.x == 0)   // digit totals, row totals and tile tickets of the depth sort behind this kernel start at zero
+    __shared__ __attribute__((aligned(16))) float s_sh[PRE_BLOCK * (3 * PRE_MAXM + 1)];
+    if (sort_hdr && blockIdx.x == 0)   // digit totals, row totals and tile tickets of the depth sort behind this kernel start at zero
         for (int k = threadIdx.x; k < RS_HDR_WORDS; k += PRE_BLOCK) sort_hdr[k] = 0u;
     const GsCam cam = cam_with_pose(cam_arg, pose);
     const int row_len = 3 * cam.M, pitch = row_len + 1;
     const int n_blocks = (P + PRE_BLOCK - 1) / PRE_BLOCK;
     for (int blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
         const int first = blk * PRE_BLOCK, i = first + threadIdx.x;
-        if (PART != 1 && shs) {
+        if (shs) {
             sh_rows_copy<true, SHB_U, SPLIT>(s_sh, pitch, row_len, min(PRE_BLOCK, P - first), (size_t)first, const_cast<float*>(shs), const_cast<float*>(shs_rest), PRE_BLOCK);
             __syncthreads();
         }
@@ -427,28 +409,22 @@ __global__ void __launch_bounds__(PRE_BLOCK) k_preprocess(int P, GsCam cam_arg, 
         // Rows of culled Gaussians hold zeros or stale bytes: no tile list ever names them.
         float4 rec[4] = {};
         if (i < P)
-            preprocess_one<PART != 2, PART != 1>(i, cam, means3D, s_sh + threadIdx.x * pitch, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii, depths,
-                                                 points_xy, conic_opacity, rgb, clamped, cov3D, tiles_touched, tile_counts, splat != nullptr, rec);
+            preprocess_one(i, cam, means3D, s_sh + threadIdx.x * pitch, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii, depths,
+                           points_xy, conic_opacity, rgb, clamped, cov3D, tiles_touched, tile_counts, splat != nullptr, rec);
         if (splat) {
-            if (PART == 2) {   // vector 3 only: one 16-byte store per Gaussian
-                if (i < P) splat[4 * (size_t)i + 3] = rec[3];
-            } else {
-                constexpr int NV = PART == 0 ? 4 : 3;   // vectors of a record this pass writes
-                float4* s_rec = reinterpret_cast<float4*>(s_sh);
-                __syncthreads();
+            float4* s_rec = reinterpret_cast<float4*>(s_sh);
+            __syncthreads();
 #pragma unroll
-                for (int k = 0; k < NV; k++) s_rec[NV * threadIdx.x + k] = rec[k];
-                __syncthreads();
-                const int nv = NV * min(PRE_BLOCK, P - first);
-                float4* dst = splat + 4 * (size_t)first;
+            for (int k = 0; k < 4; k++) s_rec[4 * threadIdx.x + k] = rec[k];
+            __syncthreads();
+            const int nv = 4 * min(PRE_BLOCK, P - first);
+            float4* dst = splat + 4 * (size_t)first;
 #pragma unroll
-                for (int k = 0; k < NV; k++) {
-                    const int e = threadIdx.x + PRE_BLOCK * k;
-                    if (e < nv) dst[NV == 4 ? e : 4 * (e / 3) + e % 3] = s_rec[e];
-                }
+            for (int k = 0; k < 4; k++) {
+                const int e = threadIdx.x + PRE_BLOCK * k;
+                if (e < nv) dst[e] = s_rec[e];
             }
         }
-        if (PART == 2) __syncthreads();   // the SH rows of the next block overwrite the staging area
     }
 }
 
@@ -1994,24 +1970,6 @@ struct BinWs {
     int nblk, ngroups, item_cap;
     int64_t cap, words, n_status;
 };
-// The library's one side stream (per device, created on first use) and the two events of its fork / join: the colour pass of the
-// preprocessing runs there while the caller's stream works through the depth sort and the binning.  Never used inside a stream capture and
-// never while the stage timer is armed (the pass then runs in line, where its time can be attributed).
-struct GsSide { hipStream_t stream; hipEvent_t fork, join; bool ok; };
-GsSide* gs_side() {
-    static GsSide side[64] = {};
-    static bool tried[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-    if (!tried[dev]) {
-        tried[dev] = true;
-        GsSide& s = side[dev];
-        s.ok = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) == hipSuccess &&
-               hipEventCreateWithFlags(&s.fork, hipEventDisableTiming) == hipSuccess &&
-               hipEventCreateWithFlags(&s.join, hipEventDisableTiming) == hipSuccess;
-    }
-    return side[dev].ok ? &side[dev] : nullptr;
-}
 int64_t gs_default_span_cap(int P) { return 4 * (int64_t)(P > 0 ? P : 1) + 65536; }
 BinWs gs_bin_ws(uint32_t* base, int P, int gx, int gy, int64_t cap) {
     BinWs w;
@@ -2036,13 +1994,6 @@ BinWs gs_bin_ws(uint32_t* base, int P, int gx, int gy, int64_t cap) {
     return w;
 }
 
-// NRC_GS_OVERLAP=1 (read once): the colour outputs of the preprocessing as a separate pass on the side stream (k_preprocess<1> + <2>).  OFF by
-// default -- measured at 1 M / 6 M Gaussians: 0.48 / 1.50 ms per forward in one pass, 0.50-0.58 / 1.78-1.95 ms split, whatever the number of
-// persistent workgroups: next to a kernel that streams 233 MB the latency-bound sort passes take 2-4 x as long (k_depth_keys 17 -> 33 us, the
-// first two radix passes 16 -> 64 and 35 us), which costs more than the 45 us the geometry pass saves over the single pass.
-const bool g_gs_no_overlap = [] { const char* e = getenv("NRC_GS_OVERLAP"); return !(e && e[0] == '1'); }();
-// NRC_GS_COLOR_BLOCKS (read once): persistent workgroups of the colour pass per compute unit (default 2)
-const int g_gs_color_blocks_per_cu = [] { const char* e = getenv("NRC_GS_COLOR_BLOCKS"); const int v = e ? atoi(e) : 0; return v > 0 && v <= 16 ? v : 2; }();
 // The camera block of a frame (GS_POSE_FLOATS) from a camera-to-world pose that lives on the DEVICE: what GaussianSplatting/Renderer.py:60-74 computes on the
 // host -- viewmatrix = w2c^T = [[R, 0], [-(R^T t)^T, 1]], projmatrix = viewmatrix @ P^T, campos = t -- as one launch of one wave (the tensor-op form was
 // eleven launches of 4-5 us in front of every training step: transpose, matrix-vector product, negation, four concatenations, two fills, a 4x4 product).
@@ -2153,27 +2104,11 @@ int nrc_gs_preprocess(int32_t P, int32_t D, int32_t M, int32_t W, int32_t H, con
             return NRC_ERR_INVALID;
         if (shs && M > PRE_MAXM) return NRC_ERR_UNSUPPORTED;
         const BinWs w = lds_path ? gs_bin_ws(bin_hist, P, cam.gx, cam.gy, span_capacity > 0 ? span_capacity : gs_default_span_cap(P)) : BinWs{};
-        // The colour outputs (192 of the 236 bytes read per Gaussian are SH coefficients) on the side stream, forked HERE -- in front of the geometry
-        // pass, so that no event sits between the kernels of the caller's stream -- and joined at the end of this call.  In line (one pass) for
-        // the fallback binning, given colours, inside a stream capture, and while the stage timer is armed.
-        hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-        (void)hipStreamIsCapturing(s, &capturing);
-        GsSide* side = (lds_path && shs && !colors_precomp && capturing == hipStreamCaptureStatusNone && !g_nrc_stage_timer_armed && !g_gs_no_overlap) ? gs_side() : nullptr;
-        bool forked = false;
         const int pre_blocks = (int)nrc_cdiv(P, PRE_BLOCK);
 #define GS_PRE_ARGS P, cam, camera_dev, means3D, shs, shs_rest, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii, depths, points_xy, conic_opacity, rgb, \
                     clamped, cov3D, tiles_touched, lds_path ? (uint32_t*)nullptr : tile_counts, (float4*)splat_records, lds_path ? w.hdr : (uint32_t*)nullptr
-        if (side && hipEventRecord(side->fork, s) == hipSuccess && hipStreamWaitEvent(side->stream, side->fork, 0) == hipSuccess) {
-            const int cus = 256;   // MI355X; only the experiment's grid size depends on it
-            if (shs_rest) hipLaunchKernelGGL((k_preprocess<2, true>), dim3(pre_blocks < g_gs_color_blocks_per_cu * cus ? pre_blocks : g_gs_color_blocks_per_cu * cus), dim3(PRE_BLOCK), 0, side->stream, GS_PRE_ARGS);
-            else hipLaunchKernelGGL((k_preprocess<2, false>), dim3(pre_blocks < g_gs_color_blocks_per_cu * cus ? pre_blocks : g_gs_color_blocks_per_cu * cus), dim3(PRE_BLOCK), 0, side->stream, GS_PRE_ARGS);
-            forked = hipEventRecord(side->join, side->stream) == hipSuccess;
-            if (!forked) (void)hipStreamSynchronize(side->stream);   // cannot happen short of a broken runtime: stay correct
-            hipLaunchKernelGGL((k_preprocess<1, false>), dim3(pre_blocks), dim3(PRE_BLOCK), 0, s, GS_PRE_ARGS);
-        } else {
-            if (shs_rest) hipLaunchKernelGGL((k_preprocess<0, true>), dim3(pre_blocks), dim3(PRE_BLOCK), 0, s, GS_PRE_ARGS);
-            else hipLaunchKernelGGL((k_preprocess<0, false>), dim3(pre_blocks), dim3(PRE_BLOCK), 0, s, GS_PRE_ARGS);
-        }
+        if (shs_rest) hipLaunchKernelGGL((k_preprocess<true>), dim3(pre_blocks), dim3(PRE_BLOCK), 0, s, GS_PRE_ARGS);
+        else hipLaunchKernelGGL((k_preprocess<false>), dim3(pre_blocks), dim3(PRE_BLOCK), 0, s, GS_PRE_ARGS);
         NRC_STAGE(s, "k_preprocess");
 #undef GS_PRE_ARGS
         if (lds_path) {
@@ -2200,7 +2135,6 @@ int nrc_gs_preprocess(int32_t P, int32_t D, int32_t M, int32_t W, int32_t H, con
             hipLaunchKernelGGL(k_item_scan, dim3((unsigned)nrc_cdiv(cam.gx, IS_XL), cam.gy), dim3(1024), 0, s, cam.gx, cam.gy, w.item_cap, w.nitems, w.ioff, w.cnt2, w.tcount,
                                w.hdr + RS_HDR_TICKET + 5, list_cap, ranges, tile_fill, num_rendered, count_mailbox, mailbox_ticket);
             NRC_STAGE(s, "k_item_scan");
-            if (forked && hipStreamWaitEvent(s, side->join, 0) != hipSuccess) (void)hipStreamSynchronize(side->stream);   // the colours are in place for whatever the caller enqueues next
         }
     }
     if (!(P > 0 && lds_path)) {

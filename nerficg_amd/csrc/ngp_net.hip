@@ -324,15 +324,13 @@ __device__ __forceinline__ void fetch_dir(const QueryIn& in, int64_t i, float& d
 // channels (measured: 0.262 ms vs 0.22 ms per 2 Mi samples).  One lane per sample, all 16 levels.
 template <int SRC>
 __global__ void __launch_bounds__(256) k_grid_encode(QueryIn in, int64_t base, int64_t n, const __half2* __restrict__ table, GridCfg g,
-                                                         uint4* __restrict__ feat, int narrow_levels, int hashed_mode, int lane_shape = 0) {
+                                                         uint4* __restrict__ feat, int narrow_levels, int lvl_range, int lane_shape = 0) {
     int64_t bid = blockIdx.x;
     if constexpr (SRC == SRC_TILED) {
-        // workgroups are dealt round-robin over the 8 XCDs; with NRC_ENC_XCD each XCD takes a CONTIGUOUS eighth of the launch's slots instead of
-        // every eighth workgroup, so that neighbouring bricks (which share table lines) meet in the same L2
-        if (hashed_mode & (1 << 28)) {
-            const int64_t g8 = (int64_t)gridDim.x >> 3;
-            if (bid < 8 * g8) bid = (bid & 7) * g8 + (bid >> 3);
-        }
+        // workgroups are dealt round-robin over the 8 XCDs; each XCD takes a CONTIGUOUS eighth of the launch's slots instead of every eighth
+        // workgroup, so that neighbouring bricks (which share table lines) meet in the same L2.  Measured: 612 -> 591 us per launch (mean of 24 poses)
+        const int64_t g8 = (int64_t)gridDim.x >> 3;
+        if (bid < 8 * g8) bid = (bid & 7) * g8 + (bid >> 3);
     }
     int64_t j = bid * 256 + threadIdx.x;
     bool remapped = false;
@@ -371,14 +369,10 @@ __global__ void __launch_bounds__(256) k_grid_encode(QueryIn in, int64_t base, i
     const __amdgpu_buffer_rsrc_t trs = make_table_rsrc(table, g.total_entries * 4u);
     uint4* out = feat + ((j >> 5) * 4) * 32 + (j & 31);
     const int rot = (int)((j >> 5) & 3);
-    const int lvl_lo = (hashed_mode >> 4) & 0xff, lvl_hi = (hashed_mode >> 12) & 0xff;  // NRC_ENC_LEVELS (measurement only; 0 .. 16 normally)
-    const int uniform_levels = (hashed_mode >> 20) & 0xff;                             // levels that try the wave-uniform scalar path first
-    const bool skip_last_group = ((hashed_mode >> 29) & 1) != 0;                       // NRC_ENC_FINE_SPLIT: levels 12-15 come from k_grid_encode_fine
-    hashed_mode &= 0xf;
-    const uint32_t* __restrict__ table32 = reinterpret_cast<const uint32_t*>(table);
+    const int lvl_lo = lvl_range & 0xff, lvl_hi = (lvl_range >> 8) & 0xff;   // NRC_ENC_LEVELS (measurement only; 0 .. 16 normally)
     // gridDim.y == 4: one group of four levels per workgroup row (small batches: four times the waves, a quarter of the dependent gathers each --
     // a 264 K-sample training batch is ~4 waves per SIMD in all and runs at the latency of ONE wave's sixteen gather rounds otherwise)
-    const int grp_begin = gridDim.y == 4 ? (int)blockIdx.y : 0, grp_end = gridDim.y == 4 ? grp_begin + 1 : (skip_last_group ? 3 : 4);
+    const int grp_begin = gridDim.y == 4 ? (int)blockIdx.y : 0, grp_end = gridDim.y == 4 ? grp_begin + 1 : 4;
 #pragma unroll 1
     for (int grp = grp_begin; grp < grp_end; grp++) {
         uint32_t v[4] = {0u, 0u, 0u, 0u};
@@ -388,19 +382,13 @@ __global__ void __launch_bounds__(256) k_grid_encode(QueryIn in, int64_t base, i
                 const int level = 4 * grp + q;
                 if (level < lvl_lo || level >= lvl_hi) continue;   // scalar, wave-uniform
                 Corner8 c;
-                float f0 = 0.f, f1 = 0.f;
-                bool have = false;
-                if constexpr (SRC == SRC_TILED) {   // rows of the tiled layout are spatially compact: try the scalar-cache path on the coarse levels
-                    if (level < uniform_levels)
-                        have = g.hashed[level] ? grid_level_features_uniform<true>(table32, px, py, pz, g.scale[level], g.res[level], g.size[level], g.offset[level], f0, f1)
-                                               : grid_level_features_uniform<false>(table32, px, py, pz, g.scale[level], g.res[level], g.size[level], g.offset[level], f0, f1);
-                }
-                if (!have) {
-                    if (g.hashed[level]) grid_corners_u<true>(px, py, pz, g.scale[level], g.res[level], g.size[level], g.offset[level], c);
-                    else grid_corners_u<false>(px, py, pz, g.scale[level], g.res[level], g.size[level], g.offset[level], c);
+                float f0, f1;
+                if (g.hashed[level]) {   // (the narrow levels are the leading dense ones: launch_encode)
+                    grid_corners_u<true>(px, py, pz, g.scale[level], g.res[level], g.size[level], g.offset[level], c);
+                    grid_level_features_hashed(trs, c, f0, f1);
+                } else {
+                    grid_corners_u<false>(px, py, pz, g.scale[level], g.res[level], g.size[level], g.offset[level], c);
                     if (level < narrow_levels) grid_level_features_narrow(trs, c, f0, f1);
-                    else if (g.hashed[level] && hashed_mode == 1) grid_level_features_hashed(trs, c, f0, f1);
-                    else if (g.hashed[level] && hashed_mode == 2) grid_level_features_pair(trs, c, f0, f1);
                     else grid_level_features(trs, c, f0, f1);
                 }
                 const __half2 h = __floats2half2_rn(f0, f1);
@@ -417,54 +405,6 @@ __global__ void __launch_bounds__(256) k_grid_encode(QueryIn in, int64_t base, i
     }
 }
 
-// Experiment (round-3 review, item 5b; NRC_ENC_FINE_SPLIT=1): the four finest levels in a launch of their own, ONE LEVEL PER XCD.  The whole table is
-// 24.4 MB and an XCD's L2 4 MB: with all sixteen levels in one kernel every L2 sees all of it (hit rate 0.70, 7.5 of the 7.9 L1 misses per sample
-// come from levels 12-15 and 30 % of those go on to the fabric).  Here workgroup b works on level 12 + (b & 3) for the slots of half (b >> 2) & 1
-// (workgroups are dealt round-robin over the XCDs), so each L2 holds ONE 2 MB level.  Price: the position of a sample is derived five times instead
-// of once and the level's 4 bytes are stored into the 16-byte group of the fragment-major record on their own.  Same values in the same places.
-template <int SRC>
-__global__ void __launch_bounds__(256) k_grid_encode_fine(QueryIn in, int64_t base, int64_t n, const __half2* __restrict__ table, GridCfg g, uint4* __restrict__ feat,
-                                                              int first_level, int lane_shape) {
-    const int xcd = (int)(blockIdx.x & 7u);
-    const int level = first_level + (xcd & 3);
-    const int64_t per_half = (int64_t)(gridDim.x >> 3);
-    const int64_t bid = (int64_t)(xcd >> 2) * per_half + (int64_t)(blockIdx.x >> 3);
-    int64_t j = bid * 256 + threadIdx.x;
-    if constexpr (SRC == SRC_TILED) {
-        if (in.n_rows_dev) {
-            const int64_t have = (int64_t)in.n_rows_dev[0] * 64 - base;
-            n = have < n ? have : n;
-        }
-        if (lane_shape != 0) {   // the same bricks as k_grid_encode
-            const int lu = (lane_shape >> 4) & 7, lv = lane_shape & 7, ls = 6 - lu - lv;
-            const int64_t g1024 = (base + j) & ~(int64_t)1023;
-            const int w = (int)((j >> 6) & 15), l = (int)(j & 63);
-            const int iu = l & ((1 << lu) - 1), iv = (l >> lu) & ((1 << lv) - 1), is = l >> (lu + lv);
-            const int gu = w & ((NRC_TILE_W >> lu) - 1), gv = (w >> (NRC_TILE_W_LOG2 - lu)) & ((NRC_TILE_H >> lv) - 1), gs = w >> (6 - lu - lv);
-            j = g1024 + ((int64_t)((gs << ls) + is) << 6) + NRC_TILE_W * ((gv << lv) + iv) + (gu << lu) + iu - base;
-        }
-    }
-    if (j >= n || j < 0) return;
-    float px, py, pz;
-    in.x01_out = nullptr;
-    const int state = fetch_pos<SRC, false>(in, base + j, px, py, pz);
-    if (state < 0) return;
-    const bool live = state > 0;
-    const __amdgpu_buffer_rsrc_t trs = make_table_rsrc(table, g.total_entries * 4u);
-    const int rot = (int)((j >> 5) & 3);
-    uint32_t* out = reinterpret_cast<uint32_t*>(feat + ((j >> 5) * 4) * 32 + (j & 31) + ((3 + rot) & 3) * 32) + (level - first_level);
-    uint32_t v = 0u;
-    if (live) {
-        Corner8 c;
-        float f0, f1;
-        grid_corners_u<true>(px, py, pz, g.scale[level], g.res[level], g.size[level], g.offset[level], c);
-        grid_level_features_hashed(trs, c, f0, f1);
-        const __half2 h = __floats2half2_rn(f0, f1);
-        v = *reinterpret_cast<const uint32_t*>(&h);
-    }
-    *out = v;
-}
-
 // Small batches (a training iteration: ~264 K samples, once, right after the optimizer rewrote the fp16 table: every XCD's L2 is cold).  With one
 // lane per sample and all sixteen levels each of the 8 XCDs pulls the whole 24.4 MB table through its own L2 (measured 63-67 us = 0.24 of the
 // HBM roofline on 512 B per sample).  Here workgroup b encodes a level PAIR of sample block b >> 3: workgroups are dealt round-robin over the
@@ -474,7 +414,7 @@ __global__ void __launch_bounds__(256) k_grid_encode_fine(QueryIn in, int64_t ba
 // read once per pair, 8 x 7.7 M records per launch); at this size the positions are 3 MB.  Placement is a speed assumption only: any
 // workgroup-to-XCD mapping gives the same features.
 __global__ void __launch_bounds__(256) k_grid_encode_pairs(QueryIn in, int64_t n, const __half2* __restrict__ table, GridCfg g, uint2* __restrict__ feat,
-                                                           int narrow_levels, int hashed_mode, const int32_t* __restrict__ m_live = nullptr) {
+                                                           int narrow_levels, const int32_t* __restrict__ m_live = nullptr) {
     const int pair = (int)(blockIdx.x & 7u);
     const int64_t j = (int64_t)(blockIdx.x >> 3) * 256 + threadIdx.x;
     if (m_live) n = min(n, ((int64_t)max(*m_live, 0) + 31) / 32 * 32);   // whole MLP tiles of the live rows (the rows behind them hold finite, inert samples)
@@ -494,8 +434,7 @@ __global__ void __launch_bounds__(256) k_grid_encode_pairs(QueryIn in, int64_t n
         if (g.hashed[level]) grid_corners_u<true>(px, py, pz, g.scale[level], g.res[level], g.size[level], g.offset[level], c);
         else grid_corners_u<false>(px, py, pz, g.scale[level], g.res[level], g.size[level], g.offset[level], c);
         if (level < narrow_levels) grid_level_features_narrow(trs, c, f0, f1);
-        else if (g.hashed[level] && hashed_mode == 1) grid_level_features_hashed(trs, c, f0, f1);
-        else if (g.hashed[level] && hashed_mode == 2) grid_level_features_pair(trs, c, f0, f1);
+        else if (g.hashed[level]) grid_level_features_hashed(trs, c, f0, f1);
         else grid_level_features(trs, c, f0, f1);
         const __half2 h = __floats2half2_rn(f0, f1);
         const int grp = level >> 2;
@@ -537,12 +476,13 @@ __device__ __forceinline__ f16v mlp_mfma(const h8& a, const h8& b, const f16v& c
 #ifndef NRC_MLP_WAVES
 #define NRC_MLP_WAVES 2   // workgroups per CU the register budget is set for (= waves per SIMD); A/B builds: -DNRC_MLP_WAVES=3
 #endif
-template <int SRC, int NT>
+template <int SRC>
 __global__ void __launch_bounds__(256, NRC_MLP_WAVES) k_ngp_mlp(QueryIn in, int64_t base, int64_t n, const uint4* __restrict__ feat,
                                                     const h8* __restrict__ ray_sh, const __half* __restrict__ Wd,
                                                     const __half* __restrict__ Wc, float* __restrict__ sigmas, float* __restrict__ rgbs,
                                                     __half* __restrict__ packed) {
     enum { F_D0 = 0, F_DO = 4, F_C0 = 8, F_C1 = 12, F_CO = 20, N_FRAG = 24 };
+    constexpr int NT = 2;
     if constexpr (SRC == SRC_TILED) {
         if (in.n_rows_dev) {   // fixed row capacity: only the rows the march produced (uniform over the launch)
             const int64_t have = (int64_t)in.n_rows_dev[0] * 64 - base;
@@ -824,151 +764,6 @@ __global__ void __launch_bounds__(256, NRC_MLP_WAVES) k_ngp_mlp(QueryIn in, int6
 #undef CO
 }
 
-// ---- encode + both MLPs in ONE kernel (tiled layout, inference) -------------------------------------------------------------------------
-// The encoder is bound by the texture-address path and loses nothing down to 5 waves per SIMD; its MFMA units idle.  Here a wave encodes one
-// ROW of the tiled layout (64 samples, lane = pixel of the tile, all 16 levels) into registers, the two lane halves trade half of their feature
-// dwords with 8 v_permlane32_swap -- after which the four 16-byte feature groups ARE the first-layer B fragments of two 32-sample MFMA tiles
-// (tile A = pixels 0-31: groups 0 and 2, tile B = pixels 32-63: groups 1 and 3; the same fragment-major order k_grid_encode writes to memory)
-// -- and runs the MLP chain of k_ngp_mlp on them, one tile after the other.  No feature buffer (128 B per sample of HBM traffic), no second
-// kernel; the matrix work of one wave runs in the shadow of the other waves' gathers.
-template <int SRC>
-__global__ void __launch_bounds__(256, 4) k_encode_mlp(QueryIn in, int64_t base, int64_t n, const __half2* __restrict__ table, GridCfg g, int narrow_levels,
-                                                       const h8* __restrict__ ray_sh, const __half* __restrict__ Wd, const __half* __restrict__ Wc,
-                                                       __half* __restrict__ packed) {
-    static_assert(SRC == SRC_TILED, "tiled layout only");
-    enum { F_D0 = 0, F_DO = 4, F_C0 = 8, F_C1 = 12, F_CO = 20, N_FRAG = 24 };
-    if constexpr (SRC == SRC_TILED) {
-        if (in.n_rows_dev) {   // fixed row capacity: only the rows the march produced (uniform over the launch)
-            const int64_t have = (int64_t)in.n_rows_dev[0] * 64 - base;
-            n = have < n ? have : n;
-            if (n <= 0) return;
-        }
-    }
-    __shared__ h8 wlds[N_FRAG][64];
-    const int lane = threadIdx.x & 63, r = lane & 31, hh = lane >> 5;
-    for (int f = threadIdx.x >> 6; f < N_FRAG; f += 4) {
-        h8 v;
-        if (f < F_DO) v = load_w_frag<false>(Wd, 32, 64, (f - F_D0) >> 1, (f - F_D0) & 1, r, hh);
-        else if (f < F_C0) v = load_w_head_frag(Wd + 64 * 32, 64, 16, (f - F_DO) & 1, lane);     // as in k_ngp_mlp: the two kernels paint the same picture bit for bit
-        else if (f < F_C1) {
-            const int mt = (f - F_C0) >> 1, sk = (f - F_C0) & 1;
-            v = load_w_frag<false>(Wc, 32, 64, mt, sk, r, hh);
-        } else if (f < F_CO) v = load_w_frag<true>(Wc + 64 * 32, 64, 64, (f - F_C1) >> 2, (f - F_C1) & 3, r, hh);
-        else v = load_w_head_frag(Wc + 64 * 32 + 64 * 64, 64, 16, (f - F_CO) & 1, lane);
-        wlds[f][lane] = v;
-    }
-    __syncthreads();
-    const __amdgpu_buffer_rsrc_t trs = make_table_rsrc(table, g.total_entries * 4u);
-    const int64_t n_rows = (n + 63) / 64;
-    const int64_t wave0 = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (int64_t)gridDim.x * 4;
-    for (int64_t row = wave0; row < n_rows; row += n_waves) {
-        const int64_t j = row * 64 + lane;
-        float px = 0.f, py = 0.f, pz = 0.f;
-        const bool live = j < n && fetch_pos<SRC>(in, base + j, px, py, pz) > 0;
-        const unsigned long long live_mask = __ballot(live);
-        if (live_mask == 0ull) continue;  // a row of holes
-        uint32_t G0[4] = {0u, 0u, 0u, 0u}, G1[4] = {0u, 0u, 0u, 0u}, G2[4] = {0u, 0u, 0u, 0u}, G3[4] = {0u, 0u, 0u, 0u};
-#pragma unroll 1
-        for (int grp = 0; grp < 4; grp++) {
-            uint32_t v[4] = {0u, 0u, 0u, 0u};
-            if (live) {
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const int level = 4 * grp + q;
-                    Corner8 c;
-                    float f0, f1;
-                    if (g.hashed[level]) grid_corners_u<true>(px, py, pz, g.scale[level], g.res[level], g.size[level], g.offset[level], c);
-                    else grid_corners_u<false>(px, py, pz, g.scale[level], g.res[level], g.size[level], g.offset[level], c);
-                    if (level < narrow_levels) grid_level_features_narrow(trs, c, f0, f1);
-                    else if (g.hashed[level]) grid_level_features_hashed(trs, c, f0, f1);
-                    else grid_level_features(trs, c, f0, f1);
-                    const __half2 h = __floats2half2_rn(f0, f1);
-                    v[q] = *reinterpret_cast<const uint32_t*>(&h);
-                    asm volatile("" : "+v"(v[q]));
-                }
-            }
-            // wave-uniform group index: the four groups live in named registers
-            if (grp == 0) { G0[0] = v[0]; G0[1] = v[1]; G0[2] = v[2]; G0[3] = v[3]; }
-            else if (grp == 1) { G1[0] = v[0]; G1[1] = v[1]; G1[2] = v[2]; G1[3] = v[3]; }
-            else if (grp == 2) { G2[0] = v[0]; G2[1] = v[1]; G2[2] = v[2]; G2[3] = v[3]; }
-            else { G3[0] = v[0]; G3[1] = v[1]; G3[2] = v[2]; G3[3] = v[3]; }
-        }
-        // lanes 32-63 of G0 / G2 <-> lanes 0-31 of G1 / G3: lane 32 + r receives pixel r's groups 1 and 3 (k-half hh = 1 of tile A), lane r
-        // receives pixel 32 + r's groups 0 and 2 (k-half hh = 0 of tile B)
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const auto s01 = __builtin_amdgcn_permlane32_swap(G0[q], G1[q], false, false);
-            G0[q] = s01[0]; G1[q] = s01[1];
-            const auto s23 = __builtin_amdgcn_permlane32_swap(G2[q], G3[q], false, false);
-            G2[q] = s23[0]; G3[q] = s23[1];
-        }
-        const int32_t rt = tile_of(in.row_tile[(base + row * 64) >> 6]);
-#pragma unroll 1
-        for (int u = 0; u < 2; u++) {
-            uint4 b0, b1;
-            if (u == 0) { b0 = make_uint4(G0[0], G0[1], G0[2], G0[3]); b1 = make_uint4(G2[0], G2[1], G2[2], G2[3]); }
-            else { b0 = make_uint4(G1[0], G1[1], G1[2], G1[3]); b1 = make_uint4(G3[0], G3[1], G3[2], G3[3]); }
-            const bool valid = (live_mask >> (32 * u + r)) & 1ull;
-            if (__ballot(valid) == 0ull) continue;
-            h8 B[2], X[2], H[4], HB[2][2];
-            f16v acc[2];
-            f4v o[2];
-            B[0] = *reinterpret_cast<const h8*>(&b0);
-            B[1] = *reinterpret_cast<const h8*>(&b1);
-            X[0] = ray_sh[((int64_t)rt * 2 + hh) * 64 + 32 * u + r];
-            acc[0] = zero16(); acc[1] = zero16(); o[0] = f4v{0.f, 0.f, 0.f, 0.f}; o[1] = o[0];
-#pragma unroll
-            for (int mt = 0; mt < 2; mt++)
-#pragma unroll
-                for (int sk = 0; sk < 2; sk++) acc[mt] = NRC_MFMA(wlds[F_D0 + 2 * mt + sk][lane], B[sk], acc[mt]);
-#pragma unroll
-            for (int mt = 0; mt < 2; mt++)
-#pragma unroll
-                for (int gq = 0; gq < 2; gq++) H[2 * mt + gq] = acc_to_frag_relu(acc[mt], gq);
-            head_split(H, HB);
-#pragma unroll
-            for (int sk = 0; sk < 2; sk++)
-#pragma unroll
-                for (int nb = 0; nb < 2; nb++) o[nb] = NRC_MFMA16(wlds[F_DO + sk][lane], HB[nb][sk], o[nb]);
-            X[1] = head_join(o[0], o[1]);
-            const _Float16 h0 = X[1][0];
-            acc[0] = zero16(); acc[1] = zero16();
-#pragma unroll
-            for (int mt = 0; mt < 2; mt++)
-#pragma unroll
-                for (int sk = 0; sk < 2; sk++) acc[mt] = NRC_MFMA(wlds[F_C0 + 2 * mt + sk][lane], X[sk], acc[mt]);
-#pragma unroll
-            for (int mt = 0; mt < 2; mt++)
-#pragma unroll
-                for (int gq = 0; gq < 2; gq++) H[2 * mt + gq] = acc_to_frag_relu(acc[mt], gq);
-            acc[0] = zero16(); acc[1] = zero16();
-#pragma unroll
-            for (int mt = 0; mt < 2; mt++)
-#pragma unroll
-                for (int sk = 0; sk < 4; sk++) acc[mt] = NRC_MFMA(wlds[F_C1 + 4 * mt + sk][lane], H[sk], acc[mt]);
-#pragma unroll
-            for (int mt = 0; mt < 2; mt++)
-#pragma unroll
-                for (int gq = 0; gq < 2; gq++) H[2 * mt + gq] = acc_to_frag_relu(acc[mt], gq);
-            head_split(H, HB);
-            o[0] = f4v{0.f, 0.f, 0.f, 0.f}; o[1] = o[0];
-#pragma unroll
-            for (int sk = 0; sk < 2; sk++)
-#pragma unroll
-                for (int nb = 0; nb < 2; nb++) o[nb] = NRC_MFMA16(wlds[F_CO + sk][lane], HB[nb][sk], o[nb]);
-            float rgb[3];
-            head_join_rgb(o[0], o[1], rgb);
-            if (valid && hh == 0) {
-                h4 pk;
-                pk[0] = h0;
-#pragma unroll
-                for (int c = 0; c < 3; c++) pk[1 + c] = (_Float16)fast_sigmoid(rgb[c]);
-                *reinterpret_cast<h4*>(reinterpret_cast<_Float16*>(packed) + 4 * (base + row * 64 + 32 * u + r)) = pk;
-            }
-        }
-    }
-}
-
 __global__ void k_f32_to_f16(const float* __restrict__ src, __half* __restrict__ dst, int64_t n) {
     const int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     if (i + 3 < n) {
@@ -1008,10 +803,9 @@ int make_grid_cfg(int n_levels, int log2_T, int base_res, float pls, GridCfg& g,
 
 int pick_blocks(int64_t M) {
     // every workgroup stages the network's weight fragments in LDS (24 KB) before its first tile: few workgroups with several tiles per wave beat
-    // one tile per wave (NRC_MLP_BLOCKS: cap on the number of workgroups, default 2 048)
-    static const int64_t cap_env = [] { const char* e = getenv("NRC_MLP_BLOCKS"); return e ? atoll(e) : (int64_t)0; }();
+    // one tile per wave (cap on the number of workgroups: 512 below 1 Mi samples, 2 048 above)
     // measured on a 264 K-sample batch (us, density + colour forward): 2 048 workgroups 25.7 + 47.6, 1 024: 23.8 + 40.5, 512: 22.9 + 36.8, 256: 22.9 + 37.4
-    const int64_t cap = cap_env > 0 ? cap_env : (M < (int64_t(1) << 20) ? 512 : 2048);
+    const int64_t cap = M < (int64_t(1) << 20) ? 512 : 2048;
     const int64_t need = nrc_cdiv(nrc_cdiv(M, 32), 4);
     return (int)(need < cap ? (need > 0 ? need : 1) : cap);
 }
@@ -1036,11 +830,8 @@ static thread_local int g_enc_shape_override = 0;   // nrc_ngp_set_encoder_shape
 template <int SRC>
 static void launch_encode(const QueryIn& in, int64_t base, int64_t n, const void* table, const GridCfg& g, uint4* feat, hipStream_t s) {
     // levels whose cells are larger than a wave's footprint: narrow gathers (see grid_level_features_narrow)
-    static const int narrow_env = [] { const char* e = getenv("NRC_ENC_NARROW"); return e ? atoi(e) : -1; }();
     int narrow = 0;
-    if (narrow_env >= 0) narrow = narrow_env;
-    else while (narrow < NRC_MAX_LEVELS && !g.hashed[narrow] && g.size[narrow] > 8) narrow++;
-    static const int hashed_mode = [] { const char* e = getenv("NRC_ENC_HASHED"); return e ? atoi(e) : 1; }();
+    while (narrow < NRC_MAX_LEVELS && !g.hashed[narrow] && g.size[narrow] > 8) narrow++;
     // measurement switch (profiles/: L1 lookups per level range): NRC_ENC_LEVELS=lo-hi encodes only levels lo <= l < hi, the others read nothing and
     // come out as zeros -- WRONG pictures by design, never set outside a counter run
     static const int lvl_range = [] {
@@ -1050,78 +841,28 @@ static void launch_encode(const QueryIn& in, int64_t base, int64_t n, const void
         return NRC_MAX_LEVELS << 8;
     }();
     // below ~2 M samples the chip is not full with one lane per sample: split the four level groups over workgroup rows
-    static const int64_t split_below = [] { const char* e = getenv("NRC_ENC_SPLIT_BELOW"); return e ? atoll(e) : (int64_t)2 << 20; }();
+    const int64_t split_below = (int64_t)2 << 20;
     if constexpr (SRC == SRC_ARRAYS) {
-        static const int pairs_mode = [] { const char* e = getenv("NRC_ENC_PAIRS"); return e ? atoi(e) : 1; }();
-        if (pairs_mode && n < split_below && base == 0 && lvl_range == (NRC_MAX_LEVELS << 8)) {
+        if (n < split_below && base == 0 && lvl_range == (NRC_MAX_LEVELS << 8)) {
             hipLaunchKernelGGL(k_grid_encode_pairs, dim3((unsigned)(8 * nrc_cdiv(n, 256))), dim3(256), 0, s, in, n, (const __half2*)table, g, (uint2*)feat, narrow,
-                               hashed_mode, in.m_live);
+                               in.m_live);
             return;
         }
     }
     const unsigned rows = (SRC == SRC_ARRAYS && n < split_below) ? 4u : 1u;
-    // coarse levels of the tiled layout: wave-uniform cells through the scalar cache (NRC_ENC_UNIFORM = number of levels that try).  Measured
-    // (round 3, profiles/): it removes the vector lookups of those levels and changes NOTHING in time (0.643 ms off, 0.650-0.652 ms with 5, 7
-    // or 9 levels): the kernel is bound by the four finest levels' L1 misses (52 % of its time, 8.8 of 9.3 L2 requests per sample), not by
-    // the lookups of the coarse ones.  Default off; bit-identical features either way.
-    static const int uniform_levels = [] { const char* e = getenv("NRC_ENC_UNIFORM"); const int v = e ? atoi(e) : 0; return v < 0 ? 0 : (v > NRC_MAX_LEVELS ? NRC_MAX_LEVELS : v); }();
-    // NRC_ENC_SHAPE=uv: a wave encodes 2^u x 2^v pixels x 2^(6-u-v) steps of the tiled layout (default 31 = 8 x 2 x 4; 33 = a row, the round-2 form)
-    static const int lane_shape = [] {
-        const char* e = getenv("NRC_ENC_SHAPE");
-        const int v = e ? atoi(e) : 31, lu = v / 10, lv = v % 10;
-        return (lu < 0 || lu > NRC_TILE_W_LOG2 || lv < 0 || lv > 6 - NRC_TILE_W_LOG2 || lu + lv < 2 || lu + lv == 6) ? 0 : (lu << 4) | lv;   // 2 <= u + v: at most 16 steps
-    }();
+    // a wave encodes 2^u x 2^v pixels x 2^(6-u-v) steps of the tiled layout: 8 x 2 x 4 unless the renderer chose a shape for the pose
+    // (nrc_ngp_set_encoder_shape; the remapping permutes whole blocks of 1024 slots: the launch covers whole blocks)
+    const int lane_shape = (3 << 4) | 1;
     const int lanes = (SRC == SRC_TILED && (base & 1023) == 0) ? (g_enc_shape_override ? g_enc_shape_override : lane_shape) : 0;
-    static const int xcd_ranges = [] { const char* e = getenv("NRC_ENC_XCD"); return e ? (atoi(e) != 0) : 1; }();   // measured: 612 -> 591 us per launch (mean of 24 poses)
-    // (the remapping permutes whole blocks of 1024 slots: the launch covers whole blocks)
-    // NRC_ENC_FINE_SPLIT=1 (experiment, see k_grid_encode_fine): levels 12-15 in a second launch, one level per XCD
-    static const int fine_split = [] { const char* e = getenv("NRC_ENC_FINE_SPLIT"); return e ? atoi(e) : 0; }();
-    bool split = false;
-    if constexpr (SRC == SRC_TILED)
-        split = fine_split && lanes && rows == 1u && hashed_mode == 1 && lvl_range == (NRC_MAX_LEVELS << 8) && g.hashed[NRC_MAX_LEVELS - 4] && narrow <= NRC_MAX_LEVELS - 4;
     hipLaunchKernelGGL(k_grid_encode<SRC>, dim3((unsigned)(lanes ? 4 * nrc_cdiv(n, 1024) : nrc_cdiv(n, 256)), rows), dim3(256), 0, s, in, base, n, (const __half2*)table, g, feat,
-                       narrow, hashed_mode | (lvl_range << 4) | (uniform_levels << 20) | (xcd_ranges << 28) | ((split ? 1 : 0) << 29), lanes);
-    if constexpr (SRC == SRC_TILED) {
-        if (split) {
-            const int64_t per_half = 2 * nrc_cdiv(n, 1024);   // 256-slot blocks per half of the launch's slots
-            hipLaunchKernelGGL(k_grid_encode_fine<SRC>, dim3((unsigned)(8 * per_half)), dim3(256), 0, s, in, base, n, (const __half2*)table, g, feat, NRC_MAX_LEVELS - 4, lanes);
-        }
-    }
+                       narrow, lvl_range, lanes);
 }
 
 template <int SRC>
-static void launch_encode_mlp(const QueryIn& in, int64_t base, int64_t n, const void* table, const GridCfg& g, const void* ray_sh, const void* wd,
-                              const void* wc, void* packed, hipStream_t s) {
-    int narrow = 0;
-    while (narrow < NRC_MAX_LEVELS && !g.hashed[narrow] && g.size[narrow] > 8) narrow++;
-    // persistent waves: a workgroup stages the 24 KB of weight fragments once and walks rows with a stride
-    const int64_t rows = nrc_cdiv(n, 64);
-    const int64_t want = nrc_cdiv(rows, 4);
-    const unsigned blocks = (unsigned)(want < 256 * 6 ? (want > 0 ? want : 1) : 256 * 6);
-    hipLaunchKernelGGL(k_encode_mlp<SRC>, dim3(blocks), dim3(256), 0, s, in, base, n, (const __half2*)table, g, narrow, (const h8*)ray_sh,
-                       (const __half*)wd, (const __half*)wc, (__half*)packed);
-}
-// NRC_QUERY_FUSED=1 selects k_encode_mlp.  Measured on the 800x800 bench: 65.1-65.4 Mrays/s against 66.9-67.0 for the two kernels through the
-// feature buffer (77 VGPRs, 6 waves per SIMD; prefetching the SH fragments across the encoding: 100 VGPRs, 63.3; staggered workgroup
-// starts: 64.1-65.0) -- the fused kernel costs the SUM of the two kernels, the matrix phase does not hide behind the other waves' gathers.
-// Kept as an experiment switch (and covered by a parity test), not the default.
-static bool query_fused_kernel() {
-    static const bool v = [] { const char* e = getenv("NRC_QUERY_FUSED"); return e && e[0] == '1'; }();
-    return v;
-}
-static int mlp_tiles_per_wave() {
-    static const int v = [] { const char* e = getenv("NRC_MLP_NT"); return (e && e[0] == '1') ? 1 : 2; }();
-    return v;
-}
-template <int SRC>
 static void launch_mlp(const QueryIn& in, int64_t base, int64_t n, const void* feat, const void* ray_sh, const void* wd, const void* wc,
                        float* sigmas, float* rgbs, void* packed, hipStream_t s) {
-    if (mlp_tiles_per_wave() == 2)
-        hipLaunchKernelGGL((k_ngp_mlp<SRC, 2>), dim3(pick_blocks(nrc_cdiv(n, 2))), dim3(256), 0, s, in, base, n, (const uint4*)feat, (const h8*)ray_sh,
-                           (const __half*)wd, (const __half*)wc, sigmas, rgbs, (__half*)packed);
-    else
-        hipLaunchKernelGGL((k_ngp_mlp<SRC, 1>), dim3(pick_blocks(n)), dim3(256), 0, s, in, base, n, (const uint4*)feat, (const h8*)ray_sh,
-                           (const __half*)wd, (const __half*)wc, sigmas, rgbs, (__half*)packed);
+    hipLaunchKernelGGL(k_ngp_mlp<SRC>, dim3(pick_blocks(nrc_cdiv(n, 2))), dim3(256), 0, s, in, base, n, (const uint4*)feat, (const h8*)ray_sh,
+                       (const __half*)wd, (const __half*)wc, sigmas, rgbs, (__half*)packed);
 }
 
 // (Measured and dropped: running the MLP kernel of chunk c on a second stream next to the encode kernel of chunk c+1, with two
@@ -1137,9 +878,6 @@ static int run_query(const QueryIn& in, int64_t M, int64_t n_ray_tiles, const vo
     NRC_STAGE(s, nullptr);      // (armed stage timer: the two kernels of every chunk IN the frame's own sequence -- bench.py's in-frame ruler)
     for (int64_t base = 0; base < M; base += NRC_QUERY_CHUNK) {
         const int64_t n = (M - base) < NRC_QUERY_CHUNK ? (M - base) : NRC_QUERY_CHUNK;
-        if constexpr (SRC == SRC_TILED) {
-            if (query_fused_kernel()) { launch_encode_mlp<SRC>(in, base, n, table, g, ray_sh, wd, wc, packed, s); NRC_STAGE(s, "k_encode_mlp"); continue; }
-        }
         launch_encode<SRC>(in, base, n, table, g, feat, s);
         NRC_STAGE(s, "k_grid_encode");
         launch_mlp<SRC>(in, base, n, feat, ray_sh, wd, wc, sigmas, rgbs, packed, s);
@@ -1377,12 +1115,8 @@ int nrc_ngp_render_layers(const float* ts, int32_t* row_tile, const float* ray_o
     do {
         const int64_t cn = (M - base) < NRC_QUERY_CHUNK ? (M - base) : NRC_QUERY_CHUNK;
         if (cn > 0) {
-            if (query_fused_kernel()) {
-                launch_encode_mlp<SRC_TILED>(in, base, cn, table_f16, g, ray_sh, density_weights_f16, color_weights_f16, packed_f16, s);
-            } else {
-                launch_encode<SRC_TILED>(in, base, cn, table_f16, g, feat, s);
-                launch_mlp<SRC_TILED>(in, base, cn, feat, ray_sh, density_weights_f16, color_weights_f16, nullptr, nullptr, packed_f16, s);
-            }
+            launch_encode<SRC_TILED>(in, base, cn, table_f16, g, feat, s);
+            launch_mlp<SRC_TILED>(in, base, cn, feat, ray_sh, density_weights_f16, color_weights_f16, nullptr, nullptr, packed_f16, s);
         }
         nrc_launch_composite_layers(packed_f16, ts, ray_cnt, tile_rows, tile_off, row_of, row_tile, (base + cn) / 64, width, height, tile_begin, n_ray_tiles, cascades,
                                     exp_step_factor, grid_size, max_samples, T_threshold, bg3_host, state, ray_alive, next_k, tile_alive, rgb, alpha, depth,
@@ -2345,9 +2079,8 @@ __global__ void __launch_bounds__(GBA_THREADS) k_gb_accumulate(GridCfg g, Bucket
 static void pick_bucket_levels(const GridCfg& g, int n_levels, BucketCfg& bc, bool* is_bucketed) {
     bc.n_levels = 0; bc.bucket0[0] = 0;
     for (int l = 0; l < NRC_MAX_LEVELS; l++) is_bucketed[l] = false;
-    static const int max_lv = [] { const char* e = getenv("NRC_GB_LEVELS"); return e ? atoi(e) : NRC_MAX_LEVELS; }();
     int first = n_levels, units = 0;
-    for (int l = n_levels - 1; l >= 0 && n_levels - l <= max_lv; l--) {
+    for (int l = n_levels - 1; l >= 0; l--) {
         if (!g.hashed[l] || g.size[l] < (uint32_t)GB_ENTRIES || (g.size[l] % GB_ENTRIES) != 0u || g.res[l] + 1u >= (uint32_t)GB_ENTRIES) break;
         const int c = (int)(g.size[l] / GB_ENTRIES);
         if (units + c > GB_MAX_BUCKETS) break;
@@ -2379,8 +2112,8 @@ static int nwie_backward_impl(int64_t M, const void* weights_f16, int32_t n_hidd
     if ((!d_out_f16 && !tq.d_rgbs) || !out_f16 || !save_in || !save_acts) return NRC_ERR_INVALID;
     if (tq.d_rgbs && (!tq.d_sigmas || !tq.h || !tq.d_h16 || n_hidden != 2 || out_ld != 4)) return NRC_ERR_INVALID;
     // every wave ends with an atomic flush of its weight-gradient accumulators (3 072 / 7 168 values): the number of waves, not the
-    // batch, sets that cost -- one workgroup per CU (NRC_BWD_BLOCKS env override for experiments)
-    static const int max_blocks = [] { const char* e = getenv("NRC_BWD_BLOCKS"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 256; }();
+    // batch, sets that cost -- one workgroup per CU
+    const int max_blocks = 256;
     const int64_t need = nrc_cdiv(nrc_cdiv(M, 32), 4);
     const dim3 grid((unsigned)(need < max_blocks ? need : max_blocks)), block(256);
     hipStream_t s = (hipStream_t)stream;
@@ -2440,9 +2173,7 @@ static void step_adam_range(const TrainStep& st, int64_t from, int64_t to, bool 
 
 // does this call take the bucketed path (all conditions of grid_backward_impl in one place: nrc_ngp_train_query_backward_set needs the answer first)
 static bool gb_will_bucket(int64_t M, int pair_major, const void* workspace, const GridCfg& g, int n_levels, BucketCfg& bc, bool* isb) {
-    static const bool allow_owned = [] { const char* e = getenv("NRC_GRID_BWD_OWNED"); return !(e && e[0] == '0'); }();
-    static const bool allow_buckets = [] { const char* e = getenv("NRC_GRID_BWD_BUCKETS"); return !(e && e[0] == '0'); }();
-    if (!(allow_owned && allow_buckets && pair_major && M >= 16384 && workspace && M < (int64_t(1) << 30))) return false;
+    if (!(pair_major && M >= 16384 && workspace && M < (int64_t(1) << 30))) return false;
     pick_bucket_levels(g, n_levels, bc, isb);
     return bc.n_levels > 0;
 }
@@ -2459,8 +2190,7 @@ static int grid_backward_impl(const float* x01, int64_t M, const float* d_featur
     if (rc != NRC_OK) return rc;
     // ownership path: hashed levels of a large, pair-major batch (its cost is ~32 x M index computations per level whatever M is
     // worth in atomics, plus a 128 KB slice flush per workgroup: below ~16 K samples the atomics are cheaper)
-    static const bool allow_owned = [] { const char* e = getenv("NRC_GRID_BWD_OWNED"); return !(e && e[0] == '0'); }();
-    const bool owned = allow_owned && d_features_pair_major && M >= 16384;
+    const bool owned = d_features_pair_major && M >= 16384;
     hipStream_t s = (hipStream_t)stream;
     // bucketed ownership (needs the workspace): all hashed levels in two launches, the dense ones through the run-aggregated atomics
     {
@@ -2545,8 +2275,7 @@ static int grid_backward_impl(const float* x01, int64_t M, const float* d_featur
         (void)attr; (void)attr_q;
         bool sparse_ok = M < (int64_t(1) << 32);  // queue entries are 32-bit sample indices; x corners must stay below the slice bits
         for (int k = 0; k < oc.n_levels; k++) sparse_ok = sparse_ok && g.res[oc.level[k]] + 1u < (uint32_t)OWN_ENTRIES && g.size[oc.level[k]] >= (uint32_t)OWN_ENTRIES;
-        static const bool allow_q = [] { const char* e = getenv("NRC_GRID_BWD_SPARSE"); return !(e && e[0] == '0'); }();
-        if (sparse_ok && allow_q)
+        if (sparse_ok)
             hipLaunchKernelGGL(k_grid_bwd_owned_q, dim3((unsigned)oc.unit0[oc.n_levels]), dim3(OWN_THREADS), OWN_ENTRIES * 8 + (OWN_THREADS / 64) * OWN_Q * 4,
                                s, x01, M, d_features, g, oc, grad_table, m_live);
         else

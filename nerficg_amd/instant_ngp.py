@@ -406,7 +406,7 @@ class InstantNGPRenderer:
         MEASURED SLOWER, kept as an experiment (tools/bench_pipeline.py, 800x800 bench frame, ms per frame): one pass 8.67; 2 / 3 / 4 / 6 / 8
         ranges 8.82 / 8.91 / 8.98 / 9.29 / 9.56 -- next to the march the encoder (bound by its L1 / texture-address path) loses more than the
         0.4 ms the overlap hides, and every range ends in a partly filled launch.  The same was seen in the 3DGS forward (a bandwidth-heavy pass
-        next to the latency-bound sort: NRC_GS_OVERLAP) -- on this chip concurrent kernels do not add up."""
+        next to the latency-bound sort, measured slower and retired) -- on this chip concurrent kernels do not add up."""
         from .parallel import shard_range
         m = self.model
         dev = m.center.device

@@ -218,9 +218,7 @@ def test_grid_backward_bucketed_path_matches_atomics_and_is_reproducible(log2_t)
     np.testing.assert_allclose(a, want, rtol=2e-3, atol=2e-5 * scale)
     np.testing.assert_allclose(plain, want, rtol=2e-3, atol=2e-5 * scale)
     first_hashed = next(l for l in range(16) if offsets[l + 1] - offsets[l] == 2 ** log2_t)
-    import os
-    if os.environ.get('NRC_GRID_BWD_BUCKETS', '1') != '0' and os.environ.get('NRC_GRID_BWD_OWNED', '1') != '0':  # experiment switches
-        np.testing.assert_array_equal(a[offsets[first_hashed]:], b[offsets[first_hashed]:])  # fixed-point sums: order-independent
+    np.testing.assert_array_equal(a[offsets[first_hashed]:], b[offsets[first_hashed]:])  # fixed-point sums: order-independent
     assert np.array_equal(a == 0, want == 0) or np.mean((a == 0) != (want == 0)) < 1e-4
     # a non-finite upstream gradient (GradScaler overflow) must stay visible in the table gradient: the fixed-point path cannot carry inf / NaN,
     # it marks every slice of the affected level instead
