@@ -489,6 +489,20 @@ int nrc_ngp_composite_image(const void* packed_f16, const float* ts, const int32
                             float exp_step_factor, int32_t grid_size, int32_t max_samples, float T_threshold,
                             const float* bg3, float* rgb, float* alpha, float* depth, int64_t row_capacity, int32_t arena_rows,
                             nrc_stream_t stream);
+/* Steps 3 + 4 as ONE pass over the arena (the default single-pass frame): the MLP kernel composites the rows it evaluates, so no packed
+ * outputs are written or read back.  Takes the count pass's arena in place exactly like nrc_ngp_query_samples(ts = ts_provisional,
+ * arena_tile_off = tile_off, arena_rows = max_samples) and FILLS row_tile (n_rows entries) likewise; writes rgb / alpha / depth of the
+ * shard's pixels like nrc_ngp_composite_image.  Same pictures as steps 3 + 4, bit for bit (the per-sample step is shared).
+ * The frame runs in chunks of WHOLE ray tiles of at most row_budget rows (<= 0: the library default, 2 Mi rows = one chunk for an 800x800
+ * frame; otherwise >= 2 * max_samples); inside a chunk the tiles are processed longest first.  workspace:
+ * nrc_ngp_render_frame_ws_bytes(n_rows, n_ray_tiles, max_samples, row_budget) bytes. */
+int64_t nrc_ngp_render_frame_ws_bytes(int64_t n_rows, int64_t n_ray_tiles, int32_t max_samples, int64_t row_budget);
+int nrc_ngp_render_frame(const float* ts_arena, int32_t* row_tile, const float* ray_od, int64_t n_rows, int64_t n_ray_tiles,
+                         const float* xyz_min3, const float* xyz_size3, const void* density_weights_f16, const void* color_weights_f16,
+                         const void* table_f16, int32_t n_levels, int32_t log2_hashmap_size, int32_t base_resolution, float per_level_scale,
+                         const int32_t* ray_cnt, const int32_t* tile_off, int32_t width, int32_t height, int64_t tile_begin, int32_t cascades,
+                         float exp_step_factor, int32_t grid_size, int32_t max_samples, float T_threshold, const float* bg3_host, float* rgb,
+                         float* alpha, float* depth, int64_t row_budget, void* workspace, nrc_stream_t stream);
 
 /* =====================================================================================================
  * Group 7 -- SSIM map and its gradient (3DGS loss): replaces fused_ssim as imported at

@@ -8,11 +8,12 @@
 //   fw : 28 B read + 4 B written per sample ; bw : 44 B read + 16 B written per sample.
 // f32 sums are therefore tree-ordered instead of serial; the tolerance against the oracle is stated in the tests.
 #include "common.h"
+#include "ngp_image_step.h"
 #include <hip/hip_fp16.h>
 
 namespace {
 
-__device__ __forceinline__ float alpha_of(float sigma, float delta) { return 1.0f - __expf(-sigma * delta); }
+__device__ __forceinline__ float alpha_of(float sigma, float delta) { return nrc_alpha_of(sigma, delta); }
 
 // Transmittance bookkeeping for one G-lane chunk.  `a` = alpha of this lane's sample (0 for lanes past the ray end).
 // carry = T before the chunk.  Returns T before / after this lane's sample and updates carry to T after the chunk.
@@ -264,7 +265,9 @@ __global__ void __launch_bounds__(256) k_distortion_bw(const float* __restrict__
 // 64 rays: 512-byte (packed values) + 256-byte (t) coalesced reads per row.  Each lane composites ITS ray serially, in the
 // reference's order, with the inference early-out (volumerendering.cu:205-249: a ray dies after compositing the sample
 // that brings T <= threshold) and the finalisation of render_rays_inference (Renderer.py:133-138).  sigma = exp(h0)
-// (TruncExp), dt re-derived from t with the test kernel's step rule (raymarching.cu:370).
+// (TruncExp), dt re-derived from t with the test kernel's step rule (raymarching.cu:370).  The step and the finalisation live in
+// ngp_image_step.h, shared with k_composite_layers and k_ngp_mlp_composite (the single-pass frame composites inside its MLP kernel; this
+// kernel serves the pipelined, fixed-capacity and compact-row frames).
 __global__ void __launch_bounds__(256) k_composite_image(const __half* __restrict__ packed, const float* __restrict__ ts,
                                                          const int32_t* __restrict__ ray_cnt, const int32_t* __restrict__ tile_off,
                                                          int width, int height, int tiles_x, int64_t tile_begin, int64_t n_tiles,
@@ -280,20 +283,19 @@ __global__ void __launch_bounds__(256) k_composite_image(const __half* __restric
     const int64_t row0 = tile_off[lt];
     // row_cap (fixed-capacity frames): rows behind it were never written -- an overflowed frame reads nothing out of bounds (its picture is discarded)
     const int N = inside ? (int)min((int64_t)ray_cnt[lt * 64 + lane], max(row_cap - row0, (int64_t)0)) : 0;
-    float T = 1.0f, accR = 0.f, accG = 0.f, accB = 0.f, accD = 0.f, accO = 0.f;
-    bool alive = N > 0;
+    NrcRayAcc acc = nrc_ray_acc(N > 0);
     // several rows per turn, their loads issued together (a row's loads depend on nothing but k): the serial per-lane loop was bound by
     // one exposed load latency per sample
 #ifndef NRC_COMPOSITE_ROWS
 #define NRC_COMPOSITE_ROWS 8   // measured per 800x800 image: 4 rows 218 us, 8 rows 202, 16 rows 210
 #endif
     enum { CU = NRC_COMPOSITE_ROWS };
-    for (int k = 0; __any(alive); k += CU) {
+    for (int k = 0; __any(acc.alive); k += CU) {
         uint2 raw[CU];
         float tv[CU];
 #pragma unroll
         for (int u = 0; u < CU; u++) {
-            const bool in = alive && k + u < N;
+            const bool in = acc.alive && k + u < N;
             const int64_t s = (row0 + (in ? k + u : 0)) * 64 + lane;
             raw[u] = in ? *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(packed) + 4 * s) : make_uint2(0u, 0u);
             // arena_rows > 0: `ts` is the count pass's arena, sample k of this tile in its row lt * arena_rows + k
@@ -301,29 +303,14 @@ __global__ void __launch_bounds__(256) k_composite_image(const __half* __restric
         }
 #pragma unroll
         for (int u = 0; u < CU; u++) {
-            if (alive && k + u < N) {
+            if (acc.alive && k + u < N) {
                 const float2 f01 = __half22float2(*reinterpret_cast<const __half2*>(&raw[u].x));
                 const float2 f23 = __half22float2(*reinterpret_cast<const __half2*>(&raw[u].y));
-                const float t = tv[u];
-                const float dt = fmaxf(dt_min, fminf(t * esf, dt_max));
-                const float a = alpha_of(expf(f01.x), dt);
-                const float w = a * T;
-                accR += w * f01.y; accG += w * f23.x; accB += w * f23.y; accD += w * t; accO += w;
-                T *= 1.0f - a;
-                if (T <= thr || k + u + 1 >= N) alive = false;
+                nrc_composite_sample(acc, f01.x, f01.y, f23.x, f23.y, tv[u], esf, dt_min, dt_max, thr, k + u + 1 >= N);
             }
         }
     }
-    if (inside) {
-        const int64_t n = (int64_t)py * width + px;
-        const float al = fminf(fmaxf(accO, 0.f), 1.f);
-        const float Tr = 1.f - al;
-        rgb[3 * n] = fminf(fmaxf(accR + Tr * bg_r, 0.f), 1.f);
-        rgb[3 * n + 1] = fminf(fmaxf(accG + Tr * bg_g, 0.f), 1.f);
-        rgb[3 * n + 2] = fminf(fmaxf(accB + Tr * bg_b, 0.f), 1.f);
-        alpha_out[n] = al;
-        depth_out[n] = Tr < 1.0f ? accD / al : 0.0f;
-    }
+    if (inside) nrc_composite_finish(acc, bg_r, bg_g, bg_b, (int64_t)py * width + px, rgb, alpha_out, depth_out);
 }
 
 // up to five output arrays cleared by ONE launch (five hipMemsetAsync calls are five launches of host time in a ~90-launch training step)
@@ -368,16 +355,15 @@ __global__ void __launch_bounds__(256) k_composite_layers(const __half* __restri
     int k = next_k[lt];
     if (k < R && (int64_t)row_of[base + k] >= row_end) return;  // nothing of this tile in the chunk
     const int N = ray_cnt[q];
-    float T = state[q], accR = state[plane + q], accG = state[2 * plane + q], accB = state[3 * plane + q], accD = state[4 * plane + q],
-          accO = state[5 * plane + q];
-    bool alive = ray_alive[q] != 0;
+    NrcRayAcc acc = {state[q], state[plane + q], state[2 * plane + q], state[3 * plane + q], state[4 * plane + q], state[5 * plane + q],
+                     ray_alive[q] != 0};
     // The rows of a slab, EIGHT at a time with their loads issued together (round 4: one row per turn was a chain of up to sixteen dependent round
     // trips per slab, 62-75 us per launch); the arithmetic walks them in order, stops where the one-row loop stopped (row behind the chunk, all
     // lanes finished, last row of the tile) and leaves the same k.  arena_rows > 0: `ts` is the count pass's arena (sample k of this tile in its
     // row lt * arena_rows + k); `packed` stays indexed by the slab-major rows.
     enum { CU = 8 };
     bool behind = false;
-    while (k < R && !behind && __any(alive)) {
+    while (k < R && !behind && __any(acc.alive)) {
         int64_t rows[CU];
         uint2 raw[CU];
         float tv[CU];
@@ -385,34 +371,28 @@ __global__ void __launch_bounds__(256) k_composite_layers(const __half* __restri
         for (int u = 0; u < CU; u++) rows[u] = k + u < R ? (int64_t)row_of[base + k + u] : INT64_MAX;
 #pragma unroll
         for (int u = 0; u < CU; u++) {
-            const bool in = alive && k + u < N && rows[u] < row_end;
+            const bool in = acc.alive && k + u < N && rows[u] < row_end;
             const int64_t s = rows[u] * 64 + lane;
             raw[u] = in ? *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(packed) + 4 * s) : make_uint2(0u, 0u);
             tv[u] = in ? ts[arena_rows > 0 ? ((lt * arena_rows + k + u) << 6) + lane : s] : 0.f;
         }
 #pragma unroll
         for (int u = 0; u < CU; u++) {
-            if (k >= R || !__any(alive)) break;
+            if (k >= R || !__any(acc.alive)) break;
             if (rows[u] >= row_end) { behind = true; break; }
-            if (alive) {
+            if (acc.alive) {
                 const float2 f01 = __half22float2(*reinterpret_cast<const __half2*>(&raw[u].x));
                 const float2 f23 = __half22float2(*reinterpret_cast<const __half2*>(&raw[u].y));
-                const float t = tv[u];
-                const float dt = fmaxf(dt_min, fminf(t * esf, dt_max));
-                const float a = alpha_of(expf(f01.x), dt);
-                const float w = a * T;
-                accR += w * f01.y; accG += w * f23.x; accB += w * f23.y; accD += w * t; accO += w;
-                T *= 1.0f - a;
-                if (T <= thr || k + 1 >= N) alive = false;
+                nrc_composite_sample(acc, f01.x, f01.y, f23.x, f23.y, tv[u], esf, dt_min, dt_max, thr, k + 1 >= N);
             }
             k++;
         }
     }
-    const bool finished = !__any(alive) || k >= R;
+    const bool finished = !__any(acc.alive) || k >= R;
     if (!finished) {
-        state[q] = T; state[plane + q] = accR; state[2 * plane + q] = accG; state[3 * plane + q] = accB; state[4 * plane + q] = accD;
-        state[5 * plane + q] = accO;
-        ray_alive[q] = alive;
+        state[q] = acc.T; state[plane + q] = acc.r; state[2 * plane + q] = acc.g; state[3 * plane + q] = acc.b; state[4 * plane + q] = acc.d;
+        state[5 * plane + q] = acc.o;
+        ray_alive[q] = acc.alive;
         if (lane == 0) next_k[lt] = k;
         return;
     }
@@ -425,16 +405,7 @@ __global__ void __launch_bounds__(256) k_composite_layers(const __half* __restri
         for (int kk = k + lane; kk < R; kk += 64) row_tile[row_of[base + kk]] = -1 - (int32_t)lt;
     const int64_t tile = tile_begin + lt;
     const int px = (int)(tile % tiles_x) * NRC_TILE_W + (lane & (NRC_TILE_W - 1)), py = (int)(tile / tiles_x) * NRC_TILE_H + (lane >> NRC_TILE_W_LOG2);
-    if (px < width && py < height) {
-        const int64_t n = (int64_t)py * width + px;
-        const float al = fminf(fmaxf(accO, 0.f), 1.f);
-        const float Tr = 1.f - al;
-        rgb[3 * n] = fminf(fmaxf(accR + Tr * bg_r, 0.f), 1.f);
-        rgb[3 * n + 1] = fminf(fmaxf(accG + Tr * bg_g, 0.f), 1.f);
-        rgb[3 * n + 2] = fminf(fmaxf(accB + Tr * bg_b, 0.f), 1.f);
-        alpha_out[n] = al;
-        depth_out[n] = Tr < 1.0f ? accD / al : 0.0f;
-    }
+    if (px < width && py < height) nrc_composite_finish(acc, bg_r, bg_g, bg_b, (int64_t)py * width + px, rgb, alpha_out, depth_out);
 }
 
 }  // namespace

@@ -10,6 +10,7 @@
 // live in the wave's VGPRs for the whole persistent loop.  Per sample the kernel reads 12 B (+ the gathers, served by
 // L2 / Infinity Cache: the 24.4 MB table never streams from HBM twice) and writes 8-32 B.
 #include "ngp_net.h"
+#include "ngp_image_step.h"
 
 namespace {
 
@@ -267,6 +268,8 @@ struct QueryIn {
     const int32_t* row_k;                                           // ... or, for rows in slab-major order, sample row_k[i >> 6] of its tile (tile_off unused)
     float mn[3], sz[3];                                             // xyz_min, xyz_size of the model box (Renderer.py:50)
     const int32_t* m_live;                                          // SRC_ARRAYS, optional: rows that hold samples (DEVICE), see k_nwie_fwd
+    const int32_t* chunk_rows;                                      // SRC_TILED, optional: [first row, end row) of the launch on the DEVICE (chunks of whole
+                                                                    // ray tiles, nrc_ngp_render_frame): base = 64 * first row, the launch is sized for a bound
 };
 // index of slot i (row i >> 6 of ray tile rt) in `ts`: the slot itself, or its place in the count pass's arena
 __device__ __forceinline__ int64_t ts_slot(const QueryIn& in, int64_t i, int32_t rt) {
@@ -339,6 +342,11 @@ __global__ void __launch_bounds__(256) k_grid_encode(QueryIn in, int64_t base, i
             const int64_t have = (int64_t)in.n_rows_dev[0] * 64 - base;
             n = have < n ? have : n;
         }
+        if (in.chunk_rows) {   // uniform scalar loads: the chunk's rows, decided on the device (k_tile_chunks)
+            const int64_t r0 = in.chunk_rows[0], r1 = in.chunk_rows[1];
+            base = r0 * 64;
+            n = (r1 - r0) * 64 < n ? (r1 - r0) * 64 : n;
+        }
     }
     if constexpr (SRC == SRC_TILED) {
         if (lane_shape != 0) {
@@ -352,11 +360,11 @@ __global__ void __launch_bounds__(256) k_grid_encode(QueryIn in, int64_t base, i
             // (image-row) side wins on almost every pose; choosing per pose between it, 8x1x8 and a row would gain another 1 %.  Default 8 x 2 x 4.
             // The slot a sample is stored in does not change, and neither does any value.
             const int lu = (lane_shape >> 4) & 7, lv = lane_shape & 7, ls = 6 - lu - lv;
-            const int64_t g1024 = (base + j) & ~(int64_t)1023;
+            const int64_t g1024 = j & ~(int64_t)1023;   // (blocks of 1024 slots counted from base: row-aligned with the host's base % 1024 == 0)
             const int w = (int)((j >> 6) & 15), l = (int)(j & 63);
             const int iu = l & ((1 << lu) - 1), iv = (l >> lu) & ((1 << lv) - 1), is = l >> (lu + lv);
             const int gu = w & ((NRC_TILE_W >> lu) - 1), gv = (w >> (NRC_TILE_W_LOG2 - lu)) & ((NRC_TILE_H >> lv) - 1), gs = w >> (6 - lu - lv);
-            j = g1024 + ((int64_t)((gs << ls) + is) << 6) + NRC_TILE_W * ((gv << lv) + iv) + (gu << lu) + iu - base;
+            j = g1024 + ((int64_t)((gs << ls) + is) << 6) + NRC_TILE_W * ((gv << lv) + iv) + (gu << lu) + iu;
             remapped = true;
         }
     }
@@ -476,12 +484,134 @@ __device__ __forceinline__ f16v mlp_mfma(const h8& a, const h8& b, const f16v& c
 #ifndef NRC_MLP_WAVES
 #define NRC_MLP_WAVES 2   // workgroups per CU the register budget is set for (= waves per SIMD); A/B builds: -DNRC_MLP_WAVES=3
 #endif
+// the two networks' weights as LDS-resident A fragments (24 KB per workgroup): slot f of wlds[f][lane]
+enum { MLP_F_D0 = 0, MLP_F_DO = 4, MLP_F_C0 = 8, MLP_F_C1 = 12, MLP_F_CO = 20, MLP_N_FRAG = 24 };
+__device__ __forceinline__ void mlp_stage_weights(h8 (*wlds)[64], const __half* __restrict__ Wd, const __half* __restrict__ Wc) {
+    const int lane = threadIdx.x & 63, r = lane & 31, hh = lane >> 5;
+    for (int f = threadIdx.x >> 6; f < MLP_N_FRAG; f += 4) {
+        h8 v;
+        if (f < MLP_F_DO) v = load_w_frag<false>(Wd, 32, 64, (f - MLP_F_D0) >> 1, (f - MLP_F_D0) & 1, r, hh);
+        else if (f < MLP_F_C0) v = load_w_head_frag(Wd + 64 * 32, 64, 16, (f - MLP_F_DO) & 1, lane);     // 16-row head: two 16x16x32 k-steps (slots F_DO + 2, + 3 unused)
+        else if (f < MLP_F_C1) {
+            const int mt = (f - MLP_F_C0) >> 1, s = (f - MLP_F_C0) & 1;  // k-step 0 = SH coefficients, 1 = density features: both natural order (head_join)
+            v = load_w_frag<false>(Wc, 32, 64, mt, s, r, hh);
+        } else if (f < MLP_F_CO) v = load_w_frag<true>(Wc + 64 * 32, 64, 64, (f - MLP_F_C1) >> 2, (f - MLP_F_C1) & 3, r, hh);
+        else v = load_w_head_frag(Wc + 64 * 32 + 64 * 64, 64, 16, (f - MLP_F_CO) & 1, lane);
+        wlds[f][lane] = v;
+    }
+}
+// The MFMA chain of NT tiles of 32 samples: density net -> 16-row head -> colour net -> rgb head.  B: first-layer B fragments (fragment-major
+// features), X0: colour-net k-step 0 (SH of the direction).  Out, on lane r < 32 of tile u (sample r): h0[u] = fp16 density feature 0 and
+// rgb[u] = fp16 sigmoid of the colour head -- the values the packed records hold.
+template <int NT>
+__device__ __forceinline__ void mlp_chain(const h8 (*wlds)[64], const h8 (&B)[NT][2], const h8 (&X0)[NT], _Float16 (&h0)[NT], _Float16 (&rgbh)[NT][3]) {
+    const int lane = threadIdx.x & 63;
+#define D0(mt, s) wlds[MLP_F_D0 + 2 * (mt) + (s)][lane]
+#define DO(s) wlds[MLP_F_DO + (s)][lane]
+#define C0(mt, s) wlds[MLP_F_C0 + 2 * (mt) + (s)][lane]
+#define C1(mt, s) wlds[MLP_F_C1 + 4 * (mt) + (s)][lane]
+#define CO(s) wlds[MLP_F_CO + (s)][lane]
+    h8 X[NT][2], H[NT][4];
+    f16v acc[NT][2];
+    h8 HB[NT][2][2];      // head operands: [sample block][k-step] (head_split)
+    f4v o[NT][2];         // head accumulators, one per 16-sample block
+#pragma unroll
+    for (int u = 0; u < NT; u++) {
+        X[u][0] = X0[u];
+        acc[u][0] = zero16(); acc[u][1] = zero16();
+        o[u][0] = f4v{0.f, 0.f, 0.f, 0.f}; o[u][1] = o[u][0];
+    }
+#pragma unroll
+    for (int mt = 0; mt < 2; mt++)
+#pragma unroll
+        for (int s = 0; s < 2; s++) {
+            const h8 w = D0(mt, s);
+#pragma unroll
+            for (int u = 0; u < NT; u++) acc[u][mt] = mlp_mfma(w, B[u][s], acc[u][mt]);
+        }
+#pragma unroll
+    for (int u = 0; u < NT; u++) {
+#pragma unroll
+        for (int mt = 0; mt < 2; mt++)
+#pragma unroll
+            for (int gq = 0; gq < 2; gq++) H[u][2 * mt + gq] = mlp_frag_relu(acc[u][mt], gq);
+        head_split(H[u], HB[u]);
+    }
+    // density head, 64 -> 16: two 16x16x32 k-steps per 16-sample block instead of four 32x32x16 steps over a half-empty tile
+#pragma unroll
+    for (int s = 0; s < 2; s++) {
+        const h8 w = DO(s);
+#pragma unroll
+        for (int u = 0; u < NT; u++)
+#pragma unroll
+            for (int nb = 0; nb < 2; nb++) o[u][nb] = NRC_MFMA16(w, HB[u][nb][s], o[u][nb]);
+    }
+#pragma unroll
+    for (int u = 0; u < NT; u++) {
+        X[u][1] = head_join(o[u][0], o[u][1]);  // colour-net k-step 1 = fp16(h), natural order, back on the sample's lanes
+        h0[u] = X[u][1][0];              // fp16 density feature 0 (lane half 0, element 0)
+        acc[u][0] = zero16(); acc[u][1] = zero16();
+    }
+#pragma unroll
+    for (int mt = 0; mt < 2; mt++)
+#pragma unroll
+        for (int s = 0; s < 2; s++) {
+            const h8 w = C0(mt, s);
+#pragma unroll
+            for (int u = 0; u < NT; u++) acc[u][mt] = mlp_mfma(w, X[u][s], acc[u][mt]);
+        }
+#pragma unroll
+    for (int u = 0; u < NT; u++) {
+#pragma unroll
+        for (int mt = 0; mt < 2; mt++)
+#pragma unroll
+            for (int gq = 0; gq < 2; gq++) H[u][2 * mt + gq] = mlp_frag_relu(acc[u][mt], gq);
+        acc[u][0] = zero16(); acc[u][1] = zero16();
+    }
+#pragma unroll
+    for (int mt = 0; mt < 2; mt++)
+#pragma unroll
+        for (int s = 0; s < 4; s++) {
+            const h8 w = C1(mt, s);
+#pragma unroll
+            for (int u = 0; u < NT; u++) acc[u][mt] = mlp_mfma(w, H[u][s], acc[u][mt]);
+        }
+#pragma unroll
+    for (int u = 0; u < NT; u++) {
+#pragma unroll
+        for (int mt = 0; mt < 2; mt++)
+#pragma unroll
+            for (int gq = 0; gq < 2; gq++) H[u][2 * mt + gq] = mlp_frag_relu(acc[u][mt], gq);
+        head_split(H[u], HB[u]);
+        o[u][0] = f4v{0.f, 0.f, 0.f, 0.f}; o[u][1] = o[u][0];
+    }
+#pragma unroll
+    for (int s = 0; s < 2; s++) {
+        const h8 w = CO(s);
+#pragma unroll
+        for (int u = 0; u < NT; u++)
+#pragma unroll
+            for (int nb = 0; nb < 2; nb++) o[u][nb] = NRC_MFMA16(w, HB[u][nb][s], o[u][nb]);
+    }
+#pragma unroll
+    for (int u = 0; u < NT; u++) {
+        // rgb = neurons 0..2: lanes 0-15 of each block (k-group 0); a row swap puts sample r's triple on lane r, the sigmoid runs there
+        float rgb[3];
+        head_join_rgb(o[u][0], o[u][1], rgb);
+#pragma unroll
+        for (int c = 0; c < 3; c++) rgbh[u][c] = (_Float16)fast_sigmoid(rgb[c]);
+    }
+#undef D0
+#undef DO
+#undef C0
+#undef C1
+#undef CO
+}
 template <int SRC>
 __global__ void __launch_bounds__(256, NRC_MLP_WAVES) k_ngp_mlp(QueryIn in, int64_t base, int64_t n, const uint4* __restrict__ feat,
                                                     const h8* __restrict__ ray_sh, const __half* __restrict__ Wd,
                                                     const __half* __restrict__ Wc, float* __restrict__ sigmas, float* __restrict__ rgbs,
                                                     __half* __restrict__ packed) {
-    enum { F_D0 = 0, F_DO = 4, F_C0 = 8, F_C1 = 12, F_CO = 20, N_FRAG = 24 };
     constexpr int NT = 2;
     if constexpr (SRC == SRC_TILED) {
         if (in.n_rows_dev) {   // fixed row capacity: only the rows the march produced (uniform over the launch)
@@ -490,28 +620,13 @@ __global__ void __launch_bounds__(256, NRC_MLP_WAVES) k_ngp_mlp(QueryIn in, int6
             if (n <= 0) return;
         }
     }
-    __shared__ h8 wlds[N_FRAG][64];
+    __shared__ h8 wlds[MLP_N_FRAG][64];
     const int lane = threadIdx.x & 63, r = lane & 31, hh = lane >> 5;
     const int64_t n_tiles = (n + 31) / 32;
     const int64_t n_groups = (n_tiles + NT - 1) / NT;
     const int64_t wave0 = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = (int64_t)gridDim.x * 4;
-    for (int f = threadIdx.x >> 6; f < N_FRAG; f += 4) {
-        h8 v;
-        if (f < F_DO) v = load_w_frag<false>(Wd, 32, 64, (f - F_D0) >> 1, (f - F_D0) & 1, r, hh);
-        else if (f < F_C0) v = load_w_head_frag(Wd + 64 * 32, 64, 16, (f - F_DO) & 1, lane);     // 16-row head: two 16x16x32 k-steps (slots F_DO + 2, + 3 unused)
-        else if (f < F_C1) {
-            const int mt = (f - F_C0) >> 1, s = (f - F_C0) & 1;  // k-step 0 = SH coefficients, 1 = density features: both natural order (head_join)
-            v = load_w_frag<false>(Wc, 32, 64, mt, s, r, hh);
-        } else if (f < F_CO) v = load_w_frag<true>(Wc + 64 * 32, 64, 64, (f - F_C1) >> 2, (f - F_C1) & 3, r, hh);
-        else v = load_w_head_frag(Wc + 64 * 32 + 64 * 64, 64, 16, (f - F_CO) & 1, lane);
-        wlds[f][lane] = v;
-    }
+    mlp_stage_weights(wlds, Wd, Wc);
     __syncthreads();
-#define D0(mt, s) wlds[F_D0 + 2 * (mt) + (s)][lane]
-#define DO(s) wlds[F_DO + (s)][lane]
-#define C0(mt, s) wlds[F_C0 + 2 * (mt) + (s)][lane]
-#define C1(mt, s) wlds[F_C1 + 4 * (mt) + (s)][lane]
-#define CO(s) wlds[F_CO + (s)][lane]
     // software pipeline: the loads of the NEXT group (features 2 x 16 B, SH 16 B or direction, hole flag) are issued before the MFMA
     // chain of the current one
     // A tile's row number (hence its ray tile) is uniform over the wave and known from the tile index alone, so it is fetched through the SCALAR
@@ -652,116 +767,154 @@ __global__ void __launch_bounds__(256, NRC_MLP_WAVES) k_ngp_mlp(QueryIn in, int6
         if (__ballot(any) == 0ull) continue;  // nothing but holes
         // first-layer B fragments straight from the encoder's fragment-major records (512 contiguous bytes per half wave);
         // element (2q, 2q+1) of k-step s <- features of level 8s + 4hh + q
-        h8 B[NT][2], X[NT][2], H[NT][4];
-        f16v acc[NT][2];
-        h8 HB[NT][2][2];      // head operands: [sample block][k-step] (head_split)
-        f4v o[NT][2];         // head accumulators, one per 16-sample block
+        h8 B[NT][2], X0[NT];
 #pragma unroll
         for (int u = 0; u < NT; u++) {
             B[u][0] = *reinterpret_cast<const h8*>(&cur[u].b0);
             B[u][1] = *reinterpret_cast<const h8*>(&cur[u].b1);
             if constexpr (SRC == SRC_TILED) {
-                X[u][0] = cur[u].sh;  // colour-net k-step 0 = SH(dir) (natural order)
+                X0[u] = cur[u].sh;  // colour-net k-step 0 = SH(dir) (natural order)
             } else {
                 h8 lo, hi;
                 sh4_fragments(cur[u].dx, cur[u].dy, cur[u].dz, lo, hi);
-                X[u][0] = hh ? hi : lo;
+                X0[u] = hh ? hi : lo;
             }
-            acc[u][0] = zero16(); acc[u][1] = zero16();
-            o[u][0] = f4v{0.f, 0.f, 0.f, 0.f}; o[u][1] = o[u][0];
         }
-#pragma unroll
-        for (int mt = 0; mt < 2; mt++)
-#pragma unroll
-            for (int s = 0; s < 2; s++) {
-                const h8 w = D0(mt, s);
-#pragma unroll
-                for (int u = 0; u < NT; u++) acc[u][mt] = mlp_mfma(w, B[u][s], acc[u][mt]);
-            }
-#pragma unroll
-        for (int u = 0; u < NT; u++) {
-#pragma unroll
-            for (int mt = 0; mt < 2; mt++)
-#pragma unroll
-                for (int gq = 0; gq < 2; gq++) H[u][2 * mt + gq] = mlp_frag_relu(acc[u][mt], gq);
-            head_split(H[u], HB[u]);
-        }
-        // density head, 64 -> 16: two 16x16x32 k-steps per 16-sample block instead of four 32x32x16 steps over a half-empty tile
-#pragma unroll
-        for (int s = 0; s < 2; s++) {
-            const h8 w = DO(s);
-#pragma unroll
-            for (int u = 0; u < NT; u++)
-#pragma unroll
-                for (int nb = 0; nb < 2; nb++) o[u][nb] = NRC_MFMA16(w, HB[u][nb][s], o[u][nb]);
-        }
-        _Float16 h0[NT];
-#pragma unroll
-        for (int u = 0; u < NT; u++) {
-            X[u][1] = head_join(o[u][0], o[u][1]);  // colour-net k-step 1 = fp16(h), natural order, back on the sample's lanes
-            h0[u] = X[u][1][0];              // fp16 density feature 0 (lane half 0, element 0)
-            acc[u][0] = zero16(); acc[u][1] = zero16();
-        }
-#pragma unroll
-        for (int mt = 0; mt < 2; mt++)
-#pragma unroll
-            for (int s = 0; s < 2; s++) {
-                const h8 w = C0(mt, s);
-#pragma unroll
-                for (int u = 0; u < NT; u++) acc[u][mt] = mlp_mfma(w, X[u][s], acc[u][mt]);
-            }
-#pragma unroll
-        for (int u = 0; u < NT; u++) {
-#pragma unroll
-            for (int mt = 0; mt < 2; mt++)
-#pragma unroll
-                for (int gq = 0; gq < 2; gq++) H[u][2 * mt + gq] = mlp_frag_relu(acc[u][mt], gq);
-            acc[u][0] = zero16(); acc[u][1] = zero16();
-        }
-#pragma unroll
-        for (int mt = 0; mt < 2; mt++)
-#pragma unroll
-            for (int s = 0; s < 4; s++) {
-                const h8 w = C1(mt, s);
-#pragma unroll
-                for (int u = 0; u < NT; u++) acc[u][mt] = mlp_mfma(w, H[u][s], acc[u][mt]);
-            }
-#pragma unroll
-        for (int u = 0; u < NT; u++) {
-#pragma unroll
-            for (int mt = 0; mt < 2; mt++)
-#pragma unroll
-                for (int gq = 0; gq < 2; gq++) H[u][2 * mt + gq] = mlp_frag_relu(acc[u][mt], gq);
-            head_split(H[u], HB[u]);
-            o[u][0] = f4v{0.f, 0.f, 0.f, 0.f}; o[u][1] = o[u][0];
-        }
-#pragma unroll
-        for (int s = 0; s < 2; s++) {
-            const h8 w = CO(s);
-#pragma unroll
-            for (int u = 0; u < NT; u++)
-#pragma unroll
-                for (int nb = 0; nb < 2; nb++) o[u][nb] = NRC_MFMA16(w, HB[u][nb][s], o[u][nb]);
-        }
+        _Float16 h0[NT], rgbh[NT][3];
+        mlp_chain<NT>(wlds, B, X0, h0, rgbh);
 #pragma unroll
         for (int u = 0; u < NT; u++) {
             pend_ok[u] = valid[u] && hh == 0;
             pend_idx[u] = idx[u];
             pend_pk[u][0] = h0[u];
-            // rgb = neurons 0..2: lanes 0-15 of each block (k-group 0); a row swap puts sample r's triple on lane r, the sigmoid runs there
-            float rgb[3];
-            head_join_rgb(o[u][0], o[u][1], rgb);
 #pragma unroll
-            for (int c = 0; c < 3; c++) pend_pk[u][1 + c] = (_Float16)fast_sigmoid(rgb[c]);
+            for (int c = 0; c < 3; c++) pend_pk[u][1 + c] = rgbh[u][c];
         }
       }
     }
     flush_pending();
-#undef D0
-#undef DO
-#undef C0
-#undef C1
-#undef CO
+}
+
+// ---- the single-pass frame: MLP and compositing in one kernel ---------------------------------------------------------------------------------
+// Chunks of WHOLE ray tiles, so that one wave can walk every row of a tile: chunk c = the tiles whose first row lies in [c span, (c + 1) span)
+// (span = row budget - max_samples: no chunk holds more rows than the budget; one chunk = the whole frame below the budget).  One workgroup per
+// chunk: chunk_tab[4 c ..] = (first tile, end tile, first row, end row), queue[c] = 0, and order[first tile .. end tile) = the chunk's tiles
+// LONGEST FIRST (counting sort over the row counts, 1024 buckets; the order inside a bucket is whatever the atomics give -- it only schedules).
+__global__ void __launch_bounds__(1024) k_tile_chunks(const int32_t* __restrict__ tile_off, int64_t n_tiles, int64_t span, int32_t* __restrict__ chunk_tab,
+                                                      int32_t* __restrict__ order, int32_t* __restrict__ queue) {
+    __shared__ int hist[1024];
+    __shared__ int wave_tot[16];
+    __shared__ int range[2];
+    const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid < 2) {   // first tile whose first row is >= the bound (tile_off ascends); the last chunk ends at n_tiles
+        int64_t lo = 0, hi = n_tiles;
+        if (tid == 1 && c + 1 == (int)gridDim.x) lo = n_tiles;
+        else {
+            const int64_t bound = (int64_t)(c + tid) * span;
+            while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if ((int64_t)tile_off[mid] < bound) lo = mid + 1; else hi = mid; }
+        }
+        range[tid] = (int)lo;
+    }
+    hist[tid] = 0;
+    __syncthreads();
+    const int t0 = range[0], t1 = range[1];
+    for (int t = t0 + tid; t < t1; t += 1024) atomicAdd(&hist[1023 - min(tile_off[t + 1] - tile_off[t], 1023)], 1);
+    __syncthreads();
+    const int v = hist[tid];
+    const int incl = nrc_wave_incl_sum_i(v, lane);
+    if (lane == 63) wave_tot[wave] = incl;
+    __syncthreads();
+    int off = incl - v;
+    for (int w = 0; w < wave; w++) off += wave_tot[w];
+    hist[tid] = off;
+    __syncthreads();
+    for (int t = t0 + tid; t < t1; t += 1024) order[t0 + atomicAdd(&hist[1023 - min(tile_off[t + 1] - tile_off[t], 1023)], 1)] = t;
+    if (tid == 0) {
+        chunk_tab[4 * c] = t0; chunk_tab[4 * c + 1] = t1; chunk_tab[4 * c + 2] = tile_off[t0]; chunk_tab[4 * c + 3] = tile_off[t1];
+        queue[c] = 0;
+    }
+}
+
+struct ImageCfg { int width, height, tiles_x; int64_t tile_begin; float esf, dt_min, dt_max, thr, bg_r, bg_g, bg_b; };
+// One wave = one 8x8 ray tile at a time, lane = ray: the wave runs the MFMA chain of k_ngp_mlp on every row of the tile in order (NT = 2 tiles of
+// 32 samples = one row of 64) and composites each row's outputs straight away with the per-sample step of k_composite_image (ngp_image_step.h):
+// the same f32 operation sequence per ray, so the same pictures, without writing the 8-byte outputs of every slot and reading them back.  The
+// outputs leave the chain on lanes 0-31 of each 32-sample tile; one v_permlane32_swap per dword moves samples 32-63 onto lanes 32-63.  Tiles come
+// from the chunk's longest-first list through an atomic counter (a plain work queue: a wave never waits for another one).  A tile whose rays have
+// all finished (saturated or out of samples) requests no further rows.  Features: the chunk's fragment-major records (row - first row of the
+// chunk); t: the count pass's arena in place (sample k of local tile lt in arena row lt * arena_rows + k).
+__global__ void __launch_bounds__(256, NRC_MLP_WAVES) k_ngp_mlp_composite(const uint4* __restrict__ feat, const h8* __restrict__ ray_sh,
+                                                                          const __half* __restrict__ Wd, const __half* __restrict__ Wc,
+                                                                          const float* __restrict__ ts, int arena_rows, const int32_t* __restrict__ ray_cnt,
+                                                                          const int32_t* __restrict__ tile_off, const int32_t* __restrict__ order,
+                                                                          const int32_t* __restrict__ chunk, int32_t* __restrict__ queue, ImageCfg ic,
+                                                                          float* __restrict__ rgb, float* __restrict__ alpha_out, float* __restrict__ depth_out) {
+    constexpr int NT = 2;
+    __shared__ h8 wlds[MLP_N_FRAG][64];
+    const int lane = threadIdx.x & 63, r = lane & 31, hh = lane >> 5;
+    mlp_stage_weights(wlds, Wd, Wc);
+    __syncthreads();
+    const int t_first = chunk[0], n_chunk = chunk[1] - chunk[0], row0 = chunk[2];
+    auto take = [&]() -> int {
+        int q = 0;
+        if (lane == 0) q = atomicAdd(queue, 1);
+        return __builtin_amdgcn_readfirstlane(__shfl(q, 0, 64));
+    };
+    for (int q = take(); q < n_chunk; q = take()) {
+        const int lt = __builtin_amdgcn_readfirstlane(order[t_first + q]);
+        const int rb = tile_off[lt], R = tile_off[lt + 1] - rb;
+        const int64_t tile = ic.tile_begin + lt;
+        const int px = (int)(tile % ic.tiles_x) * NRC_TILE_W + (lane & (NRC_TILE_W - 1)), py = (int)(tile / ic.tiles_x) * NRC_TILE_H + (lane >> NRC_TILE_W_LOG2);
+        const bool inside = px < ic.width && py < ic.height;
+        const int N = inside ? ray_cnt[(int64_t)lt * 64 + lane] : 0;
+        NrcRayAcc acc = nrc_ray_acc(N > 0);
+        h8 X0[NT];   // colour-net k-step 0 = SH of the rays: the same for every row of the tile
+#pragma unroll
+        for (int u = 0; u < NT; u++) X0[u] = ray_sh[((int64_t)lt * 2 + hh) * 64 + r + 32 * u];
+        const float* tcol = ts + (((int64_t)lt * arena_rows) << 6) + lane;
+        const uint4* fcol = feat + (int64_t)(rb - row0) * (NT * 128) + r;   // 32-sample tile 2 (row - row0) + u at fcol + (2 k + u) * 128
+        const int rot0 = (2 * (rb - row0)) & 3;
+        uint4 nb[NT][2];
+        float nt_ = 0.f;
+        auto fetch = [&](int k) {   // row k of the tile: features of both halves, this lane's t
+#pragma unroll
+            for (int u = 0; u < NT; u++) {
+                const uint4* fp = fcol + (int64_t)(2 * k + u) * 128;
+                const int rot = (rot0 + 2 * k + u) & 3;
+                nb[u][0] = fp[((hh + rot) & 3) * 32];
+                nb[u][1] = fp[((2 + hh + rot) & 3) * 32];
+            }
+            nt_ = tcol[(int64_t)k << 6];
+        };
+        if (R > 0) fetch(0);
+        // one row of prefetch: the next row's loads are issued before this row's chain
+        for (int k = 0; k < R && __any(acc.alive); k++) {
+            h8 B[NT][2];
+#pragma unroll
+            for (int u = 0; u < NT; u++) { B[u][0] = *reinterpret_cast<const h8*>(&nb[u][0]); B[u][1] = *reinterpret_cast<const h8*>(&nb[u][1]); }
+            const float t = nt_;
+            if (k + 1 < R) fetch(k + 1);
+            _Float16 h0[NT], rgbh[NT][3];
+            mlp_chain<NT>(wlds, B, X0, h0, rgbh);
+            // fp16 outputs exactly as the packed records hold them, (h0, r) and (g, b); sample 32 u + r sits on lane r of tile u
+            uint32_t w01[NT], w23[NT];
+#pragma unroll
+            for (int u = 0; u < NT; u++) {
+                const h2 a = {h0[u], rgbh[u][0]}, b = {rgbh[u][1], rgbh[u][2]};
+                w01[u] = *reinterpret_cast<const uint32_t*>(&a);
+                w23[u] = *reinterpret_cast<const uint32_t*>(&b);
+            }
+            const auto s01 = __builtin_amdgcn_permlane32_swap(w01[0], w01[1], false, false);   // [tile 0 lanes 0-31 | tile 1 lanes 0-31]
+            const auto s23 = __builtin_amdgcn_permlane32_swap(w23[0], w23[1], false, false);
+            const uint32_t p01 = s01[0], p23 = s23[0];
+            if (acc.alive && k < N) {
+                const float2 f01 = __half22float2(*reinterpret_cast<const __half2*>(&p01));
+                const float2 f23 = __half22float2(*reinterpret_cast<const __half2*>(&p23));
+                nrc_composite_sample(acc, f01.x, f01.y, f23.x, f23.y, t, ic.esf, ic.dt_min, ic.dt_max, ic.thr, k + 1 >= N);
+            }
+        }
+        if (inside) nrc_composite_finish(acc, ic.bg_r, ic.bg_g, ic.bg_b, (int64_t)py * ic.width + px, rgb, alpha_out, depth_out);
+    }
 }
 
 __global__ void k_f32_to_f16(const float* __restrict__ src, __half* __restrict__ dst, int64_t n) {
@@ -1123,6 +1276,86 @@ int nrc_ngp_render_layers(const float* ts, int32_t* row_tile, const float* ray_o
                                     skipped_rows, (int)arena_rows, s);
         base += NRC_QUERY_CHUNK;
     } while (base < M);
+    NRC_LAUNCH_CHECK();
+    return NRC_OK;
+}
+
+/* workspace of the single-pass frame: [features of the largest chunk][ray_sh][order: n_ray_tiles i32][chunk table: 4 i32 per chunk][queue: 1 i32 per chunk] */
+#ifndef NRC_FRAME_ROW_BUDGET
+#define NRC_FRAME_ROW_BUDGET (int64_t(1) << 21)   // rows of 64 slots per encode / MLP round of the single-pass frame (8 GiB of features; an 800x800 bench
+                                                  // frame has ~1.2 Mi rows: ONE round).  Larger frames are cut into chunks of whole ray tiles.
+#endif
+static int64_t frame_budget(int64_t row_budget) { return row_budget > 0 ? row_budget : NRC_FRAME_ROW_BUDGET; }
+static int64_t frame_chunks(int64_t n_rows, int64_t budget, int32_t max_samples) {
+    return n_rows <= budget ? 1 : nrc_cdiv(n_rows, budget - max_samples);
+}
+static int64_t round256(int64_t b) { return (b + 255) / 256 * 256; }
+int64_t nrc_ngp_render_frame_ws_bytes(int64_t n_rows, int64_t n_ray_tiles, int32_t max_samples, int64_t row_budget) {
+    const int64_t budget = frame_budget(row_budget);
+    if (n_rows < 0 || n_ray_tiles < 0 || max_samples < 1 || budget < 2 * (int64_t)max_samples) return NRC_ERR_INVALID;
+    const int64_t chunks = frame_chunks(n_rows, budget, max_samples);
+    const int64_t feat_rows = n_rows < budget ? n_rows : budget;
+    return round256((feat_rows > 0 ? feat_rows : 1) * 64 * 64) + round256(n_ray_tiles * 2048) + round256(n_ray_tiles * 4) + round256(chunks * 20);
+}
+
+int nrc_ngp_render_frame(const float* ts_arena, int32_t* row_tile, const float* ray_od, int64_t n_rows, int64_t n_ray_tiles, const float* xyz_min3,
+                         const float* xyz_size3, const void* density_weights_f16, const void* color_weights_f16, const void* table_f16, int32_t n_levels,
+                         int32_t log2_hashmap_size, int32_t base_resolution, float per_level_scale, const int32_t* ray_cnt, const int32_t* tile_off,
+                         int32_t width, int32_t height, int64_t tile_begin, int32_t cascades, float exp_step_factor, int32_t grid_size, int32_t max_samples,
+                         float T_threshold, const float* bg3_host, float* rgb, float* alpha, float* depth, int64_t row_budget, void* workspace,
+                         nrc_stream_t stream) {
+    NRC_ENTER();
+    const int64_t budget = frame_budget(row_budget);
+    if (n_rows < 0 || n_ray_tiles < 1 || width < 1 || height < 1 || tile_begin < 0 || cascades < 1 || grid_size < 1 || max_samples < 1 ||
+        budget < 2 * (int64_t)max_samples || !density_weights_f16 || !color_weights_f16 || !table_f16 || !xyz_min3 || !xyz_size3 || !bg3_host)
+        return NRC_ERR_INVALID;
+    if (n_levels != 16) return NRC_ERR_UNSUPPORTED;
+    if (!ray_od || !ray_cnt || !tile_off || !rgb || !alpha || !depth || !workspace || (n_rows > 0 && (!ts_arena || !row_tile))) return NRC_ERR_INVALID;
+    GridCfg g;
+    const int rc = make_grid_cfg(n_levels, log2_hashmap_size, base_resolution, per_level_scale, g, nullptr);
+    if (rc != NRC_OK) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t chunks = frame_chunks(n_rows, budget, max_samples);
+    const int64_t feat_rows = n_rows < budget ? n_rows : budget;
+    char* wsp = (char*)workspace;
+    uint4* feat = (uint4*)wsp;
+    wsp += round256((feat_rows > 0 ? feat_rows : 1) * 64 * 64);
+    h8* ray_sh = (h8*)wsp;
+    wsp += round256(n_ray_tiles * 2048);
+    int32_t* order = (int32_t*)wsp;
+    wsp += round256(n_ray_tiles * 4);
+    int32_t* chunk_tab = (int32_t*)wsp;
+    int32_t* queue = chunk_tab + 4 * chunks;
+    QueryIn in = {};
+    in.ts = ts_arena; in.row_tile = row_tile; in.ray_od = ray_od; in.tile_off = tile_off; in.arena_rows = max_samples;
+    for (int k = 0; k < 3; k++) { in.mn[k] = xyz_min3[k]; in.sz[k] = xyz_size3[k]; }
+    ImageCfg ic;
+    ic.width = width; ic.height = height; ic.tiles_x = (width + NRC_TILE_W - 1) / NRC_TILE_W; ic.tile_begin = tile_begin;
+    // calc_dt of the test kernel (raymarching.cu:11-13 with `cascades` in place of `scale`, :370), as nrc_ngp_composite_image
+    ic.esf = exp_step_factor; ic.dt_min = 1.73205080757f / max_samples; ic.dt_max = 1.73205080757f * 2 * (float)cascades / grid_size;
+    ic.thr = T_threshold; ic.bg_r = bg3_host[0]; ic.bg_g = bg3_host[1]; ic.bg_b = bg3_host[2];
+    // one workgroup per CU and MLP wave slot: the waves stay resident and drain the tile queue
+    int dev = 0, n_cu = 0;
+    hipGetDevice(&dev);
+    hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
+    const int64_t resident = (int64_t)(n_cu > 0 ? n_cu : 256) * NRC_MLP_WAVES, mlp_blocks = nrc_cdiv(n_ray_tiles, 4) < resident ? nrc_cdiv(n_ray_tiles, 4) : resident;
+    NRC_STAGE(s, nullptr);
+    // SH of every ray + the ray tile of every row (for the encoder)
+    hipLaunchKernelGGL(k_ray_sh, dim3((unsigned)nrc_cdiv(n_ray_tiles * 64, 256)), dim3(256), 0, s, ray_od, n_ray_tiles, ray_sh, tile_off, row_tile, n_rows);
+    NRC_STAGE(s, "k_ray_sh");
+    hipLaunchKernelGGL(k_tile_chunks, dim3((unsigned)chunks), dim3(1024), 0, s, tile_off, n_ray_tiles, chunks > 1 ? budget - max_samples : n_rows + 1,
+                       chunk_tab, order, queue);
+    NRC_STAGE(s, "k_tile_chunks");
+    for (int64_t c = 0; c < chunks; c++) {
+        if (n_rows > 0) {
+            in.chunk_rows = chunk_tab + 4 * c + 2;
+            launch_encode<SRC_TILED>(in, 0, feat_rows * 64, table_f16, g, feat, s);
+            NRC_STAGE(s, "k_grid_encode");
+        }
+        hipLaunchKernelGGL(k_ngp_mlp_composite, dim3((unsigned)mlp_blocks), dim3(256), 0, s, feat, ray_sh, (const __half*)density_weights_f16,
+                           (const __half*)color_weights_f16, ts_arena, (int)max_samples, ray_cnt, tile_off, order, chunk_tab + 4 * c, queue + c, ic, rgb, alpha, depth);
+        NRC_STAGE(s, "k_ngp_mlp");   // (k_ngp_mlp_composite: the stage keeps the MLP kernel's name, where the in-frame ruler looks for it)
+    }
     NRC_LAUNCH_CHECK();
     return NRC_OK;
 }

@@ -146,6 +146,7 @@ class InstantNGPRenderer:
     COUNT_MAILBOX = True       # fused image path: the row count reaches the host through a mapped host mailbox (False: device-to-host copy)
     POSE_ENCODER_SHAPE = True  # fused image path: the encoder's brick of samples per wave follows the camera's axes (False: the fixed 8 x 2 x 4 default)
     ARENA_IN_PLACE = True      # fused image path, single pass: the query / compositing kernels read the samples from the count pass's arena (False: copied to compact rows first)
+    FRAME_ROW_BUDGET = 0       # single pass from the arena: rows per encode / MLP round (chunks of whole ray tiles; 0 = the library's default, one round at 800x800)
 
     def __init__(self, model: InstantNGPModel, MAX_SAMPLES: int = 1024, EXPONENTIAL_STEPS: bool = False, DENSITY_THRESHOLD: float = 0.01) -> None:
         self.model = model
@@ -386,6 +387,30 @@ class InstantNGPRenderer:
             lib.nrc_ngp_set_encoder_shape(*fc['enc_shape'])
         _lib.check(lib.nrc_ngp_query_samples(*args), 'ngp_query_samples')
 
+    def _frame_args(self, fc: dict, ws: dict, out: dict, tile_begin: int, nt: int) -> list:
+        """argument list of nrc_ngp_render_frame (the single pass from the arena: MLP and compositing in one kernel) with the row count (index 3)
+        still open; its workspace follows the sample buffers' capacity"""
+        m, lib, cam, vp, g = self.model, _lib.load(), fc['camera'], ctypes.c_void_p, fc['grid']
+        budget = int(self.FRAME_ROW_BUDGET)
+        if ws.get('fws_key') != (ws['cap'], budget):
+            ws['fws'] = None
+            ws['fws'] = torch.empty(int(lib.nrc_ngp_render_frame_ws_bytes(ws['cap'], nt, self.MAX_SAMPLES, budget)), dtype=torch.uint8, device=ws['ray_od'].device)
+            ws['fws_key'] = (ws['cap'], budget)
+        return [_lib.ptr(ws['ts_prov']), _lib.ptr(ws['row_tile']), _lib.ptr(ws['ray_od']), 0, nt, ctypes.cast(fc['mn'], vp), ctypes.cast(fc['sz'], vp),
+                _lib.ptr(m.encoding_xyz._half_params()), _lib.ptr(m.color_mlp_with_encoding._half_params()), _lib.ptr(m.encoding_xyz._table16()),
+                g['n_levels'], g['log2_hashmap_size'], g['base_resolution'], float(g['per_level_scale']), _lib.ptr(ws['ray_cnt']), _lib.ptr(ws['tile_off']),
+                cam.width, cam.height, int(tile_begin), m.cascades, float(fc['esf']), m.RESOLUTION, self.MAX_SAMPLES, 1e-4, ctypes.cast(fc['bg'], vp),
+                _lib.ptr(out['rgb']), _lib.ptr(out['alpha']), _lib.ptr(out['depth']), budget, _lib.ptr(ws['fws']), _lib.stream_of(ws['ray_od'])]
+
+    def _fused_frame(self, fc: dict, ws: dict, out: dict, rows: int, tile_begin: int, nt: int, frame_args: list | None = None) -> None:
+        """single pass from the arena: encode + MLP with the compositing inside the MLP kernel (nrc_ngp_render_frame)"""
+        lib = _lib.load()
+        args = frame_args if frame_args is not None else self._frame_args(fc, ws, out, tile_begin, nt)
+        args[3] = rows
+        if self.POSE_ENCODER_SHAPE:
+            lib.nrc_ngp_set_encoder_shape(*fc['enc_shape'])
+        _lib.check(lib.nrc_ngp_render_frame(*args), 'ngp_render_frame')
+
     def _fused_composite(self, fc: dict, ws: dict, out: dict, tile_begin: int, nt: int, row_capacity: int = 0, arena: bool = False) -> None:
         m, lib, cam = self.model, _lib.load(), fc['camera']
         _lib.check(lib.nrc_ngp_composite_image(
@@ -531,7 +556,9 @@ class InstantNGPRenderer:
             ticket = self._fused_count(fc, ws, tile_begin, nt, mailbox)
             # what does not depend on the count is prepared before the wait (the sample buffers exist from the previous frame; a frame that needs
             # more regrows them below and marshals again)
-            ready = self._query_args(fc, ws, nt, False, arena) if ws['cap'] > 0 else None
+            ready = None
+            if ws['cap'] > 0:
+                ready = self._frame_args(fc, ws, out, tile_begin, nt) if arena else self._query_args(fc, ws, nt, False, arena)
             cap_before = ws['cap']
             counts = mailbox.counts(ticket, dev) if mailbox is not None else None
         finally:
@@ -580,6 +607,8 @@ class InstantNGPRenderer:
             if 'skipped_host' not in ws:
                 ws['skipped_host'] = torch.zeros(1, dtype=torch.int32).pin_memory()
             ws['skipped_host'].copy_(ws['skipped'], non_blocking=True)   # for the next frame's policy; ordered behind this frame on the stream
+        elif arena and rows > 0:
+            self._fused_frame(fc, ws, out, rows, tile_begin, nt, frame_args=ready if ws['cap'] == cap_before else None)
         else:
             self._fused_write_query(fc, ws, rows, nt, arena=arena, query_args=ready if ws['cap'] == cap_before else None)
             self._fused_composite(fc, ws, out, tile_begin, nt, arena=arena)
