@@ -33,8 +33,9 @@ enum {
  * 4 = round 4, later: nrc_gs_preprocess and nrc_ngp_render_count gained count_mailbox / mailbox_ticket, nrc_host_mailbox_alloc / _free are new;
  * nrc_ngp_query_samples gained arena_tile_off / arena_rows, nrc_ngp_composite_image arena_rows, nrc_ngp_render_write accepts ts = NULL;
  * nrc_photometric_loss_* are new; 5 = round 5: group 13 (the fused InstantNGP training iteration) is new; nrc_ngp_train_query_forward gained
- * n_samples_dev (NULL = every row, as before). */
-#define NRC_ABI_VERSION 6
+ * n_samples_dev (NULL = every row, as before); 7 = the band entry points of group 4 (nrc_gs_*_band: one frame rendered and differentiated as bands of tile
+ * rows) are new, every earlier signature is unchanged. */
+#define NRC_ABI_VERSION 7
 /* library identification; also used by the loader's symbol check */
 int nrc_abi_version(void);
 const char* nrc_build_info(void);
@@ -373,6 +374,50 @@ int nrc_gs_backward_rest_step(int32_t P, int32_t D, int32_t M, int32_t W, int32_
                     float* dL_dmean2D, float* dL_dopacity, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscale,
                     float* dL_drot, float* grad_records, int32_t records_clear, float* rest_exp_avg, float* rest_exp_avg_sq, float lr, float beta1, float beta2,
                     float eps, float bias_correction1, float bias_correction2, nrc_stream_t stream);
+/* Bands (ABI 7): ONE frame rendered and differentiated as contiguous ranges of 16-pixel tile rows, [tile_row_begin, tile_row_begin + n_tile_rows) of the
+ * gy = ceil(H / 16) rows -- the unit a single view is sharded by across GPUs (nerficg_amd.parallel.tile_row_band).  The four entry points below are
+ * nrc_gs_bin_hist_bytes / nrc_gs_preprocess / nrc_gs_bin_render / nrc_gs_backward with a band; the entry points above are the band (0, gy).  A band is checked
+ * before anything else (no HIP call in front of it): tile_row_begin < 0, n_tile_rows < 1 or tile_row_begin + n_tile_rows > gy return NRC_ERR_INVALID.
+ *   nrc_gs_preprocess_band : projects ALL P Gaussians -- radii, depths, points_xy, conic_opacity, rgb, clamped, cov3D, tiles_touched and splat_records are those
+ *                       of the whole-frame call bit for bit, and so is the depth order.  Binning is CLIPPED: a Gaussian's tile rectangle is intersected with the
+ *                       band where the rectangles are made, a Gaussian that misses the band takes part in nothing behind the depth sort, tiles outside the
+ *                       band get empty `ranges`, num_rendered[0] / [1] count the band's instances / spans only (point_list and span_capacity may be sized for
+ *                       the band; the bytes of the workspace depend on span_capacity alone), instance_capacity and the count mailbox work as on a frame.  The
+ *                       list of a band tile equals that tile's list of the whole-frame call.  tile_fill receives the launch order of the BAND's gx *
+ *                       n_tile_rows tiles in its first entries.  band_mask (P) u8, optional: 1 where the clipped rectangle is non-empty, i.e. the Gaussians
+ *                       that can receive a gradient from this band (written on the binning-workspace path only).
+ *   nrc_gs_bin_render_band : blends the band's tiles only (gx * n_tile_rows workgroups).  out_color, n_contrib, final_T stay FULL-FRAME buffers of which only the
+ *                       pixel rows [16 begin, min(H, 16 (begin + n))) are written -- bit for bit the whole-frame call's values --, the rest is untouched.
+ *   nrc_gs_backward_band : dL_dpix is full-frame, only the band's rows are read; the blend backward runs over the band's tiles, the per-Gaussian backward over
+ *                       all P on records that hold the band's contributions.  It is linear in the records: every gradient tensor is this band's SHARE of the
+ *                       whole-frame gradient (the shares of a partition sum to it), exactly zero for a Gaussian whose rectangle misses the band.  There is no
+ *                       band form of nrc_gs_backward_rest_step: an Adam step inside the backward pass would be taken on a partial gradient.
+ * The per-tile key sort fallback (more than 256 tile rows or columns, or bin_hist == NULL) bins whole frames only: with P > 0 a band other than (0, gy)
+ * returns NRC_ERR_UNSUPPORTED there. */
+int64_t nrc_gs_bin_hist_bytes_band(int32_t P, int32_t W, int32_t H, int64_t span_capacity, int32_t tile_row_begin, int32_t n_tile_rows);
+int nrc_gs_preprocess_band(int32_t P, int32_t D, int32_t M, int32_t W, int32_t H, const float* means3D, const float* shs,
+                      const float* shs_rest, int32_t raw_parameters, const float* colors_precomp, const float* opacities, const float* scales, float scale_modifier,
+                      const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                      const float* campos, const float* camera_dev, float tan_fovx, float tan_fovy, int32_t* radii, float* depths,
+                      float* points_xy, float* conic_opacity, float* rgb, uint8_t* clamped, float* cov3D, uint32_t* tiles_touched,
+                      uint32_t* tile_counts, uint32_t* ranges, uint32_t* tile_fill, uint32_t* bin_hist, int64_t span_capacity,
+                      int64_t instance_capacity, float* splat_records, int64_t* num_rendered, int64_t* count_mailbox, int64_t mailbox_ticket,
+                      int32_t tile_row_begin, int32_t n_tile_rows, uint8_t* band_mask, nrc_stream_t stream);
+int nrc_gs_bin_render_band(int32_t P, int32_t W, int32_t H, const float* bg, const float* camera_dev, const int32_t* radii,
+                      const float* depths, const float* points_xy, const float* conic_opacity, const float* rgb,
+                      const uint32_t* ranges, uint32_t* tile_fill, const uint32_t* bin_hist, int64_t span_capacity,
+                      int64_t instance_capacity, uint64_t* keys, int32_t* point_list, const float* splat_records, float* out_color,
+                      uint32_t* n_contrib, float* final_T, int32_t tile_row_begin, int32_t n_tile_rows, nrc_stream_t stream);
+int nrc_gs_backward_band(int32_t P, int32_t D, int32_t M, int32_t W, int32_t H, const float* bg, const float* means3D, const float* shs,
+                    const float* shs_rest, int32_t raw_parameters, const float* opacities, const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
+                    const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix, const float* campos,
+                    const float* camera_dev, float tan_fovx, float tan_fovy, const int32_t* radii, const float* points_xy, const float* conic_opacity,
+                    const float* rgb, const uint8_t* clamped, const float* cov3D, const int32_t* point_list,
+                    const uint32_t* ranges, const float* splat_records, const uint32_t* tile_order, const uint32_t* n_contrib,
+                    const float* final_T, const float* dL_dpix,
+                    float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
+                    float* dL_dcov3D, float* dL_dsh, float* dL_dsh_rest, float* dL_dscale, float* dL_drot, float* grad_records,
+                    int32_t records_clear, int32_t tile_row_begin, int32_t n_tile_rows, nrc_stream_t stream);
 
 /* =====================================================================================================
  * Group 5 -- ray generation (replaces PerspectiveCamera.compute_local_ray_directions src/Cameras/Perspective.py:64-94

@@ -461,9 +461,12 @@ __global__ void __launch_bounds__(PRE_BLOCK) k_preprocess(int P, GsCam cam_arg, 
 // 1 M Gaussians: 4 x (9.5 + 4.9 + 19.6) + 6.4 us in 13 launches -> 5 launches (numbers in DESIGN.md section 3.3).
 #define DK_BLOCK 256
 #define DK_ITEMS 16
-__global__ void __launch_bounds__(DK_BLOCK) k_depth_keys(int P, int gx, int gy, const int32_t* __restrict__ radii, const float* __restrict__ depths,
+// Band (tile rows [yb0, yb1) of the frame; the whole frame is (0, gy)): a rectangle is cut to the band HERE, so the sort carries clipped rectangles and
+// every binning kernel behind it sees band rows only -- a Gaussian that misses the band is RECT_NONE (it keeps its place in the depth order, which does
+// not depend on the band).  band_mask (optional): 1 where the clipped rectangle is non-empty = the Gaussians that can receive a gradient from the band.
+__global__ void __launch_bounds__(DK_BLOCK) k_depth_keys(int P, int gx, int gy, int yb0, int yb1, const int32_t* __restrict__ radii, const float* __restrict__ depths,
                                                          const float* __restrict__ points_xy, uint32_t* __restrict__ keys, uint32_t* __restrict__ rects,
-                                                         uint32_t* __restrict__ hdr, uint32_t* __restrict__ status, int64_t n_status) {
+                                                         uint32_t* __restrict__ hdr, uint32_t* __restrict__ status, int64_t n_status, uint8_t* __restrict__ band_mask) {
     __shared__ uint32_t h[4][256];
     __shared__ uint32_t rows[SPAN_DIM_MAX];
 #pragma unroll
@@ -491,6 +494,7 @@ __global__ void __launch_bounds__(DK_BLOCK) k_depth_keys(int P, int gx, int gy, 
             const float pxy[2] = {xy[r].x, xy[r].y};
             int rmin[2], rmax[2];
             tile_rect(pxy, rad[r], gx, gy, rmin, rmax);
+            rmin[1] = max(rmin[1], yb0); rmax[1] = min(rmax[1], yb1);
             if (rmax[0] > rmin[0] && rmax[1] > rmin[1]) {
                 rect = (uint32_t)rmin[0] | (uint32_t)rmin[1] << 8 | (uint32_t)(rmax[0] - rmin[0] - 1) << 16 | (uint32_t)(rmax[1] - rmin[1] - 1) << 24;
                 for (int y = rmin[1]; y < rmax[1]; y++) atomicAdd(&rows[y], 1u);
@@ -499,6 +503,7 @@ __global__ void __launch_bounds__(DK_BLOCK) k_depth_keys(int P, int gx, int gy, 
         const uint32_t key = rad[r] > 0 ? __float_as_uint(dep[r]) : 0xffffffffu;  // invisible Gaussians go last
         keys[i] = key;
         rects[i] = rect;
+        if (band_mask) band_mask[i] = rect != RECT_NONE;
         atomicAdd(&h[0][key & 255u], 1u);
         atomicAdd(&h[1][(key >> 8) & 255u], 1u);
         atomicAdd(&h[2][(key >> 16) & 255u], 1u);
@@ -901,11 +906,11 @@ __global__ void __launch_bounds__(64) k_item_count(int gx, int gy, const uint32_
 // finishes LAST runs what used to be two more launches: the scan of the tile totals into `ranges` (k_scan_tiles) and the launch order of the
 // tiles, longest list first (k_tile_order).  Hand-over: the totals are written through (sc1) and drained, one lane per workgroup takes a
 // ticket with a returning agent-scope atomic, the last ticket holder reads the totals with sc1 loads.
-__device__ __forceinline__ void tile_order_of(int n_tiles, const uint32_t* __restrict__ ranges, uint32_t* __restrict__ order, uint32_t* hist, uint32_t* wsum);
+__device__ __forceinline__ void tile_order_of(int t_first, int n_tiles, const uint32_t* __restrict__ ranges, uint32_t* __restrict__ order, uint32_t* hist, uint32_t* wsum);
 #define IS_XL 32     // tiles (columns) per workgroup
 #define IS_NG 32     // item groups per workgroup: thread (xl, g) scans the g-th 1/32 of the row's items for column x, sixteen loads at a time
                      // (~250 items per row at 1 M Gaussians: one batch for the sum, one for the prefix)
-__global__ void __launch_bounds__(1024) k_item_scan(int gx, int gy, int item_cap, const uint32_t* __restrict__ nitems, const uint32_t* __restrict__ ioff,
+__global__ void __launch_bounds__(1024) k_item_scan(int gx, int gy, int yb0, int yb1, int item_cap, const uint32_t* __restrict__ nitems, const uint32_t* __restrict__ ioff,
                                                     uint32_t* __restrict__ cnt2, uint32_t* __restrict__ tcount, uint32_t* __restrict__ done_counter,
                                                     uint32_t cap, uint32_t* __restrict__ ranges, uint32_t* __restrict__ order, int64_t* __restrict__ num_rendered,
                                                     int64_t* __restrict__ mailbox, int64_t mailbox_ticket) {
@@ -994,7 +999,7 @@ __global__ void __launch_bounds__(1024) k_item_scan(int gx, int gy, int item_cap
         trun += v;
     }
     __syncthreads();
-    tile_order_of(n, ranges, order, hist, wave_tot);
+    tile_order_of(yb0 * gx, (yb1 - yb0) * gx, ranges, order, hist, wave_tot);   // the band's tiles only: the blend kernels launch one workgroup per entry
 }
 // level 2, scatter: ids of the item's spans appended to the tiles they cover; tile (y, x) of this item starts at ranges[tile].first + cnt2[item][x]
 template <bool CAPPED>  // CAPPED: the caller fixed the length of point_list (graph capture); entries that would land behind it are dropped
@@ -1151,11 +1156,13 @@ __global__ void __launch_bounds__(256) k_sort_tiles(const uint32_t* __restrict__
 // that starts late finishes alone.  The render kernels therefore take their tile from a table sorted by list length, longest first
 // (counting sort over 2 048 length classes, one workgroup).
 // one workgroup of 1024 threads; hist: 2048 words, wsum: 16 words of LDS.  `ranges` may have been written by this very workgroup (behind a barrier).
-__device__ __forceinline__ void tile_order_of(int n_tiles, const uint32_t* __restrict__ ranges, uint32_t* __restrict__ order, uint32_t* hist, uint32_t* wsum) {
+// Orders the tiles [t_first, t_first + n_tiles) -- a band of tile rows is a contiguous tile range -- into order[0 .. n_tiles): tiles outside the band
+// (length 0 like an empty band tile) never enter the table, so a blend grid of n_tiles workgroups covers the band and nothing else.
+__device__ __forceinline__ void tile_order_of(int t_first, int n_tiles, const uint32_t* __restrict__ ranges, uint32_t* __restrict__ order, uint32_t* hist, uint32_t* wsum) {
     for (int k = threadIdx.x; k < 2048; k += 1024) hist[k] = 0u;
     __syncthreads();
     auto cls = [&](int t) { const uint32_t len = ranges[2 * t + 1] - ranges[2 * t]; return 2047u - min(len >> 2, 2047u); };  // class 0 = longest
-    for (int t = threadIdx.x; t < n_tiles; t += 1024) atomicAdd(&hist[cls(t)], 1u);
+    for (int t = t_first + (int)threadIdx.x; t < t_first + n_tiles; t += 1024) atomicAdd(&hist[cls(t)], 1u);
     __syncthreads();
     // exclusive scan of the 2048 classes: two per thread
     const uint32_t a = hist[2 * threadIdx.x], b = hist[2 * threadIdx.x + 1];
@@ -1175,12 +1182,12 @@ __device__ __forceinline__ void tile_order_of(int n_tiles, const uint32_t* __res
     __syncthreads();
     // placement with an LDS cursor per class: the order inside a class depends on the atomics' arrival, which only permutes the launch order of
     // tiles of (nearly) equal length -- every tile's result is independent of when it runs
-    for (int t = threadIdx.x; t < n_tiles; t += 1024) order[atomicAdd(&hist[cls(t)], 1u)] = (uint32_t)t;
+    for (int t = t_first + (int)threadIdx.x; t < t_first + n_tiles; t += 1024) order[atomicAdd(&hist[cls(t)], 1u)] = (uint32_t)t;
 }
-__global__ void __launch_bounds__(1024) k_tile_order(int n_tiles, const uint32_t* __restrict__ ranges, uint32_t* __restrict__ order) {
+__global__ void __launch_bounds__(1024) k_tile_order(int t_first, int n_tiles, const uint32_t* __restrict__ ranges, uint32_t* __restrict__ order) {
     __shared__ uint32_t hist[2048];
     __shared__ uint32_t wsum[16];
-    tile_order_of(n_tiles, ranges, order, hist, wsum);
+    tile_order_of(t_first, n_tiles, ranges, order, hist, wsum);
 }
 
 // ------------------------------------------------------------------------------------------------ 5. render
@@ -2071,15 +2078,26 @@ int64_t nrc_gs_bin_hist_bytes(int32_t P, int32_t W, int32_t H, int64_t span_capa
     return gs_bin_ws(nullptr, P, gx, gy, span_capacity > 0 ? span_capacity : gs_default_span_cap(P)).words * (int64_t)sizeof(uint32_t);
 }
 
-int nrc_gs_preprocess(int32_t P, int32_t D, int32_t M, int32_t W, int32_t H, const float* means3D, const float* shs, const float* shs_rest,
+// a band = tile rows [begin, begin + n) of the frame's gy rows; checked by the band entry points before anything else (no HIP call in front of it)
+static bool gs_band_ok(int32_t H, int32_t tile_row_begin, int32_t n_tile_rows) {
+    if (H < 1 || tile_row_begin < 0 || n_tile_rows < 1) return false;
+    return (int64_t)tile_row_begin + n_tile_rows <= (int64_t)((H + TILE - 1) / TILE);
+}
+static int32_t gs_all_rows(int32_t H) { return H >= 1 ? (H + TILE - 1) / TILE : 1; }   // (H < 1 is refused by the entry point's own checks)
+
+int64_t nrc_gs_bin_hist_bytes_band(int32_t P, int32_t W, int32_t H, int64_t span_capacity, int32_t tile_row_begin, int32_t n_tile_rows) {
+    if (!gs_band_ok(H, tile_row_begin, n_tile_rows)) return NRC_ERR_INVALID;
+    return nrc_gs_bin_hist_bytes(P, W, H, span_capacity);   // one layout for every band: what shrinks with the band is the span capacity the caller asks for
+}
+
+static int gs_preprocess_impl(int32_t P, int32_t D, int32_t M, int32_t W, int32_t H, const float* means3D, const float* shs, const float* shs_rest,
                       int32_t raw_parameters, const float* colors_precomp, const float* opacities, const float* scales, float scale_modifier,
                       const float* rotations, const float* cov3D_precomp, const float* viewmatrix_host, const float* projmatrix_host,
                       const float* campos_host, const float* camera_dev, float tan_fovx, float tan_fovy, int32_t* radii, float* depths,
                       float* points_xy, float* conic_opacity, float* rgb, uint8_t* clamped, float* cov3D, uint32_t* tiles_touched,
                       uint32_t* tile_counts, uint32_t* ranges, uint32_t* tile_fill, uint32_t* bin_hist, int64_t span_capacity,
                       int64_t instance_capacity, float* splat_records, int64_t* num_rendered, int64_t* count_mailbox, int64_t mailbox_ticket,
-                      nrc_stream_t stream) {
-    NRC_ENTER();
+                      int32_t yb0, int32_t n_rows, uint8_t* band_mask, nrc_stream_t stream) {
     GsCam cam;
     const int rc = make_cam(cam, W, H, D, M, viewmatrix_host, projmatrix_host, campos_host, camera_dev, tan_fovx, tan_fovy, scale_modifier, raw_parameters);
     if (rc != NRC_OK) return rc;
@@ -2097,6 +2115,8 @@ int nrc_gs_preprocess(int32_t P, int32_t D, int32_t M, int32_t W, int32_t H, con
     const bool lds_path = cam.gx <= SPAN_DIM_MAX && cam.gy <= SPAN_DIM_MAX && bin_hist != nullptr;
     if (instance_capacity > 0 && P > 0 && !lds_path) return NRC_ERR_UNSUPPORTED;  // the per-tile key sort fallback sizes its keys from the count
     if (count_mailbox && !(P > 0 && lds_path)) return NRC_ERR_UNSUPPORTED;        // the counts reach the mailbox from the last workgroup of k_item_scan only
+    const int yb1 = yb0 + n_rows;
+    if (P > 0 && !lds_path && (yb0 != 0 || yb1 != cam.gy)) return NRC_ERR_UNSUPPORTED;   // the per-tile key sort fallback bins whole frames only
     NRC_STAGE(s, nullptr);
     if (!(P > 0 && lds_path)) nrc_zero_async(tile_counts, sizeof(uint32_t) * n_tiles, s);  // only the global-atomic fallback counts into it
     if (P > 0) {
@@ -2113,8 +2133,8 @@ int nrc_gs_preprocess(int32_t P, int32_t D, int32_t M, int32_t W, int32_t H, con
 #undef GS_PRE_ARGS
         if (lds_path) {
             // depth pre-sort of the Gaussians: 4 stable 8-bit passes, one launch each, (keyA, rectA) -> B -> A -> B -> (valA, rectA) = depth order
-            hipLaunchKernelGGL(k_depth_keys, dim3(nrc_cdiv(P, DK_BLOCK * DK_ITEMS)), dim3(DK_BLOCK), 0, s, P, cam.gx, cam.gy, radii, depths, points_xy, w.keyA, w.rectA,
-                               w.hdr, w.status, w.n_status);
+            hipLaunchKernelGGL(k_depth_keys, dim3(nrc_cdiv(P, DK_BLOCK * DK_ITEMS)), dim3(DK_BLOCK), 0, s, P, cam.gx, cam.gy, yb0, yb1, radii, depths, points_xy, w.keyA, w.rectA,
+                               w.hdr, w.status, w.n_status, band_mask);
             NRC_STAGE(s, "k_depth_keys");
             for (int pass = 0; pass < 4; pass++) {
                 const uint32_t *ki = (pass & 1) ? w.keyB : w.keyA, *vi = (pass & 1) ? w.valB : w.valA, *ri = (pass & 1) ? w.rectB : w.rectA;
@@ -2132,7 +2152,7 @@ int nrc_gs_preprocess(int32_t P, int32_t D, int32_t M, int32_t W, int32_t H, con
                                w.spans, w.cnt2);
             NRC_STAGE(s, "k_item_count");
             // per-(item, tile) cursors, tile totals; its last workgroup: ranges, instance count and the launch order of the tiles (into tile_fill)
-            hipLaunchKernelGGL(k_item_scan, dim3((unsigned)nrc_cdiv(cam.gx, IS_XL), cam.gy), dim3(1024), 0, s, cam.gx, cam.gy, w.item_cap, w.nitems, w.ioff, w.cnt2, w.tcount,
+            hipLaunchKernelGGL(k_item_scan, dim3((unsigned)nrc_cdiv(cam.gx, IS_XL), cam.gy), dim3(1024), 0, s, cam.gx, cam.gy, yb0, yb1, w.item_cap, w.nitems, w.ioff, w.cnt2, w.tcount,
                                w.hdr + RS_HDR_TICKET + 5, list_cap, ranges, tile_fill, num_rendered, count_mailbox, mailbox_ticket);
             NRC_STAGE(s, "k_item_scan");
         }
@@ -2145,6 +2165,36 @@ int nrc_gs_preprocess(int32_t P, int32_t D, int32_t M, int32_t W, int32_t H, con
     return NRC_OK;
 }
 
+int nrc_gs_preprocess(int32_t P, int32_t D, int32_t M, int32_t W, int32_t H, const float* means3D, const float* shs, const float* shs_rest,
+                      int32_t raw_parameters, const float* colors_precomp, const float* opacities, const float* scales, float scale_modifier,
+                      const float* rotations, const float* cov3D_precomp, const float* viewmatrix_host, const float* projmatrix_host,
+                      const float* campos_host, const float* camera_dev, float tan_fovx, float tan_fovy, int32_t* radii, float* depths,
+                      float* points_xy, float* conic_opacity, float* rgb, uint8_t* clamped, float* cov3D, uint32_t* tiles_touched,
+                      uint32_t* tile_counts, uint32_t* ranges, uint32_t* tile_fill, uint32_t* bin_hist, int64_t span_capacity,
+                      int64_t instance_capacity, float* splat_records, int64_t* num_rendered, int64_t* count_mailbox, int64_t mailbox_ticket,
+                      nrc_stream_t stream) {
+    NRC_ENTER();
+    return gs_preprocess_impl(P, D, M, W, H, means3D, shs, shs_rest, raw_parameters, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp,
+                              viewmatrix_host, projmatrix_host, campos_host, camera_dev, tan_fovx, tan_fovy, radii, depths, points_xy, conic_opacity, rgb, clamped, cov3D,
+                              tiles_touched, tile_counts, ranges, tile_fill, bin_hist, span_capacity, instance_capacity, splat_records, num_rendered, count_mailbox,
+                              mailbox_ticket, 0, gs_all_rows(H), nullptr, stream);
+}
+int nrc_gs_preprocess_band(int32_t P, int32_t D, int32_t M, int32_t W, int32_t H, const float* means3D, const float* shs, const float* shs_rest,
+                      int32_t raw_parameters, const float* colors_precomp, const float* opacities, const float* scales, float scale_modifier,
+                      const float* rotations, const float* cov3D_precomp, const float* viewmatrix_host, const float* projmatrix_host,
+                      const float* campos_host, const float* camera_dev, float tan_fovx, float tan_fovy, int32_t* radii, float* depths,
+                      float* points_xy, float* conic_opacity, float* rgb, uint8_t* clamped, float* cov3D, uint32_t* tiles_touched,
+                      uint32_t* tile_counts, uint32_t* ranges, uint32_t* tile_fill, uint32_t* bin_hist, int64_t span_capacity,
+                      int64_t instance_capacity, float* splat_records, int64_t* num_rendered, int64_t* count_mailbox, int64_t mailbox_ticket,
+                      int32_t tile_row_begin, int32_t n_tile_rows, uint8_t* band_mask, nrc_stream_t stream) {
+    if (!gs_band_ok(H, tile_row_begin, n_tile_rows)) return NRC_ERR_INVALID;
+    NRC_ENTER();
+    return gs_preprocess_impl(P, D, M, W, H, means3D, shs, shs_rest, raw_parameters, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp,
+                              viewmatrix_host, projmatrix_host, campos_host, camera_dev, tan_fovx, tan_fovy, radii, depths, points_xy, conic_opacity, rgb, clamped, cov3D,
+                              tiles_touched, tile_counts, ranges, tile_fill, bin_hist, span_capacity, instance_capacity, splat_records, num_rendered, count_mailbox,
+                              mailbox_ticket, tile_row_begin, n_tile_rows, band_mask, stream);
+}
+
 int nrc_gs_camera_block(const float* c2w_dev, const float* proj_t_dev, const float* bg3_dev, float* camera_dev_out, nrc_stream_t stream) {
     NRC_ENTER();
     if (!c2w_dev || !proj_t_dev || !camera_dev_out) return NRC_ERR_INVALID;
@@ -2153,11 +2203,10 @@ int nrc_gs_camera_block(const float* c2w_dev, const float* proj_t_dev, const flo
     return NRC_OK;
 }
 
-int nrc_gs_bin_render(int32_t P, int32_t W, int32_t H, const float* bg_host, const float* camera_dev, const int32_t* radii, const float* depths,
+static int gs_bin_render_impl(int32_t P, int32_t W, int32_t H, const float* bg_host, const float* camera_dev, const int32_t* radii, const float* depths,
                       const float* points_xy, const float* conic_opacity, const float* rgb, const uint32_t* ranges, uint32_t* tile_fill,
                       const uint32_t* bin_hist, int64_t span_capacity, int64_t instance_capacity, uint64_t* keys, int32_t* point_list,
-                      const float* splat_records, float* out_color, uint32_t* n_contrib, float* final_T, nrc_stream_t stream) {
-    NRC_ENTER();
+                      const float* splat_records, float* out_color, uint32_t* n_contrib, float* final_T, int32_t yb0, int32_t n_rows, nrc_stream_t stream) {
     if (P < 0 || W < 1 || H < 1 || (!bg_host && !camera_dev) || !ranges || !tile_fill || !out_color || !n_contrib || !final_T) return NRC_ERR_INVALID;
     if (instance_capacity < 0 || instance_capacity > 0xfffffffell) return NRC_ERR_INVALID;
     const uint32_t list_cap = instance_capacity > 0 ? (uint32_t)instance_capacity : 0xffffffffu;
@@ -2171,6 +2220,7 @@ int nrc_gs_bin_render(int32_t P, int32_t W, int32_t H, const float* bg_host, con
         const int n_tiles = cam.gx * cam.gy;
         const bool lds_path = cam.gx <= SPAN_DIM_MAX && cam.gy <= SPAN_DIM_MAX && bin_hist;
         if (!lds_path && (!keys || instance_capacity > 0)) return instance_capacity > 0 ? NRC_ERR_UNSUPPORTED : NRC_ERR_INVALID;
+        if (!lds_path && (yb0 != 0 || n_rows != cam.gy)) return NRC_ERR_UNSUPPORTED;   // the per-tile key sort fallback bins whole frames only
         if (lds_path) {
             const BinWs w = gs_bin_ws(const_cast<uint32_t*>(bin_hist), P, cam.gx, cam.gy, span_capacity > 0 ? span_capacity : gs_default_span_cap(P));
             if (instance_capacity > 0)
@@ -2190,14 +2240,33 @@ int nrc_gs_bin_render(int32_t P, int32_t W, int32_t H, const float* bg_host, con
     }
     // tile_fill has served the fallback scatter (if any): it now carries the launch order of the tiles, longest list first, for both render kernels
     if (!(P > 0 && cam.gx <= SPAN_DIM_MAX && cam.gy <= SPAN_DIM_MAX && bin_hist)) {   // the span path left the order in tile_fill already (k_item_scan)
-        hipLaunchKernelGGL(k_tile_order, dim3(1), dim3(1024), 0, s, cam.gx * cam.gy, ranges, tile_fill);
+        hipLaunchKernelGGL(k_tile_order, dim3(1), dim3(1024), 0, s, yb0 * cam.gx, n_rows * cam.gx, ranges, tile_fill);
         NRC_STAGE(s, "k_tile_order");
     }
-    hipLaunchKernelGGL(k_render, dim3(cam.gx * cam.gy), dim3(256), 0, s, cam, ranges, point_list, (const float4*)splat_records, tile_fill, bg[0], bg[1], bg[2],
+    // one workgroup per band tile: tile_fill lists the band's tiles only, so the pixel rows outside the band are never written
+    hipLaunchKernelGGL(k_render, dim3(cam.gx * n_rows), dim3(256), 0, s, cam, ranges, point_list, (const float4*)splat_records, tile_fill, bg[0], bg[1], bg[2],
                        camera_dev, out_color, n_contrib, final_T);
     NRC_STAGE(s, "k_render");
     NRC_LAUNCH_CHECK();
     return NRC_OK;
+}
+int nrc_gs_bin_render(int32_t P, int32_t W, int32_t H, const float* bg_host, const float* camera_dev, const int32_t* radii, const float* depths,
+                      const float* points_xy, const float* conic_opacity, const float* rgb, const uint32_t* ranges, uint32_t* tile_fill,
+                      const uint32_t* bin_hist, int64_t span_capacity, int64_t instance_capacity, uint64_t* keys, int32_t* point_list,
+                      const float* splat_records, float* out_color, uint32_t* n_contrib, float* final_T, nrc_stream_t stream) {
+    NRC_ENTER();
+    return gs_bin_render_impl(P, W, H, bg_host, camera_dev, radii, depths, points_xy, conic_opacity, rgb, ranges, tile_fill, bin_hist, span_capacity, instance_capacity,
+                              keys, point_list, splat_records, out_color, n_contrib, final_T, 0, gs_all_rows(H), stream);
+}
+int nrc_gs_bin_render_band(int32_t P, int32_t W, int32_t H, const float* bg_host, const float* camera_dev, const int32_t* radii, const float* depths,
+                      const float* points_xy, const float* conic_opacity, const float* rgb, const uint32_t* ranges, uint32_t* tile_fill,
+                      const uint32_t* bin_hist, int64_t span_capacity, int64_t instance_capacity, uint64_t* keys, int32_t* point_list,
+                      const float* splat_records, float* out_color, uint32_t* n_contrib, float* final_T, int32_t tile_row_begin, int32_t n_tile_rows,
+                      nrc_stream_t stream) {
+    if (!gs_band_ok(H, tile_row_begin, n_tile_rows)) return NRC_ERR_INVALID;
+    NRC_ENTER();
+    return gs_bin_render_impl(P, W, H, bg_host, camera_dev, radii, depths, points_xy, conic_opacity, rgb, ranges, tile_fill, bin_hist, span_capacity, instance_capacity,
+                              keys, point_list, splat_records, out_color, n_contrib, final_T, tile_row_begin, n_tile_rows, stream);
 }
 
 static int gs_backward_impl(int32_t P, int32_t D, int32_t M, int32_t W, int32_t H, const float* bg_host, const float* means3D, const float* shs,
@@ -2208,7 +2277,7 @@ static int gs_backward_impl(int32_t P, int32_t D, int32_t M, int32_t W, int32_t 
                     const float* splat_records, const uint32_t* tile_order, const uint32_t* n_contrib, const float* final_T, const float* dL_dpix,
                     float* dL_dmean2D, float* dL_dconic,
                     float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dsh_rest, float* dL_dscale,
-                    float* dL_drot, float* grad_records, int32_t records_clear, nrc_stream_t stream, RestAdam ra) {
+                    float* dL_drot, float* grad_records, int32_t records_clear, nrc_stream_t stream, RestAdam ra, int32_t n_rows) {
     GsCam cam;
     const int rc = make_cam(cam, W, H, D, M, viewmatrix_host, projmatrix_host, campos_host, camera_dev, tan_fovx, tan_fovy, scale_modifier, raw_parameters);
     if (rc != NRC_OK) return rc;
@@ -2229,7 +2298,8 @@ static int gs_backward_impl(int32_t P, int32_t D, int32_t M, int32_t W, int32_t 
         hipLaunchKernelGGL(k_zero_grads, dim3((unsigned)nrc_cdiv((int64_t)P * (GREC / 4), 256)), dim3(256), 0, s, P, (float4*)grad_records);
         NRC_STAGE(s, "k_zero_grads");
     }
-    hipLaunchKernelGGL(k_render_bw, dim3(cam.gx * cam.gy), dim3(256), 0, s, cam, ranges, point_list, (const float4*)splat_records, tile_order, bg[0], bg[1], bg[2],
+    // n_rows tile rows (< gy for a band): tile_order lists the tiles of the forward's band, one workgroup each
+    hipLaunchKernelGGL(k_render_bw, dim3(cam.gx * n_rows), dim3(256), 0, s, cam, ranges, point_list, (const float4*)splat_records, tile_order, bg[0], bg[1], bg[2],
                        camera_dev, n_contrib, final_T, dL_dpix, grad_records);
     NRC_STAGE(s, "k_render_bw");
 #define GS_PBW_ARGS P, cam, camera_dev, means3D, shs, shs_rest, opacities, use_sh, scales, rotations, use_sr, radii, clamped, cov3D, grad_records, dL_dmean2D, dL_dconic, dL_dcolor, \
@@ -2256,7 +2326,23 @@ int nrc_gs_backward(int32_t P, int32_t D, int32_t M, int32_t W, int32_t H, const
     return gs_backward_impl(P, D, M, W, H, bg_host, means3D, shs, shs_rest, raw_parameters, opacities, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
                             viewmatrix_host, projmatrix_host, campos_host, camera_dev, tan_fovx, tan_fovy, radii, points_xy, conic_opacity, rgb, clamped, cov3D, point_list,
                             ranges, splat_records, tile_order, n_contrib, final_T, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
-                            dL_dsh_rest, dL_dscale, dL_drot, grad_records, records_clear, stream, RestAdam{nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, 0.f, 1.f, 1.f});
+                            dL_dsh_rest, dL_dscale, dL_drot, grad_records, records_clear, stream, RestAdam{nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, 0.f, 1.f, 1.f}, gs_all_rows(H));
+}
+int nrc_gs_backward_band(int32_t P, int32_t D, int32_t M, int32_t W, int32_t H, const float* bg_host, const float* means3D, const float* shs,
+                    const float* shs_rest, int32_t raw_parameters, const float* opacities, const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
+                    const float* cov3D_precomp, const float* viewmatrix_host, const float* projmatrix_host, const float* campos_host,
+                    const float* camera_dev, float tan_fovx, float tan_fovy, const int32_t* radii, const float* points_xy, const float* conic_opacity,
+                    const float* rgb, const uint8_t* clamped, const float* cov3D, const int32_t* point_list, const uint32_t* ranges,
+                    const float* splat_records, const uint32_t* tile_order, const uint32_t* n_contrib, const float* final_T, const float* dL_dpix,
+                    float* dL_dmean2D, float* dL_dconic,
+                    float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dsh_rest, float* dL_dscale,
+                    float* dL_drot, float* grad_records, int32_t records_clear, int32_t tile_row_begin, int32_t n_tile_rows, nrc_stream_t stream) {
+    if (!gs_band_ok(H, tile_row_begin, n_tile_rows)) return NRC_ERR_INVALID;
+    NRC_ENTER();
+    return gs_backward_impl(P, D, M, W, H, bg_host, means3D, shs, shs_rest, raw_parameters, opacities, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
+                            viewmatrix_host, projmatrix_host, campos_host, camera_dev, tan_fovx, tan_fovy, radii, points_xy, conic_opacity, rgb, clamped, cov3D, point_list,
+                            ranges, splat_records, tile_order, n_contrib, final_T, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
+                            dL_dsh_rest, dL_dscale, dL_drot, grad_records, records_clear, stream, RestAdam{nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, 0.f, 1.f, 1.f}, n_tile_rows);
 }
 
 /* nrc_gs_backward whose preprocessing backward applies the optimizer's Adam step to the `rest` SH tensor itself (shs_rest_param = the tensor passed as shs_rest in the
@@ -2275,7 +2361,7 @@ int nrc_gs_backward_rest_step(int32_t P, int32_t D, int32_t M, int32_t W, int32_
                             nullptr, nullptr, nullptr, camera_dev, tan_fovx, tan_fovy, radii, points_xy, conic_opacity, rgb, clamped, cov3D, point_list,
                             ranges, splat_records, tile_order, n_contrib, final_T, dL_dpix, dL_dmean2D, nullptr, dL_dopacity, nullptr, dL_dmean3D, dL_dcov3D, dL_dsh,
                             nullptr, dL_dscale, dL_drot, grad_records, records_clear, stream,
-                            RestAdam{shs_rest_param, rest_exp_avg, rest_exp_avg_sq, lr, beta1, beta2, eps, bias_correction1, bias_correction2});
+                            RestAdam{shs_rest_param, rest_exp_avg, rest_exp_avg_sq, lr, beta1, beta2, eps, bias_correction1, bias_correction2}, gs_all_rows(H));
 }
 
 }  // extern "C"

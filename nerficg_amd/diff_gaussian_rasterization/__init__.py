@@ -21,7 +21,7 @@ import torch
 
 from .. import _lib
 
-__all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'rasterize_gaussians', 'fixed_capacity', 'last_counts']
+__all__ = ['GaussianRasterizationSettings', 'GaussianRasterizer', 'rasterize_gaussians', 'fixed_capacity', 'last_counts', 'last_band_mask', 'check_tile_rows']
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -100,14 +100,35 @@ def last_counts() -> torch.Tensor | None:
     return _LAST_COUNTS
 
 
+_LAST_BAND_MASK: torch.Tensor | None = None
+
+
+def last_band_mask() -> torch.Tensor | None:
+    """DEVICE bool (P,) of the most recent forward with `tile_rows`: the Gaussians whose tile rectangle, clipped to the band, is non-empty -- the only
+    rows that can carry a non-zero gradient from that band (the `visible` mask of parallel.UnionRowExchange for a band-parallel step).  Written by the
+    kernel that makes the rectangles, so it is the binning's own decision.  None after a forward without a band."""
+    return _LAST_BAND_MASK
+
+
+def check_tile_rows(tile_rows, image_height: int) -> tuple[int, int] | None:
+    """(begin, n) of a band of 16-pixel tile rows, validated against the frame's gy = ceil(H / 16) rows; None stays None (the whole frame)."""
+    if tile_rows is None:
+        return None
+    begin, n = (int(v) for v in tile_rows)
+    gy = (int(image_height) + 15) // 16
+    if begin < 0 or n < 1 or begin + n > gy:
+        raise ValueError(f'tile_rows = ({begin}, {n}): a band needs begin >= 0, n >= 1 and begin + n <= {gy} tile rows (image height {image_height})')
+    return begin, n
+
+
 _GRAD_RECORDS: dict = {}   # (device, stream) -> (rows, (rows, 16) f32 accumulator records known to be all zero): ONE buffer per device and stream (see backward)
-_SPAN_CAPACITY: dict = {}  # (device, P, W, H) -> row-span capacity of the binning workspace once the default proved too small
+_SPAN_CAPACITY: dict = {}  # (device, P, W, H, band) -> row-span capacity of the binning workspace once the default proved too small
 # Speculative sizing of the tile lists (round 4).  The forward used to STOP at the instance count: D2H copy, host wait, allocation, and only then
 # the list scatter and the blend -- 33-37 us of idle GPU per frame at 1 M Gaussians (rocprofv3 kernel trace).  Now the lists are sized from the
 # counts of the recent frames of the same (device, P, W, H) (largest of the last 16 x 1.3 + 64 K entries), everything is enqueued at once with the
 # capacity-checked scatter, and the count travels to pinned host memory on a side stream while the blend kernel runs; the host looks at it
 # before returning and repeats the frame with exact sizes in the rare case that it did not fit.  Same lists, same image.
-_INSTANCE_HISTORY: dict = {}   # (device, P, W, H) -> recent instance counts
+_INSTANCE_HISTORY: dict = {}   # (device, P, W, H, band) -> recent instance counts (band = the tile_rows of the call, None for a whole frame)
 _READBACK: dict = {}           # device -> (side stream, pinned int64[2])
 SPECULATIVE_SIZING = True
 # How the count reaches the host (round 4, later).  The side-stream copy needs an event on the caller's stream between the counting kernels and the list
@@ -133,9 +154,13 @@ def _opt(t):
 
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, sh_rest=None, raw=False, rest_step=None):
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, sh_rest=None, raw=False, rest_step=None, tile_rows=None):
         rs = raster_settings
         lib = _lib.load()
+        band = check_tile_rows(tile_rows, rs.image_height)
+        if band is not None and rest_step is not None:
+            raise RuntimeError('rest_step together with tile_rows: the backward pass of a band holds this band\'s SHARE of the gradient only, and an Adam step '
+                               'taken on a partial gradient is not the optimizer\'s step -- sum the shares over the bands first and step then')
         dev = means3D.device
         f32 = torch.float32
         prep = lambda t: None if _opt(t) is None else t.detach().to(f32).contiguous()
@@ -174,14 +199,16 @@ class _RasterizeGaussians(torch.autograd.Function):
                                'wrap the call in diff_gaussian_rasterization.fixed_capacity(instances, spans)')
         # binning workspace: kept per (device, P, W, H) and regrown when a frame needs more row-span records than it holds (the count comes
         # back with the instance count in the one host read of the forward)
-        ws_key = (dev, P, W, H)
+        ws_key = (dev, P, W, H, band)   # a band and a whole frame do not size each other's lists
         span_cap = _SPAN_CAPACITY.get(ws_key, 0) if fixed is None else fixed[1]
         inst_cap = 0 if fixed is None else fixed[0]
         history = _INSTANCE_HISTORY.get(ws_key) if fixed is None else None
         speculative = bool(SPECULATIVE_SIZING and history and P > 0 and gx <= 256 and gy <= 256)   # the span binning path (fixed capacities exist there only)
         if speculative:
             inst_cap = min(int(max(history) * 1.3) + 65536, 0xfffffff0)
-        color = torch.empty(3, H, W, dtype=f32, device=dev)
+        # a band writes its own pixel rows only: the rest of the image is zero, so that the band images of a partition sum (and slice) to the frame
+        color = torch.empty(3, H, W, dtype=f32, device=dev) if band is None else torch.zeros(3, H, W, dtype=f32, device=dev)
+        band_mask = None if band is None else torch.empty(n1, dtype=u8, device=dev)
         n_contrib = torch.empty(H * W, dtype=i32, device=dev)
         final_T = torch.empty(H * W, dtype=f32, device=dev)
         global _LAST_COUNTS
@@ -189,6 +216,14 @@ class _RasterizeGaussians(torch.autograd.Function):
         def preprocess(cap_spans, cap_inst, box=None, ticket=0):
             hist_bytes = int(lib.nrc_gs_bin_hist_bytes(P, W, H, cap_spans))
             hist = torch.empty(hist_bytes // 4, dtype=i32, device=dev) if hist_bytes > 0 else None
+            if band is not None:
+                _lib.check(lib.nrc_gs_preprocess_band(
+                    P, D, M, W, H, _lib.ptr(means3D_c), _lib.ptr(sh_c), _lib.ptr(rest_c), int(raw), _lib.ptr(col_c), _lib.ptr(op_c), _lib.ptr(sc_c), float(rs.scale_modifier),
+                    _lib.ptr(rot_c), _lib.ptr(cov_c), None, None, None, _lib.ptr(cam_block), float(rs.tanfovx), float(rs.tanfovy), _lib.ptr(radii), _lib.ptr(depths),
+                    _lib.ptr(points_xy), _lib.ptr(conic_opacity), _lib.ptr(rgb), _lib.ptr(clamped), _lib.ptr(cov3D), _lib.ptr(tiles_touched),
+                    _lib.ptr(tile_counts), _lib.ptr(ranges), _lib.ptr(tile_fill), _lib.ptr(hist), cap_spans, cap_inst, _lib.ptr(splat), _lib.ptr(num_rendered),
+                    box if hist is not None else None, ticket, band[0], band[1], _lib.ptr(band_mask), st), 'gs_preprocess_band')
+                return hist
             _lib.check(lib.nrc_gs_preprocess(
                 P, D, M, W, H, _lib.ptr(means3D_c), _lib.ptr(sh_c), _lib.ptr(rest_c), int(raw), _lib.ptr(col_c), _lib.ptr(op_c), _lib.ptr(sc_c), float(rs.scale_modifier),
                 _lib.ptr(rot_c), _lib.ptr(cov_c), None, None, None, _lib.ptr(cam_block), float(rs.tanfovx), float(rs.tanfovy), _lib.ptr(radii), _lib.ptr(depths),
@@ -200,6 +235,11 @@ class _RasterizeGaussians(torch.autograd.Function):
         def bin_render(hist, cap_spans, cap_inst, n_list):
             keys_ = torch.empty(max(n_list, 1) if hist is None else 1, dtype=torch.int64, device=dev)  # only the per-tile key sort fallback uses them
             plist = torch.empty(max(n_list, 1), dtype=i32, device=dev)
+            if band is not None:
+                _lib.check(lib.nrc_gs_bin_render_band(P, W, H, None, _lib.ptr(cam_block), _lib.ptr(radii), _lib.ptr(depths), _lib.ptr(points_xy), _lib.ptr(conic_opacity),
+                                                      _lib.ptr(rgb), _lib.ptr(ranges), _lib.ptr(tile_fill), _lib.ptr(hist), cap_spans, cap_inst, _lib.ptr(keys_), _lib.ptr(plist),
+                                                      _lib.ptr(splat), _lib.ptr(color), _lib.ptr(n_contrib), _lib.ptr(final_T), band[0], band[1], st), 'gs_bin_render_band')
+                return keys_, plist
             _lib.check(lib.nrc_gs_bin_render(P, W, H, None, _lib.ptr(cam_block), _lib.ptr(radii), _lib.ptr(depths), _lib.ptr(points_xy), _lib.ptr(conic_opacity),
                                              _lib.ptr(rgb), _lib.ptr(ranges), _lib.ptr(tile_fill), _lib.ptr(hist), cap_spans, cap_inst, _lib.ptr(keys_), _lib.ptr(plist),
                                              _lib.ptr(splat), _lib.ptr(color), _lib.ptr(n_contrib), _lib.ptr(final_T), st), 'gs_bin_render')
@@ -272,6 +312,10 @@ class _RasterizeGaussians(torch.autograd.Function):
             if len(_INSTANCE_HISTORY) > 64:
                 _INSTANCE_HISTORY.pop(next(iter(_INSTANCE_HISTORY)))
         _LAST_COUNTS = num_rendered
+        global _LAST_BAND_MASK
+        # (the per-tile key sort fallback, which takes the band (0, gy) only, does not write the mask: every visible Gaussian is in that band)
+        _LAST_BAND_MASK = None if band is None else ((band_mask[:P] != 0) if bin_hist is not None and P > 0 else (radii[:P] > 0))
+        ctx.band = band
         ctx.raster_settings = rs
         ctx.dims = (P, D, M, W, H)
         ctx.num_rendered = n_inst if fixed is None else -1
@@ -285,7 +329,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.rest_step = rest_step
         if rest_step is not None and (rest_c is None or rest_c.data_ptr() != sh_rest.data_ptr() or sc_c is None or col_c is not None or cov_c is not None):
             raise RuntimeError('rest_step: needs shs_rest as a contiguous f32 CUDA tensor (updated in place), scales / rotations, no colors_precomp / cov3D_precomp')
-        ctx.debug_state = dict(depths=depths, tiles_touched=tiles_touched, keys=keys)
+        ctx.debug_state = dict(depths=depths, tiles_touched=tiles_touched, keys=keys, point_list=point_list, ranges=ranges, n_contrib=n_contrib, final_T=final_T,
+                               num_rendered=num_rendered)
         radii_out = radii[:P]
         ctx.mark_non_differentiable(radii_out)
         # radii carry no gradient: without this autograd hands the backward a zero-filled (P,) int tensor for them -- a 4 MB fill launch per step
@@ -343,6 +388,17 @@ class _RasterizeGaussians(torch.autograd.Function):
                 _lib.ptr(grad_records), int(records_clear), _lib.ptr(m_rest), _lib.ptr(v_rest), float(lr), float(beta1), float(beta2), float(eps), float(bc1), float(bc2),
                 _lib.stream_of(g)), 'gs_backward_rest_step')
             torch.autograd.graph.increment_version(param)      # written through a raw pointer
+        elif ctx.band is not None:
+            # this band's share of every gradient: the blend backward over the band's tiles, the per-Gaussian backward over all P
+            _lib.check(lib.nrc_gs_backward_band(
+                P, D, M, W, H, None, _lib.ptr(means3D), _lib.ptr(sh if has_sh else None), _lib.ptr(sh_rest if has_rest else None), int(raw),
+                _lib.ptr(opac if raw else None), _lib.ptr(col if has_col else None),
+                _lib.ptr(sc if has_sr else None), float(rs.scale_modifier), _lib.ptr(rot if has_sr else None), _lib.ptr(cov if has_cov else None),
+                None, None, None, _lib.ptr(cam_block), float(rs.tanfovx), float(rs.tanfovy), _lib.ptr(radii), _lib.ptr(points_xy), _lib.ptr(conic_opacity),
+                _lib.ptr(rgb), _lib.ptr(clamped), _lib.ptr(cov3D), _lib.ptr(point_list), _lib.ptr(ranges), _lib.ptr(splat), _lib.ptr(tile_order), _lib.ptr(n_contrib), _lib.ptr(final_T),
+                _lib.ptr(g), _lib.ptr(dmean2D), None, _lib.ptr(dopacity), _lib.ptr(dcolor), _lib.ptr(dmean3D), _lib.ptr(dcov3D),
+                _lib.ptr(dsh), _lib.ptr(dsh_rest), _lib.ptr(dscale), _lib.ptr(drot), _lib.ptr(grad_records), int(records_clear), ctx.band[0], ctx.band[1],
+                _lib.stream_of(g)), 'gs_backward_band')
         else:
             _lib.check(lib.nrc_gs_backward(
                 P, D, M, W, H, None, _lib.ptr(means3D), _lib.ptr(sh if has_sh else None), _lib.ptr(sh_rest if has_rest else None), int(raw),
@@ -357,11 +413,15 @@ class _RasterizeGaussians(torch.autograd.Function):
         cut = (lambda t: t) if P == n1 else (lambda t: t[:P])     # (whole buffers when nothing is cut: a gradient that is not a view can be adopted as .grad without a copy)
         return (cut(dmean3D), cut(dmean2D), cut(dsh) if has_sh else None, cut(dcolor) if has_col else None,
                 cut(dopacity).reshape(ctx.opacity_shape), cut(dscale) if has_sr else None, cut(drot) if has_sr else None,
-                cut(dcov3D) if has_cov else None, None, cut(dsh_rest) if dsh_rest is not None else None, None, None)
+                cut(dcov3D) if has_cov else None, None, cut(dsh_rest) if dsh_rest is not None else None, None, None, None)
 
 
-def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, sh_rest=None, raw=False, rest_step=None):
-    return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, sh_rest, raw, rest_step)
+def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, sh_rest=None, raw=False, rest_step=None, tile_rows=None):
+    """`tile_rows` = (begin, n): render and differentiate the band of 16-pixel tile rows [begin, begin + n) only (see GaussianRasterizer.forward); None: the frame."""
+    if tile_rows is None:
+        return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, sh_rest, raw, rest_step)
+    return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, sh_rest, raw, rest_step,
+                                     tuple(int(v) for v in tile_rows))
 
 
 class GaussianRasterizer(torch.nn.Module):
@@ -377,13 +437,18 @@ class GaussianRasterizer(torch.nn.Module):
             return z > 0.2
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, shs_rest=None,
-                raw_parameters=False, rest_step=None):
+                raw_parameters=False, rest_step=None, tile_rows=None):
         """The reference's call (Renderer.py:75-81) plus two keyword extensions for callers that own the model tensors: `shs_rest` -- `shs` is then
         (`rest_step`, round 6: an object whose take() returns (parameter, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, bc1, bc2) -- the backward pass then applies
         the optimizer's Adam step to shs_rest itself and returns no gradient for it: nerficg_amd.gaussian_splatting.RestStep)
         the DC part (P,1,3) and shs_rest the (P,M-1,3) remainder, the concatenation of Gaussians.get_features is never built; `raw_parameters` --
         opacities are logits, scales log-scales, rotations unnormalised: the activations of Model.py:45-87 run inside the preprocess kernel and the
-        gradients come back w.r.t. the raw tensors."""
+        gradients come back w.r.t. the raw tensors.
+        `tile_rows` = (begin, n): ONE BAND of the frame, the 16-pixel tile rows [begin, begin + n) of its ceil(H / 16) rows -- the unit a single view is sharded
+        by across GPUs (nerficg_amd.parallel.tile_row_band).  The image is still (3, H, W), its band rows bit for bit those of the whole-frame call and zero
+        elsewhere (the band images of a partition sum and slice to the frame); `radii` is the full (P,) tensor, identical for every band; the backward pass
+        returns this band's SHARE of every gradient, `means2D` included (the shares of a partition sum to the whole-frame gradient, rows of Gaussians that miss
+        the band are exactly zero: last_band_mask()).  Not together with `rest_step`.  None (default): the whole frame, today's call."""
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
         if ((scales is None or rotations is None) and cov3D_precomp is None) or ((scales is not None or rotations is not None) and cov3D_precomp is not None):
@@ -391,4 +456,4 @@ class GaussianRasterizer(torch.nn.Module):
         empty = torch.Tensor([])
         return rasterize_gaussians(means3D, means2D, empty if shs is None else shs, empty if colors_precomp is None else colors_precomp, opacities,
                                    empty if scales is None else scales, empty if rotations is None else rotations,
-                                   empty if cov3D_precomp is None else cov3D_precomp, self.raster_settings, shs_rest, raw_parameters, rest_step)
+                                   empty if cov3D_precomp is None else cov3D_precomp, self.raster_settings, shs_rest, raw_parameters, rest_step, tile_rows)

@@ -13,7 +13,7 @@ import torch
 
 __all__ = ['PerspectiveCamera', 'get_projection_matrix', 'invert_3d_affine', 'make_raster_settings', 'quaternion_to_rotation_matrix',
            'build_covariances', 'extract_upper_triangular_matrix', 'sh_basis', 'convert_sh_features', 'rgb_to_sh0', 'sh0_to_rgb', 'Gaussians',
-           'render_image_training', 'render_image_inference', 'training_loss', 'rest_step_schedule', 'RestStep']
+           'render_image_training', 'render_image_inference', 'training_loss', 'rest_step_schedule', 'RestStep', 'band_parallel_training_step']
 
 
 @dataclass
@@ -433,25 +433,69 @@ class RestStep:
         return p, state['exp_avg'], state['exp_avg_sq'], float(g['lr']), float(beta1), float(beta2), float(g['eps']), bc[0], bc[1]
 
 
-def render_image_training(gaussians: Gaussians, cam: PerspectiveCamera, c2w: np.ndarray, fuse_rest_step: bool | None = None) -> dict[str, torch.Tensor]:
-    """GaussianSplatting/Renderer.py:51-86.  fuse_rest_step (default: gaussians.fuse_rest_step, False unless set): the backward pass of this frame applies the
+def render_image_training(gaussians: Gaussians, cam: PerspectiveCamera, c2w: np.ndarray, fuse_rest_step: bool | None = None,
+                          band: tuple[int, int] | None = None) -> dict[str, torch.Tensor]:
+    """GaussianSplatting/Renderer.py:51-86.  band = (tile_row_begin, n_tile_rows): this call renders and differentiates that band of 16-pixel tile rows of
+    the frame only (the rasterizer's `tile_rows`; parallel.tile_row_band): 'rgb' is zero outside the band, the gradients are the band's share, and the
+    outputs gain 'band_mask' (the Gaussians that can receive a gradient from the band).  A band holds a partial gradient, so the in-backward optimizer
+    step of `f_rest` is refused with it (RuntimeError), whether asked for here or through gaussians.fuse_rest_step.  fuse_rest_step (default: gaussians.fuse_rest_step, False unless set): the backward pass of this frame applies the
     optimizer's step to the `f_rest` SH tensor itself -- for loops that run exactly one backward pass and one optimizer.step() per frame on one GPU (the
     view-parallel exchange needs the gradient on the wire, gradient accumulation needs it in .grad: both leave this off)."""
-    from .diff_gaussian_rasterization import GaussianRasterizer
+    from .diff_gaussian_rasterization import GaussianRasterizer, check_tile_rows, last_band_mask
     positions = gaussians.get_positions
+    band = check_tile_rows(band, cam.height)
+    fuse = getattr(gaussians, 'fuse_rest_step', False) if fuse_rest_step is None else bool(fuse_rest_step)
+    if band is not None and fuse:
+        raise RuntimeError('render_image_training: band= together with the fused f_rest step -- the backward pass of a band holds that band\'s share of the '
+                           'gradient only, and Adam applied to a partial gradient is not the optimizer\'s step; sum the shares over the bands and step then')
     # the carrier of the screen-space gradient (Renderer.py:56-58: zeros_like + 0, retain_grad): the rasterizer never reads its VALUES, only hands it a
     # gradient -- a leaf of uninitialised memory receives the same .grad without a 12 MB fill and a 24 MB add per step
     viewspace_points = torch.empty_like(positions).requires_grad_(True)
     rasterizer = GaussianRasterizer(make_raster_settings(cam, c2w, gaussians.active_sh_degree, 1.0, positions.device))
     if gaussians.baked:  # a baked model holds activated values
         image, radii = rasterizer(means3D=positions, means2D=viewspace_points, shs=gaussians.get_features_dc, shs_rest=gaussians.get_features_rest,
-                                  opacities=gaussians.get_opacities, scales=gaussians.get_scales, rotations=gaussians.get_rotations)
+                                  opacities=gaussians.get_opacities, scales=gaussians.get_scales, rotations=gaussians.get_rotations, tile_rows=band)
     else:  # raw parameters straight into the kernels: no get_features concatenation, no separate exp / sigmoid / normalize passes (a25)
-        fuse = getattr(gaussians, 'fuse_rest_step', False) if fuse_rest_step is None else bool(fuse_rest_step)
         rest_step = RestStep(gaussians) if fuse and not getattr(gaussians.optimizer, 'capturable', False) and not torch.cuda.is_current_stream_capturing() and torch.is_grad_enabled() and gaussians._features_rest.requires_grad and gaussians._features_rest.shape[1] > 0 and torch.is_tensor(c2w) else None
         image, radii = rasterizer(means3D=positions, means2D=viewspace_points, shs=gaussians._features_dc, shs_rest=gaussians._features_rest,
-                                  opacities=gaussians._opacities, scales=gaussians._scales, rotations=gaussians._rotations, raw_parameters=True, rest_step=rest_step)
-    return _TrainingOutputs({'rgb': image, 'viewspace_points': viewspace_points, 'radii': radii})
+                                  opacities=gaussians._opacities, scales=gaussians._scales, rotations=gaussians._rotations, raw_parameters=True, rest_step=rest_step, tile_rows=band)
+    outputs = _TrainingOutputs({'rgb': image, 'viewspace_points': viewspace_points, 'radii': radii})
+    if band is not None:
+        outputs['band_mask'] = last_band_mask()
+    return outputs
+
+
+def band_parallel_training_step(gaussians: Gaussians, cam: PerspectiveCamera, c2w, loss_fn, exchange=None, rank: int | None = None,
+                                world: int | None = None) -> dict[str, torch.Tensor]:
+    """The training render of ONE view split over the ranks as bands of tile rows, forward and backward, with the reference's one-view semantics:
+
+        1. this rank renders its own band (parallel.tile_row_band of the frame's ceil(H / 16) tile rows);
+        2. the band images are gathered: every rank holds the whole frame, bit for bit the single-GPU image (parallel.gather_band_images);
+        3. `loss_fn(image)` -- the caller's usual loss on the WHOLE (3, H, W) frame, the same value on every rank (SSIM windows need no halo logic);
+        4. backward: each rank receives its own rows of the image gradient and computes its band's share of every parameter gradient;
+        5. the shares are SUMMED (not averaged) over the ranks -- the six model tensors and the screen-space gradient of 'viewspace_points' that
+           densification reads -- through parallel.UnionRowExchange with the band mask as `visible`: only rows that some band touches travel.
+
+    Afterwards every rank holds the single-GPU gradient and takes the single-GPU optimizer step: preprocess, depth sort, per-Gaussian backward and
+    Adam are replicated, binning and the two blend kernels shrink with the band.  Returns the outputs of render_image_training with 'rgb' = the whole
+    frame (detached), plus 'loss' and 'band'.  `exchange`: a parallel.UnionRowExchange(P, device) to reuse across steps of the same P.
+    The in-backward f_rest step (gaussians.fuse_rest_step) is refused: it would run on a partial gradient."""
+    from . import parallel
+    r, w = parallel.world_info()
+    rank, world = (r if rank is None else int(rank)), (w if world is None else int(world))
+    band = parallel.tile_row_band((cam.height + 15) // 16, rank, world)
+    out = render_image_training(gaussians, cam, c2w, band=band)
+    mask = out['band_mask']
+    ex = exchange if exchange is not None else parallel.UnionRowExchange(mask.shape[0], mask.device)
+    ex.begin(mask)          # the mask traffic runs beside the gather, the loss and the backward pass
+    image = parallel.gather_band_images(out['rgb'], rank, world)
+    loss = loss_fn(image)
+    loss.backward()
+    carriers = [gaussians._positions, gaussians._features_dc, gaussians._features_rest, gaussians._opacities, gaussians._scales, gaussians._rotations,
+                out['viewspace_points']]
+    ex.finish([p for p in carriers if p.requires_grad], average=False)
+    out['rgb'], out['loss'], out['band'] = image.detach(), loss.detach(), band
+    return out
 
 
 class _TrainingOutputs(dict):
@@ -470,8 +514,9 @@ class _TrainingOutputs(dict):
 
 @torch.no_grad()
 def render_image_inference(gaussians: Gaussians, cam: PerspectiveCamera, c2w: np.ndarray, scale_modifier: float = 1.0, to_chw: bool = False,
-                           use_baked_covariance: bool = True):
-    """GaussianSplatting/Renderer.py:89-155 with the fused SH path (USE_FUSED_SH_CONVERSION = True, the shipped default); a baked model
+                           use_baked_covariance: bool = True, band: tuple[int, int] | None = None):
+    """band = (tile_row_begin, n_tile_rows): only that band of tile rows of the frame is rendered (zero elsewhere; parallel.gather_band_images composes the
+    frame from the ranks' bands).  GaussianSplatting/Renderer.py:89-155 with the fused SH path (USE_FUSED_SH_CONVERSION = True, the shipped default); a baked model
     (trained checkpoint, Model.py:248-273) is rasterized from its baked covariances like the reference's USE_BAKED_COVARIANCE branch
     (Renderer.py:129-139), everything else through the in-kernel covariance computation."""
     from .diff_gaussian_rasterization import GaussianRasterizer
@@ -482,10 +527,10 @@ def render_image_inference(gaussians: Gaussians, cam: PerspectiveCamera, c2w: np
         covariances = None  # "Baked covariance requested but not available"
     if covariances is not None:
         image, _ = rasterizer(means3D=positions, means2D=torch.empty_like(positions), shs=gaussians.get_features, opacities=gaussians.get_opacities,
-                              cov3D_precomp=covariances)
+                              cov3D_precomp=covariances, tile_rows=band)
     else:
         image, _ = rasterizer(means3D=positions, means2D=torch.empty_like(positions), shs=gaussians.get_features,
-                              opacities=gaussians.get_opacities, scales=gaussians.get_scales, rotations=gaussians.get_rotations)
+                              opacities=gaussians.get_opacities, scales=gaussians.get_scales, rotations=gaussians.get_rotations, tile_rows=band)
     image.clamp_(0.0, 1.0)
     return {'rgb': image if to_chw else image.permute(1, 2, 0)}
 

@@ -10,6 +10,10 @@ The reference has no working multi-GPU path: its DataParallel 
                             non-zero only on ranks that saw it, so the reduction moves only the rows visible on at least one rank
                             (sparse_allreduce_gradients); densification statistics are summed when densification is due and
                             densify_and_prune runs redundantly on every rank from identically seeded noise.
+  * one 3DGS view        -- band-parallel: every rank rasterizes ANOTHER band of 16-pixel tile rows of the SAME view (tile_row_band; the rasterizer's
+                            `tile_rows`), the band images are all-gathered into the frame (gather_band_images: autograd hands each rank its own rows of the
+                            image gradient), every rank computes the loss on the whole frame, and the per-band gradient SHARES are summed over the
+                            ranks with the band mask as the visibility mask (UnionRowExchange, average=False): the single-GPU gradient, the single-GPU step.
   * training rays        -- rank r takes ray_ids[r::world] of the batch every rank draws from the same seeded permutation
                             (src/Optim/Samplers/utils.py:8-34), so the global ray set is bit-identical to the single-GPU run;
                             after backward the encoding / MLP (InstantNGP) or Gaussian (3DGS) gradients are summed with ONE
@@ -33,7 +37,7 @@ from .amp import GradScaler as _FastGradScaler
 __all__ = ['init_distributed', 'world_info', 'shard_ray_ids', 'shard_range', 'allreduce_flat', 'allreduce_gradients',
            'all_gather_pixels', 'tile_pixel_indices', 'gather_image_shards', 'broadcast_parameters', 'sparse_allreduce_gradients', 'allreduce_densification_stats', 'synchronized_noise',
            'allreduce_scalars', 'DataParallelGradScaler', 'rays_per_batch_update', 'single_rank_collectives', 'ShardedStepLayout', 'allreduce_sum_',
-           'reduce_scatter_sum_', 'all_gather_', 'sharded_step', 'UnionRowExchange']
+           'reduce_scatter_sum_', 'all_gather_', 'sharded_step', 'UnionRowExchange', 'tile_row_band', 'band_pixel_rows', 'gather_band_images']
 
 
 _SINGLE_RANK_COLLECTIVES = False
@@ -103,6 +107,60 @@ def shard_range(n: int, rank: int | None = None, world: int | None = None) -> tu
     base, rem = divmod(n, world)
     begin = rank * base + min(rank, rem)
     return begin, begin + base + (1 if rank < rem else 0)
+
+
+def tile_row_band(gy: int, rank: int | None = None, world: int | None = None) -> tuple[int, int]:
+    """(tile_row_begin, n_tile_rows) of this rank's band when ONE frame of gy = ceil(H / 16) tile rows is split over the ranks: shard_range over the
+    rows, so the bands are contiguous, ordered by rank, differ by at most one row and partition [0, gy).  A frame with fewer tile rows than ranks is
+    refused (ValueError): a band has at least one row, and a rank without one would still have to enter every collective of the step -- use fewer
+    ranks for such a frame (gy >= 53 for the frames this project renders)."""
+    r, w = world_info()
+    rank = r if rank is None else int(rank)
+    world = w if world is None else int(world)
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError(f'tile_row_band: rank {rank} of {world}')
+    if gy < world:
+        raise ValueError(f'tile_row_band: {gy} tile rows cannot be split into {world} non-empty bands (one band per rank): use at most {max(gy, 0)} ranks for this frame')
+    begin, end = shard_range(gy, rank, world)
+    return begin, end - begin
+
+
+def band_pixel_rows(height: int, band: tuple[int, int], tile: int = 16) -> tuple[int, int]:
+    """[first, last) pixel rows of a band of tile rows; the last band of a frame ends at the image height."""
+    return min(height, tile * band[0]), min(height, tile * (band[0] + band[1]))
+
+
+class _GatherBands(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, image, rank, world):
+        H = image.shape[-2]
+        rows = [band_pixel_rows(H, tile_row_band((H + 15) // 16, r, world)) for r in range(world)]
+        ctx.rows = rows[rank]
+        y0, y1 = rows[rank]
+        # row-major blocks of whole pixel rows: (rows, C, W), so that the ranks' blocks concatenate along dim 0
+        local = image[..., y0:y1, :].movedim(-2, 0).contiguous()
+        staged = _staged(local)
+        full = all_gather_pixels(local.cpu() if staged else local, [b - a for a, b in rows])
+        return full.to(image.device).movedim(0, -2).contiguous()
+
+    @staticmethod
+    def backward(ctx, grad_full):
+        y0, y1 = ctx.rows
+        grad = torch.zeros_like(grad_full)
+        grad[..., y0:y1, :] = grad_full[..., y0:y1, :]
+        return grad, None, None
+
+
+def gather_band_images(image: torch.Tensor, rank: int | None = None, world: int | None = None) -> torch.Tensor:
+    """One frame rendered as tile-row bands (tile_row_band over the ranks; `image` = this rank's (C, H, W) band image, whatever it holds outside its own
+    pixel rows): all-gathers the bands' pixel rows, so that every rank returns the whole (C, H, W) frame, bit for bit the rows each rank rendered.
+    Autograd passes through: the backward pass hands each rank ITS OWN rows of the image gradient (zeros elsewhere) -- every rank computes the same
+    loss on the same whole frame, and a pixel's gradient belongs to the rank that rendered it.  world = 1: the image itself."""
+    r, w = world_info()
+    rank, world = (r if rank is None else int(rank)), (w if world is None else int(world))
+    if _no_collective(world):
+        return image
+    return _GatherBands.apply(image, rank, world)
 
 
 def _has_tensor_collectives() -> bool:

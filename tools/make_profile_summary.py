@@ -10,6 +10,10 @@ RAW = ROOT / 'gpurun_out' / 'profiles_raw'
 OUT = ROOT / 'profiles'
 OUT.mkdir(exist_ok=True)
 ROUND = sys.argv[1] if len(sys.argv) > 1 else 'r03'   # file prefix of the committed summaries
+# Partial collection (tools/collect_profiles.sh gs): the source files named behind the round are the only ones that changed since profiles/pmc_summary.json was
+# written.  Counters of kernels that were not collected again are carried over from that file -- refused unless every OTHER source file still has the digest
+# recorded there, and never for a kernel that one of the named files defines (such an entry would be stale: it is dropped).
+PARTIAL = sys.argv[2:]
 
 
 def short(name):
@@ -113,6 +117,17 @@ for k in sorted(acc):
     summary[key] = {**{n: round(v, 1) for n, v in c.items()}, **derived}
 (OUT / f'{ROUND}_pmc_summary.md').write_text('\n'.join(lines))
 import hashlib
+if PARTIAL:
+    old = json.loads((OUT / 'pmc_summary.json').read_text())
+    now = {p.name: hashlib.sha256(p.read_bytes()).hexdigest()[:16] for p in sorted((ROOT / 'nerficg_amd' / 'csrc').glob('*.h*'))}
+    moved = sorted(k for k in now if k not in PARTIAL and old['_meta']['csrc_sha'].get(k) != now[k])
+    if moved:
+        sys.exit(f'partial summary refused: {moved} changed as well since profiles/pmc_summary.json was collected -- run the whole collection')
+    changed_text = ' '.join((ROOT / 'nerficg_amd' / 'csrc' / name).read_text() for name in PARTIAL)
+    carried = [k for k in old if not k.startswith('_') and k not in summary and not re.search(r'\b' + re.escape(re.split(r'[<(]', k)[0]) + r'\b', changed_text)]
+    for k in carried:
+        summary[k] = old[k]
+    print(f'partial summary ({PARTIAL}): {len(summary) - len(carried)} kernels collected again, {len(carried)} carried over from round {old["_meta"].get("round")}')
 # provenance: bench.py quotes a counter entry only while the kernel's source file is the one these counters were collected on
 summary['_meta'] = {'round': ROUND, 'csrc_sha': {p.name: hashlib.sha256(p.read_bytes()).hexdigest()[:16] for p in sorted((ROOT / 'nerficg_amd' / 'csrc').glob('*.h*'))}}
 (OUT / 'pmc_summary.json').write_text(json.dumps(summary, indent=1, sort_keys=True))
