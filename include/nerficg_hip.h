@@ -34,8 +34,9 @@ enum {
  * nrc_ngp_query_samples gained arena_tile_off / arena_rows, nrc_ngp_composite_image arena_rows, nrc_ngp_render_write accepts ts = NULL;
  * nrc_photometric_loss_* are new; 5 = round 5: group 13 (the fused InstantNGP training iteration) is new; nrc_ngp_train_query_forward gained
  * n_samples_dev (NULL = every row, as before); 7 = the band entry points of group 4 (nrc_gs_*_band: one frame rendered and differentiated as bands of tile
- * rows) are new, every earlier signature is unchanged. */
-#define NRC_ABI_VERSION 7
+ * rows) are new, every earlier signature is unchanged; 8 = nrc_gs_bin_render_aux_band / nrc_gs_backward_aux_band (group 4: differentiable depth and alpha maps
+ * beside the colour) are new, float [3].w of a splat record carries the view-space depth, slot [9] of a gradient record dL/dz; every earlier signature is unchanged. */
+#define NRC_ABI_VERSION 8
 /* library identification; also used by the loader's symbol check */
 int nrc_abi_version(void);
 const char* nrc_build_info(void);
@@ -418,6 +419,32 @@ int nrc_gs_backward_band(int32_t P, int32_t D, int32_t M, int32_t W, int32_t H, 
                     float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
                     float* dL_dcov3D, float* dL_dsh, float* dL_dsh_rest, float* dL_dscale, float* dL_drot, float* grad_records,
                     int32_t records_clear, int32_t tile_row_begin, int32_t n_tile_rows, nrc_stream_t stream);
+/* Depth and alpha maps (ABI 8): two further blended channels with background 0, accumulated with the colour's own weights w_i = alpha_i T_i --
+ *   depth = sum_i w_i z_i  (z_i = the view-space depth of `depths`, the value the sort orders by; NOT normalised by alpha),   alpha = sum_i w_i = 1 - final_T.
+ * Both are differentiable: the alpha channel behaves like a colour that is 1 for every Gaussian, the depth channel like a colour z_i whose own gradient
+ * dL/dz_i = sum_pixels w_i g_d (slot [9] of the 64-byte gradient record) reaches dL_dmean3D through the third column of the view matrix.
+ *   nrc_gs_bin_render_aux_band : nrc_gs_bin_render_band + out_depth_alpha (2, H, W) f32, FULL-FRAME like out_color: plane 0 = depth, plane 1 = alpha; only the band's
+ *                       pixel rows are written.  out_color, n_contrib and final_T are those of nrc_gs_bin_render_band bit for bit.  NULL: the colour-only kernel,
+ *                       i.e. nrc_gs_bin_render_band itself.  z travels in float [3].w of the splat record (written by nrc_gs_preprocess since ABI 8).
+ *   nrc_gs_backward_aux_band : nrc_gs_backward_band + dL_ddepth_alpha (2, H, W) f32, full-frame, only the band's rows are read: every gradient tensor is the gradient
+ *                       (the band's share) of  <dL_dpix, colour> + <dL_ddepth_alpha[0], depth> + <dL_ddepth_alpha[1], alpha>.  NULL: nrc_gs_backward_band itself.
+ *                       The records are left cleared as by every backward (records_clear covers slot [9]: whole records are cleared).
+ * Whole frames: the band (0, ceil(H / 16)); the per-tile key sort fallback supports both on whole frames.  There is no aux form of nrc_gs_backward_rest_step. */
+int nrc_gs_bin_render_aux_band(int32_t P, int32_t W, int32_t H, const float* bg, const float* camera_dev, const int32_t* radii,
+                      const float* depths, const float* points_xy, const float* conic_opacity, const float* rgb,
+                      const uint32_t* ranges, uint32_t* tile_fill, const uint32_t* bin_hist, int64_t span_capacity,
+                      int64_t instance_capacity, uint64_t* keys, int32_t* point_list, const float* splat_records, float* out_color,
+                      uint32_t* n_contrib, float* final_T, int32_t tile_row_begin, int32_t n_tile_rows, float* out_depth_alpha, nrc_stream_t stream);
+int nrc_gs_backward_aux_band(int32_t P, int32_t D, int32_t M, int32_t W, int32_t H, const float* bg, const float* means3D, const float* shs,
+                    const float* shs_rest, int32_t raw_parameters, const float* opacities, const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
+                    const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix, const float* campos,
+                    const float* camera_dev, float tan_fovx, float tan_fovy, const int32_t* radii, const float* points_xy, const float* conic_opacity,
+                    const float* rgb, const uint8_t* clamped, const float* cov3D, const int32_t* point_list,
+                    const uint32_t* ranges, const float* splat_records, const uint32_t* tile_order, const uint32_t* n_contrib,
+                    const float* final_T, const float* dL_dpix,
+                    float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
+                    float* dL_dcov3D, float* dL_dsh, float* dL_dsh_rest, float* dL_dscale, float* dL_drot, float* grad_records,
+                    int32_t records_clear, int32_t tile_row_begin, int32_t n_tile_rows, const float* dL_ddepth_alpha, nrc_stream_t stream);
 
 /* =====================================================================================================
  * Group 5 -- ray generation (replaces PerspectiveCamera.compute_local_ray_directions src/Cameras/Perspective.py:64-94

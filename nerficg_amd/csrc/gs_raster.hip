@@ -173,12 +173,13 @@ __device__ __forceinline__ void tile_rect(const float* p, int radius, int gx, in
 // ------------------------------------------------------------------------------------------------ 1. preprocess
 // Splat record: what the two render kernels need of a Gaussian, in ONE 64-byte line (they used to gather xy, conic + opacity and rgb from
 // three arrays = three cache lines per list entry), plus the per-Gaussian part of their block tests precomputed once instead of once per
-// (tile, Gaussian) pair:  q0 = {X, Y, A, B}  q1 = {C, o, ext_x, ext_y}  q2 = {tau / A, det / A^2, B / A, y_off}  q3 = {r, g, b, -}
-// (round 4: the colour has the last vector to itself -- the one part of the record that the SH evaluation produces)
+// (tile, Gaussian) pair:  q0 = {X, Y, A, B}  q1 = {C, o, ext_x, ext_y}  q2 = {tau / A, det / A^2, B / A, y_off}  q3 = {r, g, b, z}
+// (round 4: the colour has the last vector to itself -- the one part of the record that the SH evaluation produces; z = the view-space depth the sort
+// orders by, read by the depth-and-alpha instances of the blend kernels only)
 //   alpha >= 1/255  <=>  A dx^2 + 2 B dx dy + C dy^2 <= tau = 2 ln(255 o)   (the ellipse a pixel must be inside to blend the Gaussian)
 //   ext_x, ext_y = half extents of that ellipse's bounding box (margins: x 1.001 + 0.01 px);  ext_x = -1: never blends;  +inf: not an ellipse
 //   y_off = (B / C) sqrt(tau C / det): the ellipse's leftmost / rightmost points lie at Y +- y_off
-__device__ __forceinline__ void write_splat_record(float4 (&rec)[4], float X, float Y, float A, float B, float C, float o, const float* col) {
+__device__ __forceinline__ void write_splat_record(float4 (&rec)[4], float X, float Y, float A, float B, float C, float o, const float* col, float z) {
     const float inf = __builtin_inff();
     float ex = -1.f, ey = -1.f, ta = 0.f, da = 0.f, det = 0.f, ba = 0.f, yoff = 0.f;
     if (o > 0.f) {
@@ -193,7 +194,7 @@ __device__ __forceinline__ void write_splat_record(float4 (&rec)[4], float X, fl
         }
     }
     rec[0] = make_float4(X, Y, A, B); rec[1] = make_float4(C, o, ex, ey);
-    rec[2] = make_float4(ta, da, ba, yoff); rec[3] = make_float4(col[0], col[1], col[2], 0.f);
+    rec[2] = make_float4(ta, da, ba, yoff); rec[3] = make_float4(col[0], col[1], col[2], z);
 }
 // one Gaussian; sh_row = its SH coefficients (LDS copy, see k_preprocess)
 __device__ __forceinline__ void preprocess_one(int i, const GsCam& cam, const float* __restrict__ means3D, const float* sh_row,
@@ -261,7 +262,7 @@ __device__ __forceinline__ void preprocess_one(int i, const GsCam& cam, const fl
 #pragma unroll
     for (int k = 0; k < 3; k++) rgb[3 * i + k] = col[k];
     const float opacity = cam.raw ? act_sigmoid(opacities[i]) : opacities[i];
-    if (want_record) write_splat_record(splat, pix[0], pix[1], conic[0], conic[1], conic[2], opacity, col);  // this thread's row of the LDS image
+    if (want_record) write_splat_record(splat, pix[0], pix[1], conic[0], conic[1], conic[2], opacity, col, pv[2]);  // this thread's row of the LDS image
     depths[i] = pv[2]; radii[i] = my_radius;
     points_xy[2 * i] = pix[0]; points_xy[2 * i + 1] = pix[1];
     conic_opacity[4 * i] = conic[0]; conic_opacity[4 * i + 1] = conic[1]; conic_opacity[4 * i + 2] = conic[2];
@@ -1294,11 +1295,11 @@ template <typename LT>
 struct StageLdsT {
     float4 a[BATCH];      // X, Y, r, g
     float4 b[BATCH];      // A, C, B, o  (conic xx, yy, xy, opacity: the pair (A, C) is what blend_power multiplies with (dx, dy))
-    float4 c[BATCH];      // b, -, -, -
+    float4 c[BATCH];      // b, z, -, -  (z: staged by the depth-and-alpha instances only)
     uint16_t flags[BATCH];
     __attribute__((aligned(16))) LT list[N_BLOCKS][BATCH];
 };
-template <typename LT>
+template <bool AUX, typename LT>
 __device__ __forceinline__ unsigned stage_entry(StageLdsT<LT>& st, const float4* __restrict__ splat, int id, float tx0, float ty0) {
     const float4* rec = splat + 4 * (size_t)id;
     const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2], q3 = rec[3];
@@ -1306,7 +1307,8 @@ __device__ __forceinline__ unsigned stage_entry(StageLdsT<LT>& st, const float4*
     if (flags) {
         st.a[threadIdx.x] = make_float4(q0.x, q0.y, q3.x, q3.y);
         st.b[threadIdx.x] = make_float4(q0.z, q1.x, q0.w, q1.y);
-        st.c[threadIdx.x].x = q3.z;
+        if constexpr (AUX) *reinterpret_cast<float2*>(&st.c[threadIdx.x]) = make_float2(q3.z, q3.w);
+        else st.c[threadIdx.x].x = q3.z;
     }
     return flags;
 }
@@ -1347,10 +1349,14 @@ __device__ __forceinline__ int block_lists(StageLdsT<LT>& st, unsigned flags, in
     return mine;
 }
 
+// AUX: the instance that also blends the depth channel -- the view-space depth z of the splat record as a fourth "colour" with background 0, the same
+// weight alpha T, one multiply-add per entry -- and writes out_depth_alpha (2, H, W): plane 0 = sum w z, plane 1 = sum w = 1 - T.  The colour arithmetic,
+// n_contrib and final_T are those of the default instance, bit for bit; the default instance is the kernel it was before AUX existed.
+template <bool AUX>
 __global__ void __launch_bounds__(256) k_render(GsCam cam, const uint32_t* __restrict__ ranges, const int32_t* __restrict__ point_list,
                                                 const float4* __restrict__ splat, const uint32_t* __restrict__ tile_order, float bg0, float bg1, float bg2,
                                                 const float* __restrict__ pose, float* __restrict__ out_color, uint32_t* __restrict__ n_contrib,
-                                                float* __restrict__ final_T) {
+                                                float* __restrict__ final_T, float* __restrict__ out_depth_alpha) {
     __shared__ StageLdsT<uint16_t> st;
     if (pose) { bg0 = pose[35]; bg1 = pose[36]; bg2 = pose[37]; }
     const int tile = (int)tile_order[blockIdx.x];  // longest lists first
@@ -1363,6 +1369,7 @@ __global__ void __launch_bounds__(256) k_render(GsCam cam, const uint32_t* __res
     const uint32_t r0 = ranges[2 * tile], r1 = ranges[2 * tile + 1];
     bool done = !inside;
     float T = 1.0f, C0 = 0.f, C1 = 0.f, C2 = 0.f;
+    [[maybe_unused]] float Dz = 0.f;
     uint32_t last = 0;
     const uint2* list4 = reinterpret_cast<const uint2*>(st.list[block]);   // four 16-bit entries of this row's list per LDS read
     // everything the blend loop reads from LDS must be FINITE also for a row that is past the end of its list and picks up a stale index (see the
@@ -1374,7 +1381,7 @@ __global__ void __launch_bounds__(256) k_render(GsCam cam, const uint32_t* __res
     for (uint32_t base = r0; base < r1; base += BATCH) {
         if (__syncthreads_count(done) == 256) break;
         const uint32_t k = base + threadIdx.x;
-        const unsigned flags = k < r1 ? stage_entry(st, splat, point_list[k], tx0, ty0) : 0u;
+        const unsigned flags = k < r1 ? stage_entry<AUX>(st, splat, point_list[k], tx0, ty0) : 0u;
         int n_wave;
         const int n_mine = block_lists(st, flags, &n_wave);
         const uint32_t pos0 = base - r0 + 1u;  // contributor number of batch entry 0 = its position in the tile list + 1
@@ -1392,11 +1399,15 @@ __global__ void __launch_bounds__(256) k_render(GsCam cam, const uint32_t* __res
             off[0] = (int)(pack.x & 0xffffu); off[1] = (int)(pack.x >> 16); off[2] = (int)(pack.y & 0xffffu); off[3] = (int)(pack.y >> 16);
             float4 a_j[4], b_j[4];
             float c_j[4];
+            [[maybe_unused]] float z_j[4];
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 a_j[u] = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(st.a) + off[u]);
                 b_j[u] = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(st.b) + off[u]);
-                c_j[u] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(st.c) + off[u]);
+                if constexpr (AUX) {
+                    const float2 cz = *reinterpret_cast<const float2*>(reinterpret_cast<const char*>(st.c) + off[u]);
+                    c_j[u] = cz.x; z_j[u] = cz.y;
+                } else c_j[u] = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(st.c) + off[u]);
             }
             float alpha[4];
             bool ok[4];
@@ -1419,6 +1430,7 @@ __global__ void __launch_bounds__(256) k_render(GsCam cam, const uint32_t* __res
                 // masked entry are multiplied by that 0: they are finite, because the staging arrays start as zeros and only ever receive records.
                 const float w = upd ? alpha[u] * T : 0.f;
                 C0 = fmaf(a_j[u].z, w, C0); C1 = fmaf(a_j[u].w, w, C1); C2 = fmaf(c_j[u], w, C2);
+                if constexpr (AUX) Dz = fmaf(z_j[u], w, Dz);
                 T = upd ? test_T : T;
                 last_off = upd ? off[u] : last_off;
             }
@@ -1431,6 +1443,7 @@ __global__ void __launch_bounds__(256) k_render(GsCam cam, const uint32_t* __res
         final_T[pix] = T;
         n_contrib[pix] = last;
         out_color[pix] = C0 + T * bg0; out_color[hw + pix] = C1 + T * bg1; out_color[2 * hw + pix] = C2 + T * bg2;
+        if constexpr (AUX) { out_depth_alpha[pix] = Dz; out_depth_alpha[hw + pix] = 1.0f - T; }
     }
 }
 
@@ -1447,7 +1460,7 @@ __device__ __forceinline__ float row_sum_to_lane15(float v) {
 }
 // the four accumulators of the blend backward's global atomics, cleared by one launch (3 + 4 + 1 + 3 floats per Gaussian)
 // The blend backward's per-Gaussian accumulator: ONE 64-byte record per Gaussian,
-//   [0..2] dL/dcolour   [3] dL/dopacity   [4..5] dL/dmean2D (x, y)   [6..8] dL/dconic (xx, xy, yy)   [9..15] unused,
+//   [0..2] dL/dcolour   [3] dL/dopacity   [4..5] dL/dmean2D (x, y)   [6..8] dL/dconic (xx, xy, yy)   [9] dL/dz (depth-and-alpha backward)   [10..15] unused,
 // so that the nine sums a tile flushes for a Gaussian are one contiguous 36-byte group of ONE atomic wave-instruction.  Round 2 kept them in four
 // arrays (colour (P,3), opacity (P), mean2D (P,3), conic (P,4)): nine atomic instructions per flushing thread, every lane of each in another
 // cache line -- float atomics execute at the memory side, per 64-byte request, and that shape is the slow one (MI355X_MICROARCH.md, Global float
@@ -1489,15 +1502,25 @@ __device__ __forceinline__ float dpp_add2(float a, float b) {
 #ifndef BW_PAIR
 #define BW_PAIR 1
 #endif
+// AUX: the instance that also takes the pixel gradients of the depth and alpha maps (dL_daux, (2, H, W)).  Both are further blended channels with
+// background 0: depth has the channel value z of the splat record, alpha the channel value 1.  They enter dL/dalpha like colours (so opacity, mean2D
+// and conic need no new sums), and depth adds ONE per-Gaussian sum, dL/dz = sum w g_d, the tenth column of s_acc and slot [9] of the gradient record.
+//   Fixed point: the class bounds above hold for channel values of order 1.  z is not: its term of dL/dalpha is (z - z_behind) g_d T, at most z_max |g_d|
+//   with z_max the largest depth of the tile's blended prefix -- the LAST entry of that prefix, the lists being in depth order.  The per-tile exponent is
+//   therefore taken from max(|g_rgb|, |g_a|, |g_d| max(1, z_max)): every sum is still linear in that quantity with the same class bounds.
+//   The tenth sum is a plain row sum deposited by lane 15 of the row (a lane the transposing reduction leaves without a column): the default instance
+//   keeps its nine columns, its LDS and its instructions.
+template <bool AUX>
 __global__ void __launch_bounds__(256) k_render_bw(GsCam cam, const uint32_t* __restrict__ ranges, const int32_t* __restrict__ point_list,
                                                    const float4* __restrict__ splat, const uint32_t* __restrict__ tile_order, float bg0, float bg1, float bg2,
                                                    const float* __restrict__ pose, const uint32_t* __restrict__ n_contrib, const float* __restrict__ final_T,
-                                                   const float* __restrict__ dL_dpix, float* __restrict__ grad_rec) {
+                                                   const float* __restrict__ dL_dpix, float* __restrict__ grad_rec, const float* __restrict__ dL_daux) {
+    constexpr int NQ = AUX ? 10 : 9;
     __shared__ StageLdsT<uint8_t> st;
-    __shared__ unsigned long long s_acc[BATCH][9];  // per-Gaussian gradient sums of the tile's 16 blocks (fixed point), flushed once per batch
+    __shared__ unsigned long long s_acc[BATCH][NQ];  // per-Gaussian gradient sums of the tile's 16 blocks (fixed point), flushed once per batch
     __shared__ int s_id[BATCH];                     // Gaussian of batch entry t (-1: nothing staged)
     __shared__ int s_blast[N_BLOCKS];
-    __shared__ float s_gmax[4];
+    __shared__ float s_gmax[AUX ? 8 : 4];
     if (pose) { bg0 = pose[35]; bg1 = pose[36]; bg2 = pose[37]; }
     const int tile = (int)tile_order[blockIdx.x];  // longest lists first
     const int tile_x = tile % cam.gx, tile_y = tile / cam.gx;
@@ -1515,6 +1538,8 @@ __global__ void __launch_bounds__(256) k_render_bw(GsCam cam, const uint32_t* __
     const int last = inside ? (int)n_contrib[pix] : 0;
     float n0 = 0.f, n1 = 0.f, n2 = 0.f;  // colour accumulated behind the current Gaussian
     const float g0 = inside ? dL_dpix[pix] : 0.f, g1 = inside ? dL_dpix[hw + pix] : 0.f, g2 = inside ? dL_dpix[2 * hw + pix] : 0.f;
+    [[maybe_unused]] float g_d = 0.f, g_a = 0.f, n3 = 0.f, n4 = 0.f;   // AUX: the depth and alpha channels' pixel gradients and what lies behind the current Gaussian
+    if constexpr (AUX) { if (inside) { g_d = dL_daux[pix]; g_a = dL_daux[hw + pix]; } }
     const float bg_dot = bg0 * g0 + bg1 * g1 + bg2 * g2;
     const float ddelx_dx = 0.5f * cam.W, ddely_dy = 0.5f * cam.H;
     const float neg_tf_bg = -T_final * bg_dot;
@@ -1529,11 +1554,28 @@ __global__ void __launch_bounds__(256) k_render_bw(GsCam cam, const uint32_t* __
     // past the end of its list and picks up a stale index: the staging arrays start as zeros (later batches leave finite records behind).
     st.a[threadIdx.x] = make_float4(0.f, 0.f, 0.f, 0.f); st.b[threadIdx.x] = make_float4(0.f, 0.f, 0.f, 0.f); st.c[threadIdx.x] = make_float4(0.f, 0.f, 0.f, 0.f);
     float gmax = inside ? fmaxf(fmaxf(fabsf(g0), fabsf(g1)), fabsf(g2)) : 0.f;
+    if constexpr (AUX) gmax = fmaxf(gmax, fabsf(g_a));   // (0 outside the image)
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) gmax = fmaxf(gmax, __shfl_xor(gmax, d, 64));
+    if constexpr (AUX) {   // the depth gradient is reduced on its own: it meets z_max below
+        float gdm = fabsf(g_d);
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) gdm = fmaxf(gdm, __shfl_xor(gdm, d, 64));
+        if (lane == 0) s_gmax[4 + (threadIdx.x >> 6)] = gdm;
+    }
     if (lane == 0) s_gmax[threadIdx.x >> 6] = gmax;
     __syncthreads();
     gmax = fmaxf(fmaxf(s_gmax[0], s_gmax[1]), fmaxf(s_gmax[2], s_gmax[3]));
+    if constexpr (AUX) {
+        const float gdm = fmaxf(fmaxf(s_gmax[4], s_gmax[5]), fmaxf(s_gmax[6], s_gmax[7]));
+        // z_max of the blended prefix = the depth of its last entry (depth order); the prefix length as computed below
+        int ne = lane < N_BLOCKS ? s_blast[lane] : 0;
+#pragma unroll
+        for (int d = 8; d > 0; d >>= 1) ne = max(ne, __shfl_xor(ne, d, 16));
+        ne = min(n_tile, __builtin_amdgcn_readfirstlane(ne));
+        const float z_max = ne > 0 ? splat[4 * (size_t)point_list[r0 + ne - 1] + 3].w : 0.f;
+        gmax = fmaxf(gmax, gdm * fmaxf(1.0f, z_max));
+    }
     if (!(gmax > 0.f)) return;  // no gradient reaches this tile (uniform over the workgroup: nobody is left at a barrier)
     int gexp;
     (void)frexpf(gmax, &gexp);    // every |dL/dpixel| of the tile is < 2^gexp
@@ -1557,7 +1599,7 @@ __global__ void __launch_bounds__(256) k_render_bw(GsCam cam, const uint32_t* __
         __syncthreads();
         const int nb_raw = min(BATCH, n_eff - done_cnt);
 #pragma unroll
-        for (int q = 0; q < 9; q++) s_acc[threadIdx.x][q] = 0ull;
+        for (int q = 0; q < NQ; q++) s_acc[threadIdx.x][q] = 0ull;
         // stage the batch; per block the list of entries whose alpha >= 1/255 ellipse box reaches it (see k_render)
         int id_l = 0;
         unsigned flags = 0;
@@ -1574,7 +1616,8 @@ __global__ void __launch_bounds__(256) k_render_bw(GsCam cam, const uint32_t* __
             if (flags) {
                 st.a[threadIdx.x] = make_float4(q0.x, q0.y, q3.x, q3.y);
                 st.b[threadIdx.x] = make_float4(q0.z, q1.x, q0.w, q1.y);
-                st.c[threadIdx.x].x = q3.z;
+                if constexpr (AUX) *reinterpret_cast<float2*>(&st.c[threadIdx.x]) = make_float2(q3.z, q3.w);
+                else st.c[threadIdx.x].x = q3.z;
             }
         }
         s_id[threadIdx.x] = flags ? id_l : -1;
@@ -1583,14 +1626,16 @@ __global__ void __launch_bounds__(256) k_render_bw(GsCam cam, const uint32_t* __
         // One list entry of this row: the record, this pixel's offset, alpha exactly as the forward computed it, and whether the pixel blended it.
         // entry j of the batch sits at list position pos_top - j; this pixel blended the positions < last (0 for a pixel outside the image): j > pos_top - last
         const int j_behind = pos_top - last;
-        struct Entry { float4 co; float cx, cy, dx, dy, c0, c1, c2, G, alpha; int j; bool active; };
+        struct Entry { float4 co; float cx, cy, dx, dy, c0, c1, c2, G, alpha, z; int j; bool active; };
         auto entry = [&](int jj) {
             Entry e;
             const uint32_t pack = list4[jj >> 2];  // four entries of this row's list per dword
             e.j = (int)__builtin_amdgcn_ubfe(pack, 8u * ((uint32_t)jj & 3u), 8u);   // one v_bfe_u32 (the shift is wave-uniform)
             e.co = st.b[e.j];
             const float4 xyrg = st.a[e.j];
-            e.c0 = xyrg.z; e.c1 = xyrg.w; e.c2 = st.c[e.j].x;
+            if constexpr (AUX) { const float2 cz = *reinterpret_cast<const float2*>(&st.c[e.j]); e.c2 = cz.x; e.z = cz.y; }
+            else e.c2 = st.c[e.j].x;
+            e.c0 = xyrg.z; e.c1 = xyrg.w;
             const v2f d = (v2f){xyrg.x, xyrg.y} - (v2f){fx, fy};
             e.dx = d.x; e.dy = d.y;
             const float power = blend_power((v2f){e.co.x, e.co.y}, e.co.z, d);
@@ -1603,7 +1648,7 @@ __global__ void __launch_bounds__(256) k_render_bw(GsCam cam, const uint32_t* __
         // flush and multiply-add pairs are fused: tolerance-checked values, unlike alpha above, which repeats the forward's arithmetic exactly.
         // The colour behind the current Gaussian is carried as ONE running value per channel (the reference keeps last alpha / last colour and
         // rebuilds it every step: same recurrence).  Updates T and n0..n2; returns this lane's column of the row sums.
-        auto gradients = [&](const Entry& e) {
+        auto gradients = [&](const Entry& e, [[maybe_unused]] float& z_sum) {
             // two masked factors carry `active` through everything below: a lane that does not blend this Gaussian multiplies T by 1 / (1 - 0) = 1
             // exactly, moves its colour behind by 0 and adds 0 to every sum (all other factors are finite: alpha <= 0.99, and only G can overflow,
             // when power > 0)
@@ -1614,6 +1659,12 @@ __global__ void __launch_bounds__(256) k_render_bw(GsCam cam, const uint32_t* __
             float dL_dalpha = e0 * g0;
             dL_dalpha = fmaf(e1, g1, dL_dalpha);
             dL_dalpha = fmaf(e2, g2, dL_dalpha);
+            [[maybe_unused]] float e3 = 0.f, e4 = 0.f;
+            if constexpr (AUX) {   // two more channels: value z, value 1 (background 0: no term of theirs in neg_tf_bg)
+                e3 = e.z - n3; e4 = 1.0f - n4;
+                dL_dalpha = fmaf(e3, g_d, dL_dalpha);
+                dL_dalpha = fmaf(e4, g_a, dL_dalpha);
+            }
             dL_dalpha = fmaf(neg_tf_bg, r_om, dL_dalpha * T_new);
             const float dchm = alpha_m * T_new;
             const float d_op = Gm * dL_dalpha;          // sum G dL/dalpha
@@ -1624,6 +1675,10 @@ __global__ void __launch_bounds__(256) k_render_bw(GsCam cam, const uint32_t* __
             const float d_c0 = dchm * g0, d_c1 = dchm * g1, d_c2 = dchm * g2;
             T = T_new;
             n0 = fmaf(alpha_m, e0, n0); n1 = fmaf(alpha_m, e1, n1); n2 = fmaf(alpha_m, e2, n2);   // = alpha c + (1 - alpha) n: what lies behind the next one
+            if constexpr (AUX) {
+                n3 = fmaf(alpha_m, e3, n3); n4 = fmaf(alpha_m, e4, n4);
+                z_sum = row_sum_to_lane15(dchm * g_d);   // dL/dz of this row's Gaussian, in lane 15 of the row
+            }
             // Row-level reduction (row = block = one Gaussian) that also TRANSPOSES: four exchange steps with the partners lane ^ 15, ^ 7, ^ 3, ^ 1
             // (DPP row_mirror, row_half_mirror and two quad permutations); at each step a lane keeps one half of its values and adds what the
             // partner held of that half, so the nine sums end in nine different lanes (21 instructions; nine separate row sums took 36).
@@ -1652,22 +1707,36 @@ __global__ void __launch_bounds__(256) k_render_bw(GsCam cam, const uint32_t* __
                 atomicAdd(&s_acc[j][q_col], ((unsigned long long)(uint32_t)(int)hf << 32) | lo32);
             }
         };
+        // AUX: the tenth sum, from lane 15 of the row (q_has is false there), colour class, same conversion
+        auto deposit_z = [&](int jj, int j, float z_sum) {
+            if (l16 == 15 && jj < n_mine) {
+                const float y = __builtin_amdgcn_fmed3f(z_sum * ldexpf(1.0f, BW_S_COLOR - gexp), -0x1p61f, 0x1p61f);
+                const float t = __builtin_truncf(y);
+                const float hf = __builtin_floorf(t * 0x1p-32f);
+                const uint32_t lo32 = (uint32_t)__builtin_fmaf(-hf, 0x1p32f, t);
+                atomicAdd(&s_acc[j][NQ - 1], ((unsigned long long)(uint32_t)(int)hf << 32) | lo32);
+            }
+        };
         // BW_PAIR entries per trip: their record reads, exponentials and reductions are independent instruction streams (only T and the
         // running colour pass from one to the next), which is what this latency-bound loop lacks
 #if BW_PAIR
         for (int jj = 0; jj < n_wave; jj += 2) {
             const Entry ea = entry(jj), eb = entry(jj + 1);
             if (__ballot(ea.active | eb.active) == 0ull) continue;  // nobody in this wave sees either Gaussian
-            const float ma = gradients(ea);
-            const float mb = gradients(eb);
+            float za = 0.f, zb = 0.f;
+            const float ma = gradients(ea, za);
+            const float mb = gradients(eb, zb);
             deposit(jj, ea.j, ma);
             deposit(jj + 1, eb.j, mb);
+            if constexpr (AUX) { deposit_z(jj, ea.j, za); deposit_z(jj + 1, eb.j, zb); }
         }
 #else
         for (int jj = 0; jj < n_wave; jj++) {
             const Entry ea = entry(jj);
             if (__ballot(ea.active) == 0ull) continue;  // nobody in this wave sees its Gaussian
-            deposit(jj, ea.j, gradients(ea));
+            float za = 0.f;
+            deposit(jj, ea.j, gradients(ea, za));
+            if constexpr (AUX) deposit_z(jj, ea.j, za);
         }
 #endif
         __syncthreads();
@@ -1675,12 +1744,12 @@ __global__ void __launch_bounds__(256) k_render_bw(GsCam cam, const uint32_t* __
         // 64-byte record, instead of 64 lanes in 64 different lines.  Same sums, same one atomic per (tile, Gaussian, quantity).
         {
             const int q = threadIdx.x & 15;
-            const float inv = q < 3 ? ldexpf(1.0f, gexp - BW_S_COLOR) : q == 3 ? ldexpf(1.0f, gexp - BW_S_OPACITY)
+            const float inv = (q < 3 || (AUX && q == 9)) ? ldexpf(1.0f, gexp - BW_S_COLOR) : q == 3 ? ldexpf(1.0f, gexp - BW_S_OPACITY)
                             : q == 4 ? -ddelx_dx * ldexpf(1.0f, gexp - BW_S_MEAN) : q == 5 ? -ddely_dy * ldexpf(1.0f, gexp - BW_S_MEAN)
                                                                                            : -0.5f * ldexpf(1.0f, gexp - BW_S_CONIC);
             for (int e = threadIdx.x >> 4; e < nb_raw; e += 16) {
                 const int id = s_id[e];
-                if (id >= 0 && q < 9) {
+                if (id >= 0 && q < NQ) {
                     const long long a = (long long)s_acc[e][q];
                     if (a != 0ll) atomicAdd(grad_rec + (size_t)id * GREC + q, (float)a * inv);
                 }
@@ -1700,11 +1769,12 @@ __device__ __forceinline__ void preprocess_bw_one(int i, const GsCam& cam, const
                                                   const float* __restrict__ opacities, float* __restrict__ dL_dopacity) {
     // the blend kernel's sums of this Gaussian: one 64-byte record (see k_zero_grads); the API's per-quantity tensors are written from it
     const float4 r0 = *reinterpret_cast<const float4*>(grad_rec + (size_t)i * GREC), r1 = *reinterpret_cast<const float4*>(grad_rec + (size_t)i * GREC + 4);
-    const float r2x = grad_rec[(size_t)i * GREC + 8];
+    const float2 r2 = *reinterpret_cast<const float2*>(grad_rec + (size_t)i * GREC + 8);   // [8] conic yy, [9] dL/dz (depth-and-alpha backward only; 0 otherwise)
+    const float r2x = r2.x;
     // ... and the record is left cleared for the next backward (the caller keeps the buffer: no clearing launch in front of k_render_bw)
     *reinterpret_cast<float4*>(grad_rec + (size_t)i * GREC) = make_float4(0.f, 0.f, 0.f, 0.f);
     *reinterpret_cast<float4*>(grad_rec + (size_t)i * GREC + 4) = make_float4(0.f, 0.f, 0.f, 0.f);
-    grad_rec[(size_t)i * GREC + 8] = 0.f;
+    *reinterpret_cast<float2*>(grad_rec + (size_t)i * GREC + 8) = make_float2(0.f, 0.f);
     const float gcol[3] = {r0.x, r0.y, r0.z};
     {
         float g_op = r0.w;
@@ -1774,6 +1844,11 @@ __device__ __forceinline__ void preprocess_bw_one(int i, const GsCam& cam, const
     dmean[0] += (pm[0] * mw - pm[3] * mul1) * g2x + (pm[1] * mw - pm[3] * mul2) * g2y;
     dmean[1] += (pm[4] * mw - pm[7] * mul1) * g2x + (pm[5] * mw - pm[7] * mul2) * g2y;
     dmean[2] += (pm[8] * mw - pm[11] * mul1) * g2x + (pm[9] * mw - pm[11] * mul2) * g2y;
+    // z = mean . view[:3, 2] + view[3, 2] (xform43, the line of preprocess_one that writes depths): dL/dz of the depth map reaches the mean through that column
+    if (r2.y != 0.f) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) dmean[k] += vm[2 + 4 * k] * r2.y;
+    }
     if (use_sh) {
         const float dir0[3] = {mean[0] - cam.campos[0], mean[1] - cam.campos[1], mean[2] - cam.campos[2]};
         const float sum2 = dir0[0] * dir0[0] + dir0[1] * dir0[1] + dir0[2] * dir0[2];
@@ -2206,7 +2281,8 @@ int nrc_gs_camera_block(const float* c2w_dev, const float* proj_t_dev, const flo
 static int gs_bin_render_impl(int32_t P, int32_t W, int32_t H, const float* bg_host, const float* camera_dev, const int32_t* radii, const float* depths,
                       const float* points_xy, const float* conic_opacity, const float* rgb, const uint32_t* ranges, uint32_t* tile_fill,
                       const uint32_t* bin_hist, int64_t span_capacity, int64_t instance_capacity, uint64_t* keys, int32_t* point_list,
-                      const float* splat_records, float* out_color, uint32_t* n_contrib, float* final_T, int32_t yb0, int32_t n_rows, nrc_stream_t stream) {
+                      const float* splat_records, float* out_color, uint32_t* n_contrib, float* final_T, int32_t yb0, int32_t n_rows, float* out_depth_alpha,
+                      nrc_stream_t stream) {
     if (P < 0 || W < 1 || H < 1 || (!bg_host && !camera_dev) || !ranges || !tile_fill || !out_color || !n_contrib || !final_T) return NRC_ERR_INVALID;
     if (instance_capacity < 0 || instance_capacity > 0xfffffffell) return NRC_ERR_INVALID;
     const uint32_t list_cap = instance_capacity > 0 ? (uint32_t)instance_capacity : 0xffffffffu;
@@ -2244,8 +2320,13 @@ static int gs_bin_render_impl(int32_t P, int32_t W, int32_t H, const float* bg_h
         NRC_STAGE(s, "k_tile_order");
     }
     // one workgroup per band tile: tile_fill lists the band's tiles only, so the pixel rows outside the band are never written
-    hipLaunchKernelGGL(k_render, dim3(cam.gx * n_rows), dim3(256), 0, s, cam, ranges, point_list, (const float4*)splat_records, tile_fill, bg[0], bg[1], bg[2],
-                       camera_dev, out_color, n_contrib, final_T);
+    // out_depth_alpha: the instance that also blends the depth channel; NULL: the colour-only kernel
+    if (out_depth_alpha)
+        hipLaunchKernelGGL(k_render<true>, dim3(cam.gx * n_rows), dim3(256), 0, s, cam, ranges, point_list, (const float4*)splat_records, tile_fill, bg[0], bg[1], bg[2],
+                           camera_dev, out_color, n_contrib, final_T, out_depth_alpha);
+    else
+        hipLaunchKernelGGL(k_render<false>, dim3(cam.gx * n_rows), dim3(256), 0, s, cam, ranges, point_list, (const float4*)splat_records, tile_fill, bg[0], bg[1], bg[2],
+                           camera_dev, out_color, n_contrib, final_T, (float*)nullptr);
     NRC_STAGE(s, "k_render");
     NRC_LAUNCH_CHECK();
     return NRC_OK;
@@ -2256,7 +2337,7 @@ int nrc_gs_bin_render(int32_t P, int32_t W, int32_t H, const float* bg_host, con
                       const float* splat_records, float* out_color, uint32_t* n_contrib, float* final_T, nrc_stream_t stream) {
     NRC_ENTER();
     return gs_bin_render_impl(P, W, H, bg_host, camera_dev, radii, depths, points_xy, conic_opacity, rgb, ranges, tile_fill, bin_hist, span_capacity, instance_capacity,
-                              keys, point_list, splat_records, out_color, n_contrib, final_T, 0, gs_all_rows(H), stream);
+                              keys, point_list, splat_records, out_color, n_contrib, final_T, 0, gs_all_rows(H), nullptr, stream);
 }
 int nrc_gs_bin_render_band(int32_t P, int32_t W, int32_t H, const float* bg_host, const float* camera_dev, const int32_t* radii, const float* depths,
                       const float* points_xy, const float* conic_opacity, const float* rgb, const uint32_t* ranges, uint32_t* tile_fill,
@@ -2266,7 +2347,17 @@ int nrc_gs_bin_render_band(int32_t P, int32_t W, int32_t H, const float* bg_host
     if (!gs_band_ok(H, tile_row_begin, n_tile_rows)) return NRC_ERR_INVALID;
     NRC_ENTER();
     return gs_bin_render_impl(P, W, H, bg_host, camera_dev, radii, depths, points_xy, conic_opacity, rgb, ranges, tile_fill, bin_hist, span_capacity, instance_capacity,
-                              keys, point_list, splat_records, out_color, n_contrib, final_T, tile_row_begin, n_tile_rows, stream);
+                              keys, point_list, splat_records, out_color, n_contrib, final_T, tile_row_begin, n_tile_rows, nullptr, stream);
+}
+int nrc_gs_bin_render_aux_band(int32_t P, int32_t W, int32_t H, const float* bg_host, const float* camera_dev, const int32_t* radii, const float* depths,
+                      const float* points_xy, const float* conic_opacity, const float* rgb, const uint32_t* ranges, uint32_t* tile_fill,
+                      const uint32_t* bin_hist, int64_t span_capacity, int64_t instance_capacity, uint64_t* keys, int32_t* point_list,
+                      const float* splat_records, float* out_color, uint32_t* n_contrib, float* final_T, int32_t tile_row_begin, int32_t n_tile_rows,
+                      float* out_depth_alpha, nrc_stream_t stream) {
+    if (!gs_band_ok(H, tile_row_begin, n_tile_rows)) return NRC_ERR_INVALID;
+    NRC_ENTER();
+    return gs_bin_render_impl(P, W, H, bg_host, camera_dev, radii, depths, points_xy, conic_opacity, rgb, ranges, tile_fill, bin_hist, span_capacity, instance_capacity,
+                              keys, point_list, splat_records, out_color, n_contrib, final_T, tile_row_begin, n_tile_rows, out_depth_alpha, stream);
 }
 
 static int gs_backward_impl(int32_t P, int32_t D, int32_t M, int32_t W, int32_t H, const float* bg_host, const float* means3D, const float* shs,
@@ -2277,7 +2368,7 @@ static int gs_backward_impl(int32_t P, int32_t D, int32_t M, int32_t W, int32_t 
                     const float* splat_records, const uint32_t* tile_order, const uint32_t* n_contrib, const float* final_T, const float* dL_dpix,
                     float* dL_dmean2D, float* dL_dconic,
                     float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dsh_rest, float* dL_dscale,
-                    float* dL_drot, float* grad_records, int32_t records_clear, nrc_stream_t stream, RestAdam ra, int32_t n_rows) {
+                    float* dL_drot, float* grad_records, int32_t records_clear, nrc_stream_t stream, RestAdam ra, int32_t n_rows, const float* dL_ddepth_alpha) {
     GsCam cam;
     const int rc = make_cam(cam, W, H, D, M, viewmatrix_host, projmatrix_host, campos_host, camera_dev, tan_fovx, tan_fovy, scale_modifier, raw_parameters);
     if (rc != NRC_OK) return rc;
@@ -2299,8 +2390,13 @@ static int gs_backward_impl(int32_t P, int32_t D, int32_t M, int32_t W, int32_t 
         NRC_STAGE(s, "k_zero_grads");
     }
     // n_rows tile rows (< gy for a band): tile_order lists the tiles of the forward's band, one workgroup each
-    hipLaunchKernelGGL(k_render_bw, dim3(cam.gx * n_rows), dim3(256), 0, s, cam, ranges, point_list, (const float4*)splat_records, tile_order, bg[0], bg[1], bg[2],
-                       camera_dev, n_contrib, final_T, dL_dpix, grad_records);
+    // dL_ddepth_alpha: the instance that also takes the two extra pixel gradients (slot [9] of the records); NULL: the colour-only kernel
+    if (dL_ddepth_alpha)
+        hipLaunchKernelGGL(k_render_bw<true>, dim3(cam.gx * n_rows), dim3(256), 0, s, cam, ranges, point_list, (const float4*)splat_records, tile_order, bg[0], bg[1], bg[2],
+                           camera_dev, n_contrib, final_T, dL_dpix, grad_records, dL_ddepth_alpha);
+    else
+        hipLaunchKernelGGL(k_render_bw<false>, dim3(cam.gx * n_rows), dim3(256), 0, s, cam, ranges, point_list, (const float4*)splat_records, tile_order, bg[0], bg[1], bg[2],
+                           camera_dev, n_contrib, final_T, dL_dpix, grad_records, (const float*)nullptr);
     NRC_STAGE(s, "k_render_bw");
 #define GS_PBW_ARGS P, cam, camera_dev, means3D, shs, shs_rest, opacities, use_sh, scales, rotations, use_sr, radii, clamped, cov3D, grad_records, dL_dmean2D, dL_dconic, dL_dcolor, \
                     dL_dmean3D, dL_dcov3D, dL_dsh, dL_dsh_rest, dL_dscale, dL_drot, dL_dopacity, ra
@@ -2326,7 +2422,7 @@ int nrc_gs_backward(int32_t P, int32_t D, int32_t M, int32_t W, int32_t H, const
     return gs_backward_impl(P, D, M, W, H, bg_host, means3D, shs, shs_rest, raw_parameters, opacities, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
                             viewmatrix_host, projmatrix_host, campos_host, camera_dev, tan_fovx, tan_fovy, radii, points_xy, conic_opacity, rgb, clamped, cov3D, point_list,
                             ranges, splat_records, tile_order, n_contrib, final_T, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
-                            dL_dsh_rest, dL_dscale, dL_drot, grad_records, records_clear, stream, RestAdam{nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, 0.f, 1.f, 1.f}, gs_all_rows(H));
+                            dL_dsh_rest, dL_dscale, dL_drot, grad_records, records_clear, stream, RestAdam{nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, 0.f, 1.f, 1.f}, gs_all_rows(H), nullptr);
 }
 int nrc_gs_backward_band(int32_t P, int32_t D, int32_t M, int32_t W, int32_t H, const float* bg_host, const float* means3D, const float* shs,
                     const float* shs_rest, int32_t raw_parameters, const float* opacities, const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
@@ -2342,7 +2438,25 @@ int nrc_gs_backward_band(int32_t P, int32_t D, int32_t M, int32_t W, int32_t H, 
     return gs_backward_impl(P, D, M, W, H, bg_host, means3D, shs, shs_rest, raw_parameters, opacities, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
                             viewmatrix_host, projmatrix_host, campos_host, camera_dev, tan_fovx, tan_fovy, radii, points_xy, conic_opacity, rgb, clamped, cov3D, point_list,
                             ranges, splat_records, tile_order, n_contrib, final_T, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
-                            dL_dsh_rest, dL_dscale, dL_drot, grad_records, records_clear, stream, RestAdam{nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, 0.f, 1.f, 1.f}, n_tile_rows);
+                            dL_dsh_rest, dL_dscale, dL_drot, grad_records, records_clear, stream, RestAdam{nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, 0.f, 1.f, 1.f}, n_tile_rows, nullptr);
+}
+int nrc_gs_backward_aux_band(int32_t P, int32_t D, int32_t M, int32_t W, int32_t H, const float* bg_host, const float* means3D, const float* shs,
+                    const float* shs_rest, int32_t raw_parameters, const float* opacities, const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
+                    const float* cov3D_precomp, const float* viewmatrix_host, const float* projmatrix_host, const float* campos_host,
+                    const float* camera_dev, float tan_fovx, float tan_fovy, const int32_t* radii, const float* points_xy, const float* conic_opacity,
+                    const float* rgb, const uint8_t* clamped, const float* cov3D, const int32_t* point_list, const uint32_t* ranges,
+                    const float* splat_records, const uint32_t* tile_order, const uint32_t* n_contrib, const float* final_T, const float* dL_dpix,
+                    float* dL_dmean2D, float* dL_dconic,
+                    float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dsh_rest, float* dL_dscale,
+                    float* dL_drot, float* grad_records, int32_t records_clear, int32_t tile_row_begin, int32_t n_tile_rows, const float* dL_ddepth_alpha,
+                    nrc_stream_t stream) {
+    if (!gs_band_ok(H, tile_row_begin, n_tile_rows)) return NRC_ERR_INVALID;
+    NRC_ENTER();
+    return gs_backward_impl(P, D, M, W, H, bg_host, means3D, shs, shs_rest, raw_parameters, opacities, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
+                            viewmatrix_host, projmatrix_host, campos_host, camera_dev, tan_fovx, tan_fovy, radii, points_xy, conic_opacity, rgb, clamped, cov3D, point_list,
+                            ranges, splat_records, tile_order, n_contrib, final_T, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
+                            dL_dsh_rest, dL_dscale, dL_drot, grad_records, records_clear, stream, RestAdam{nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, 0.f, 1.f, 1.f}, n_tile_rows,
+                            dL_ddepth_alpha);
 }
 
 /* nrc_gs_backward whose preprocessing backward applies the optimizer's Adam step to the `rest` SH tensor itself (shs_rest_param = the tensor passed as shs_rest in the
@@ -2361,7 +2475,7 @@ int nrc_gs_backward_rest_step(int32_t P, int32_t D, int32_t M, int32_t W, int32_
                             nullptr, nullptr, nullptr, camera_dev, tan_fovx, tan_fovy, radii, points_xy, conic_opacity, rgb, clamped, cov3D, point_list,
                             ranges, splat_records, tile_order, n_contrib, final_T, dL_dpix, dL_dmean2D, nullptr, dL_dopacity, nullptr, dL_dmean3D, dL_dcov3D, dL_dsh,
                             nullptr, dL_dscale, dL_drot, grad_records, records_clear, stream,
-                            RestAdam{shs_rest_param, rest_exp_avg, rest_exp_avg_sq, lr, beta1, beta2, eps, bias_correction1, bias_correction2}, gs_all_rows(H));
+                            RestAdam{shs_rest_param, rest_exp_avg, rest_exp_avg_sq, lr, beta1, beta2, eps, bias_correction1, bias_correction2}, gs_all_rows(H), nullptr);
 }
 
 }  // extern "C"

@@ -154,10 +154,15 @@ def _opt(t):
 
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, sh_rest=None, raw=False, rest_step=None, tile_rows=None):
+    def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, sh_rest=None, raw=False, rest_step=None, tile_rows=None,
+                depth_alpha=False):
         rs = raster_settings
         lib = _lib.load()
         band = check_tile_rows(tile_rows, rs.image_height)
+        depth_alpha = bool(depth_alpha)
+        if depth_alpha and rest_step is not None:
+            raise RuntimeError('return_depth_alpha together with rest_step: the backward pass that steps the `rest` SH tensor (nrc_gs_backward_rest_step) takes the '
+                               'colour gradient only -- there is no depth-and-alpha form of it; render without rest_step and let the optimizer take that step')
         if band is not None and rest_step is not None:
             raise RuntimeError('rest_step together with tile_rows: the backward pass of a band holds this band\'s SHARE of the gradient only, and an Adam step '
                                'taken on a partial gradient is not the optimizer\'s step -- sum the shares over the bands first and step then')
@@ -208,6 +213,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             inst_cap = min(int(max(history) * 1.3) + 65536, 0xfffffff0)
         # a band writes its own pixel rows only: the rest of the image is zero, so that the band images of a partition sum (and slice) to the frame
         color = torch.empty(3, H, W, dtype=f32, device=dev) if band is None else torch.zeros(3, H, W, dtype=f32, device=dev)
+        # depth and alpha maps (2, H, W): plane 0 = sum w z, plane 1 = sum w; a band writes its own rows only, like the colour
+        aux = None if not depth_alpha else (torch.empty(2, H, W, dtype=f32, device=dev) if band is None else torch.zeros(2, H, W, dtype=f32, device=dev))
         band_mask = None if band is None else torch.empty(n1, dtype=u8, device=dev)
         n_contrib = torch.empty(H * W, dtype=i32, device=dev)
         final_T = torch.empty(H * W, dtype=f32, device=dev)
@@ -235,6 +242,13 @@ class _RasterizeGaussians(torch.autograd.Function):
         def bin_render(hist, cap_spans, cap_inst, n_list):
             keys_ = torch.empty(max(n_list, 1) if hist is None else 1, dtype=torch.int64, device=dev)  # only the per-tile key sort fallback uses them
             plist = torch.empty(max(n_list, 1), dtype=i32, device=dev)
+            if aux is not None:   # the blend instance that also accumulates depth (a whole frame = the band of all gy tile rows)
+                b0, bn = band if band is not None else (0, gy)
+                _lib.check(lib.nrc_gs_bin_render_aux_band(P, W, H, None, _lib.ptr(cam_block), _lib.ptr(radii), _lib.ptr(depths), _lib.ptr(points_xy), _lib.ptr(conic_opacity),
+                                                          _lib.ptr(rgb), _lib.ptr(ranges), _lib.ptr(tile_fill), _lib.ptr(hist), cap_spans, cap_inst, _lib.ptr(keys_), _lib.ptr(plist),
+                                                          _lib.ptr(splat), _lib.ptr(color), _lib.ptr(n_contrib), _lib.ptr(final_T), b0, bn, _lib.ptr(aux), st),
+                           'gs_bin_render_aux_band')
+                return keys_, plist
             if band is not None:
                 _lib.check(lib.nrc_gs_bin_render_band(P, W, H, None, _lib.ptr(cam_block), _lib.ptr(radii), _lib.ptr(depths), _lib.ptr(points_xy), _lib.ptr(conic_opacity),
                                                       _lib.ptr(rgb), _lib.ptr(ranges), _lib.ptr(tile_fill), _lib.ptr(hist), cap_spans, cap_inst, _lib.ptr(keys_), _lib.ptr(plist),
@@ -316,6 +330,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         # (the per-tile key sort fallback, which takes the band (0, gy) only, does not write the mask: every visible Gaussian is in that band)
         _LAST_BAND_MASK = None if band is None else ((band_mask[:P] != 0) if bin_hist is not None and P > 0 else (radii[:P] > 0))
         ctx.band = band
+        ctx.depth_alpha = depth_alpha
         ctx.raster_settings = rs
         ctx.dims = (P, D, M, W, H)
         ctx.num_rendered = n_inst if fixed is None else -1
@@ -335,11 +350,13 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.mark_non_differentiable(radii_out)
         # radii carry no gradient: without this autograd hands the backward a zero-filled (P,) int tensor for them -- a 4 MB fill launch per step
         ctx.set_materialize_grads(False)
+        if depth_alpha:
+            return color, radii_out, aux[0], aux[1]
         return color, radii_out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_out_color, _grad_radii):
+    def backward(ctx, grad_out_color, _grad_radii, *grad_depth_alpha):   # the two extra output gradients exist only for a forward with depth_alpha
         (means3D, sh, col, sc, rot, cov, radii, points_xy, conic_opacity, rgb, clamped, cov3D, point_list, ranges, n_contrib,
          final_T, splat, tile_order, sh_rest, opac, cam_block) = ctx.saved_tensors
         raw, has_rest = ctx.raw, ctx.has_rest
@@ -352,6 +369,12 @@ class _RasterizeGaussians(torch.autograd.Function):
         if grad_out_color is None:   # (grads are not materialised: the image did not take part in the loss)
             grad_out_color = torch.zeros(3, H, W, dtype=f32, device=dev)
         g = grad_out_color.to(f32).contiguous()
+        g_aux = None
+        if ctx.depth_alpha:   # (2, H, W): dL/ddepth, dL/dalpha; a map that did not take part in the loss counts as zero
+            g_aux = torch.zeros(2, H, W, dtype=f32, device=dev)
+            for k, gk in enumerate(grad_depth_alpha[:2]):
+                if gk is not None:
+                    g_aux[k].copy_(gk.reshape(H, W))
         n1 = max(P, 1)
         dmean2D = torch.empty(n1, 3, dtype=f32, device=dev)
         # workspace: one 64-byte accumulator record per Gaussian.  The per-Gaussian backward clears every record it reads, so the buffer of the
@@ -388,6 +411,17 @@ class _RasterizeGaussians(torch.autograd.Function):
                 _lib.ptr(grad_records), int(records_clear), _lib.ptr(m_rest), _lib.ptr(v_rest), float(lr), float(beta1), float(beta2), float(eps), float(bc1), float(bc2),
                 _lib.stream_of(g)), 'gs_backward_rest_step')
             torch.autograd.graph.increment_version(param)      # written through a raw pointer
+        elif g_aux is not None:
+            b0, bn = ctx.band if ctx.band is not None else (0, (H + 15) // 16)
+            _lib.check(lib.nrc_gs_backward_aux_band(
+                P, D, M, W, H, None, _lib.ptr(means3D), _lib.ptr(sh if has_sh else None), _lib.ptr(sh_rest if has_rest else None), int(raw),
+                _lib.ptr(opac if raw else None), _lib.ptr(col if has_col else None),
+                _lib.ptr(sc if has_sr else None), float(rs.scale_modifier), _lib.ptr(rot if has_sr else None), _lib.ptr(cov if has_cov else None),
+                None, None, None, _lib.ptr(cam_block), float(rs.tanfovx), float(rs.tanfovy), _lib.ptr(radii), _lib.ptr(points_xy), _lib.ptr(conic_opacity),
+                _lib.ptr(rgb), _lib.ptr(clamped), _lib.ptr(cov3D), _lib.ptr(point_list), _lib.ptr(ranges), _lib.ptr(splat), _lib.ptr(tile_order), _lib.ptr(n_contrib), _lib.ptr(final_T),
+                _lib.ptr(g), _lib.ptr(dmean2D), None, _lib.ptr(dopacity), _lib.ptr(dcolor), _lib.ptr(dmean3D), _lib.ptr(dcov3D),
+                _lib.ptr(dsh), _lib.ptr(dsh_rest), _lib.ptr(dscale), _lib.ptr(drot), _lib.ptr(grad_records), int(records_clear), b0, bn, _lib.ptr(g_aux),
+                _lib.stream_of(g)), 'gs_backward_aux_band')
         elif ctx.band is not None:
             # this band's share of every gradient: the blend backward over the band's tiles, the per-Gaussian backward over all P
             _lib.check(lib.nrc_gs_backward_band(
@@ -413,11 +447,16 @@ class _RasterizeGaussians(torch.autograd.Function):
         cut = (lambda t: t) if P == n1 else (lambda t: t[:P])     # (whole buffers when nothing is cut: a gradient that is not a view can be adopted as .grad without a copy)
         return (cut(dmean3D), cut(dmean2D), cut(dsh) if has_sh else None, cut(dcolor) if has_col else None,
                 cut(dopacity).reshape(ctx.opacity_shape), cut(dscale) if has_sr else None, cut(drot) if has_sr else None,
-                cut(dcov3D) if has_cov else None, None, cut(dsh_rest) if dsh_rest is not None else None, None, None, None)
+                cut(dcov3D) if has_cov else None, None, cut(dsh_rest) if dsh_rest is not None else None, None, None, None, None)
 
 
-def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, sh_rest=None, raw=False, rest_step=None, tile_rows=None):
-    """`tile_rows` = (begin, n): render and differentiate the band of 16-pixel tile rows [begin, begin + n) only (see GaussianRasterizer.forward); None: the frame."""
+def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, sh_rest=None, raw=False, rest_step=None, tile_rows=None,
+                        return_depth_alpha=False):
+    """`tile_rows` = (begin, n): render and differentiate the band of 16-pixel tile rows [begin, begin + n) only (see GaussianRasterizer.forward); None: the frame.
+    `return_depth_alpha`: (image, radii, depth, alpha) instead of (image, radii) -- see GaussianRasterizer.forward."""
+    if return_depth_alpha:
+        return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, sh_rest, raw, rest_step,
+                                         None if tile_rows is None else tuple(int(v) for v in tile_rows), True)
     if tile_rows is None:
         return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, sh_rest, raw, rest_step)
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, sh_rest, raw, rest_step,
@@ -437,7 +476,7 @@ class GaussianRasterizer(torch.nn.Module):
             return z > 0.2
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, shs_rest=None,
-                raw_parameters=False, rest_step=None, tile_rows=None):
+                raw_parameters=False, rest_step=None, tile_rows=None, return_depth_alpha=False):
         """The reference's call (Renderer.py:75-81) plus two keyword extensions for callers that own the model tensors: `shs_rest` -- `shs` is then
         (`rest_step`, round 6: an object whose take() returns (parameter, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, bc1, bc2) -- the backward pass then applies
         the optimizer's Adam step to shs_rest itself and returns no gradient for it: nerficg_amd.gaussian_splatting.RestStep)
@@ -448,7 +487,12 @@ class GaussianRasterizer(torch.nn.Module):
         by across GPUs (nerficg_amd.parallel.tile_row_band).  The image is still (3, H, W), its band rows bit for bit those of the whole-frame call and zero
         elsewhere (the band images of a partition sum and slice to the frame); `radii` is the full (P,) tensor, identical for every band; the backward pass
         returns this band's SHARE of every gradient, `means2D` included (the shares of a partition sum to the whole-frame gradient, rows of Gaussians that miss
-        the band are exactly zero: last_band_mask()).  Not together with `rest_step`.  None (default): the whole frame, today's call."""
+        the band are exactly zero: last_band_mask()).  Not together with `rest_step`.  None (default): the whole frame, today's call.
+        `return_depth_alpha=True`: the call returns (image, radii, depth, alpha).  depth and alpha are (H, W) float32 maps blended with the colour's own weights
+        w_i = alpha_i T_i and background 0: depth = sum w_i z_i with z_i the view-space depth the sort orders by (ACCUMULATED, not normalised: divide by alpha
+        for an expected depth), alpha = sum w_i = 1 - T_final.  Both are differentiable (a map that takes no part in the loss counts as a zero gradient); image,
+        radii and everything the backward saves are bit for bit those of the call without the flag.  Works with every parameter form above, with `tile_rows`
+        (band rows written, zero elsewhere) and inside fixed_capacity; not together with `rest_step` (RuntimeError)."""
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
         if ((scales is None or rotations is None) and cov3D_precomp is None) or ((scales is not None or rotations is not None) and cov3D_precomp is not None):
@@ -456,4 +500,4 @@ class GaussianRasterizer(torch.nn.Module):
         empty = torch.Tensor([])
         return rasterize_gaussians(means3D, means2D, empty if shs is None else shs, empty if colors_precomp is None else colors_precomp, opacities,
                                    empty if scales is None else scales, empty if rotations is None else rotations,
-                                   empty if cov3D_precomp is None else cov3D_precomp, self.raster_settings, shs_rest, raw_parameters, rest_step, tile_rows)
+                                   empty if cov3D_precomp is None else cov3D_precomp, self.raster_settings, shs_rest, raw_parameters, rest_step, tile_rows, return_depth_alpha)

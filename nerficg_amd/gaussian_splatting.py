@@ -434,8 +434,10 @@ class RestStep:
 
 
 def render_image_training(gaussians: Gaussians, cam: PerspectiveCamera, c2w: np.ndarray, fuse_rest_step: bool | None = None,
-                          band: tuple[int, int] | None = None) -> dict[str, torch.Tensor]:
-    """GaussianSplatting/Renderer.py:51-86.  band = (tile_row_begin, n_tile_rows): this call renders and differentiates that band of 16-pixel tile rows of
+                          band: tuple[int, int] | None = None, depth_alpha: bool = False) -> dict[str, torch.Tensor]:
+    """GaussianSplatting/Renderer.py:51-86.  depth_alpha: the outputs gain 'alpha' and 'depth', (1, H, W) like 'rgb' is (3, H, W), both differentiable: alpha = 1 - T of
+    the blend, depth = (sum w z) / (alpha + 1e-6), the normalisation of InstantNGP/Renderer.py:82 (the rasterizer's `return_depth_alpha`).  Refused together with the
+    fused f_rest step (RuntimeError), like a band.  band = (tile_row_begin, n_tile_rows): this call renders and differentiates that band of 16-pixel tile rows of
     the frame only (the rasterizer's `tile_rows`; parallel.tile_row_band): 'rgb' is zero outside the band, the gradients are the band's share, and the
     outputs gain 'band_mask' (the Gaussians that can receive a gradient from the band).  A band holds a partial gradient, so the in-backward optimizer
     step of `f_rest` is refused with it (RuntimeError), whether asked for here or through gaussians.fuse_rest_step.  fuse_rest_step (default: gaussians.fuse_rest_step, False unless set): the backward pass of this frame applies the
@@ -448,18 +450,25 @@ def render_image_training(gaussians: Gaussians, cam: PerspectiveCamera, c2w: np.
     if band is not None and fuse:
         raise RuntimeError('render_image_training: band= together with the fused f_rest step -- the backward pass of a band holds that band\'s share of the '
                            'gradient only, and Adam applied to a partial gradient is not the optimizer\'s step; sum the shares over the bands and step then')
+    if depth_alpha and fuse:
+        raise RuntimeError('render_image_training: depth_alpha= together with the fused f_rest step -- the backward pass that steps f_rest takes the colour '
+                           'gradient only (the rasterizer refuses return_depth_alpha with rest_step); leave fuse_rest_step off for frames with a depth or alpha loss')
     # the carrier of the screen-space gradient (Renderer.py:56-58: zeros_like + 0, retain_grad): the rasterizer never reads its VALUES, only hands it a
     # gradient -- a leaf of uninitialised memory receives the same .grad without a 12 MB fill and a 24 MB add per step
     viewspace_points = torch.empty_like(positions).requires_grad_(True)
     rasterizer = GaussianRasterizer(make_raster_settings(cam, c2w, gaussians.active_sh_degree, 1.0, positions.device))
     if gaussians.baked:  # a baked model holds activated values
-        image, radii = rasterizer(means3D=positions, means2D=viewspace_points, shs=gaussians.get_features_dc, shs_rest=gaussians.get_features_rest,
-                                  opacities=gaussians.get_opacities, scales=gaussians.get_scales, rotations=gaussians.get_rotations, tile_rows=band)
+        image, radii, *aux = rasterizer(means3D=positions, means2D=viewspace_points, shs=gaussians.get_features_dc, shs_rest=gaussians.get_features_rest,
+                                        opacities=gaussians.get_opacities, scales=gaussians.get_scales, rotations=gaussians.get_rotations, tile_rows=band,
+                                        return_depth_alpha=depth_alpha)
     else:  # raw parameters straight into the kernels: no get_features concatenation, no separate exp / sigmoid / normalize passes (a25)
         rest_step = RestStep(gaussians) if fuse and not getattr(gaussians.optimizer, 'capturable', False) and not torch.cuda.is_current_stream_capturing() and torch.is_grad_enabled() and gaussians._features_rest.requires_grad and gaussians._features_rest.shape[1] > 0 and torch.is_tensor(c2w) else None
-        image, radii = rasterizer(means3D=positions, means2D=viewspace_points, shs=gaussians._features_dc, shs_rest=gaussians._features_rest,
-                                  opacities=gaussians._opacities, scales=gaussians._scales, rotations=gaussians._rotations, raw_parameters=True, rest_step=rest_step, tile_rows=band)
+        image, radii, *aux = rasterizer(means3D=positions, means2D=viewspace_points, shs=gaussians._features_dc, shs_rest=gaussians._features_rest,
+                                        opacities=gaussians._opacities, scales=gaussians._scales, rotations=gaussians._rotations, raw_parameters=True, rest_step=rest_step,
+                                        tile_rows=band, return_depth_alpha=depth_alpha)
     outputs = _TrainingOutputs({'rgb': image, 'viewspace_points': viewspace_points, 'radii': radii})
+    if depth_alpha:
+        outputs.update(_depth_alpha_outputs(aux[0], aux[1], True))
     if band is not None:
         outputs['band_mask'] = last_band_mask()
     return outputs
@@ -498,6 +507,15 @@ def band_parallel_training_step(gaussians: Gaussians, cam: PerspectiveCamera, c2
     return out
 
 
+def _depth_alpha_outputs(depth_sum: torch.Tensor, alpha: torch.Tensor, to_chw: bool) -> dict[str, torch.Tensor]:
+    """'alpha' and 'depth' of a frame from the rasterizer's (H, W) maps, laid out like instant_ngp.render_image lays them out: (H, W, 1), or (1, H, W) with
+    to_chw; depth normalised as InstantNGP/Renderer.py:82 does, depth / (alpha + 1e-6)."""
+    depth = depth_sum / (alpha + 1e-6)
+    if to_chw:
+        return {'alpha': alpha[None], 'depth': depth[None]}
+    return {'alpha': alpha[..., None], 'depth': depth[..., None]}
+
+
 class _TrainingOutputs(dict):
     """The outputs of Renderer.py:83-86; 'visibility_mask' (radii > 0) is built when somebody asks for it -- the densification statistics and the view-parallel
     exchange take `radii` itself, so the plain step does not pay the launch."""
@@ -514,8 +532,9 @@ class _TrainingOutputs(dict):
 
 @torch.no_grad()
 def render_image_inference(gaussians: Gaussians, cam: PerspectiveCamera, c2w: np.ndarray, scale_modifier: float = 1.0, to_chw: bool = False,
-                           use_baked_covariance: bool = True, band: tuple[int, int] | None = None):
-    """band = (tile_row_begin, n_tile_rows): only that band of tile rows of the frame is rendered (zero elsewhere; parallel.gather_band_images composes the
+                           use_baked_covariance: bool = True, band: tuple[int, int] | None = None, depth_alpha: bool = False):
+    """depth_alpha: the outputs gain 'alpha' (1 - T of the blend) and 'depth' (accumulated view-space depth / (alpha + 1e-6)), (H, W, 1) or (1, H, W) with to_chw, as
+    instant_ngp.render_image returns them.  band = (tile_row_begin, n_tile_rows): only that band of tile rows of the frame is rendered (zero elsewhere; parallel.gather_band_images composes the
     frame from the ranks' bands).  GaussianSplatting/Renderer.py:89-155 with the fused SH path (USE_FUSED_SH_CONVERSION = True, the shipped default); a baked model
     (trained checkpoint, Model.py:248-273) is rasterized from its baked covariances like the reference's USE_BAKED_COVARIANCE branch
     (Renderer.py:129-139), everything else through the in-kernel covariance computation."""
@@ -526,13 +545,17 @@ def render_image_inference(gaussians: Gaussians, cam: PerspectiveCamera, c2w: np
     if covariances is not None and covariances.shape[0] != positions.shape[0]:
         covariances = None  # "Baked covariance requested but not available"
     if covariances is not None:
-        image, _ = rasterizer(means3D=positions, means2D=torch.empty_like(positions), shs=gaussians.get_features, opacities=gaussians.get_opacities,
-                              cov3D_precomp=covariances, tile_rows=band)
+        image, _, *aux = rasterizer(means3D=positions, means2D=torch.empty_like(positions), shs=gaussians.get_features, opacities=gaussians.get_opacities,
+                                    cov3D_precomp=covariances, tile_rows=band, return_depth_alpha=depth_alpha)
     else:
-        image, _ = rasterizer(means3D=positions, means2D=torch.empty_like(positions), shs=gaussians.get_features,
-                              opacities=gaussians.get_opacities, scales=gaussians.get_scales, rotations=gaussians.get_rotations, tile_rows=band)
+        image, _, *aux = rasterizer(means3D=positions, means2D=torch.empty_like(positions), shs=gaussians.get_features,
+                                    opacities=gaussians.get_opacities, scales=gaussians.get_scales, rotations=gaussians.get_rotations, tile_rows=band,
+                                    return_depth_alpha=depth_alpha)
     image.clamp_(0.0, 1.0)
-    return {'rgb': image if to_chw else image.permute(1, 2, 0)}
+    outputs = {'rgb': image if to_chw else image.permute(1, 2, 0)}
+    if depth_alpha:
+        outputs.update(_depth_alpha_outputs(aux[0], aux[1], to_chw))
+    return outputs
 
 
 FUSED_PHOTOMETRIC_LOSS = True   # training_loss as one node (nerficg_amd.fused_ssim.photometric_loss); False: l1_loss + fused_ssim as tensor operations
