@@ -107,6 +107,9 @@ def test_ingp_bench_pose_central_crop_matches_the_oracle():
     assert alpha.max() > 0.3 and alpha.std() > 0.005 and col.std() > 0.005  # the crop is not a flat picture
     assert np.abs(got_rgb - col).max() <= 2e-3 and np.abs(got_rgb - col).mean() <= 2e-4
     assert np.abs(got_alpha - alpha).max() <= 2e-3
+    from tests.test_gpu_render_parity import assert_depth_follows_the_oracle
+    depth = np.where(Tr < 1, depth / np.where(alpha > 0, alpha, 1), 0)       # the inference finalisation (Renderer.py:137)
+    assert_depth_follows_the_oracle(out['depth'].cpu().numpy()[pix], depth, alpha, 2e-3, float(ts.max()))
 
 
 # ------------------------------------------------------------------------------------------------ raymarching_test quirk path

@@ -56,7 +56,8 @@ def inside_pose(theta, phi, radius=1.15):
 
 def oracle_image(model, cam, c2w, esf, max_samples=1024, rays=None):
     """CPU composition: box test -> near / far clamp -> march -> query -> composite with the early-out -> finalise.  Rays: independent numpy
-    rays (scenes.numpy_rays) unless `rays` = (origin, view_direction) is given."""
+    rays (scenes.numpy_rays) unless `rays` = (origin, view_direction) is given.  Returns colour, alpha, per-ray counts, positions, steps, the
+    inference depth (Renderer.py:137) and the largest t of the march."""
     w, h = cam.width, cam.height
     if rays is None:
         o, _, d = scenes.numpy_rays(w, h, c2w, cam.focal_x, cam.focal_y, cam.center_x, cam.center_y)
@@ -83,7 +84,8 @@ def oracle_image(model, cam, c2w, esf, max_samples=1024, rays=None):
     col = np.clip(col + Tr[:, None] * cam.background_color.numpy()[None], 0, 1)
     cnt = np.zeros(len(o), np.int64)
     cnt[rays_a[:, 0]] = rays_a[:, 2]
-    return col, alpha, cnt, xyzs, deltas
+    depth = np.where(Tr < 1, depth / np.where(alpha > 0, alpha, 1), 0)
+    return col, alpha, cnt, xyzs, deltas, depth, float(ts.max())
 
 
 def _ray_counts(renderer, cam):
@@ -138,14 +140,14 @@ def test_fused_image_three_cascades_against_the_oracle(exponential, table_amp):
         cnt_single = _ray_counts(renderer, cam)
         layered = renderer.render_image_fused(cam, pose, return_stats=True, early_termination=True)
         cnt_layered = _ray_counts(renderer, cam)
-        col, alpha, cnt, xyzs, deltas = oracle_image(model, cam, pose, esf)
+        col, alpha, cnt, xyzs, deltas, depth, t_far = oracle_image(model, cam, pose, esf)
         assert np.array_equal(cnt_single, cnt_layered) and single['n_samples'] == layered['n_samples'] == int(cnt_single.sum())
         for k in ('rgb', 'alpha', 'depth'):                 # same per-ray arithmetic in both orders
             assert torch.equal(single[k], layered[k]), k
         # (1) index parity of the march itself: the oracle fed with the rays of the device generator (the same ray table the fused kernels
         #     build) marches EXACTLY the same number of samples on every ray
         hip = generate_rays(w, h, cam.focal_x, cam.focal_y, cam.center_x, cam.center_y, pose, want_direction=False)
-        _, _, cnt_same_rays, _, _ = oracle_image(model, cam, pose, esf, rays=(hip['origin'].cpu().numpy(), hip['view_direction'].cpu().numpy()))
+        _, _, cnt_same_rays, _, _, _, _ = oracle_image(model, cam, pose, esf, rays=(hip['origin'].cpu().numpy(), hip['view_direction'].cpu().numpy()))
         np.testing.assert_array_equal(cnt_single, cnt_same_rays)
         # (2) the whole composition on INDEPENDENT rays: two ray generators agree to an ulp, not to the bit (the reference's CPU and device
         #     generators do not either, test_generate_rays_vs_reference_golden), and an ulp can move an isolated ray across a cell face: at most
@@ -160,6 +162,8 @@ def test_fused_image_three_cascades_against_the_oracle(exponential, table_amp):
         tol = 2e-3 if table_amp <= 10 else 5e-3
         assert err[~off].max() <= tol and err.mean() <= 2e-4 and err.max() <= 2e-2, (err[~off].max(), err.mean(), err.max())
         assert np.abs(got_alpha - alpha)[~off].max() <= 2e-3
+        from tests.test_gpu_render_parity import assert_depth_follows_the_oracle
+        assert_depth_follows_the_oracle(single['depth'].cpu().numpy(), depth, alpha, 2e-3, t_far, where=~off)
         # the frame exercises what it is meant to: samples in all three cascades' regions, a picture that is not flat
         r = np.abs(xyzs).max(axis=1)
         assert (r < 0.5).any() and ((r >= 0.5) & (r < 1.0)).any() and (r >= 1.0).any()

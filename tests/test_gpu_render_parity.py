@@ -45,8 +45,9 @@ def setup():
     return model, InstantNGPRenderer(model)
 
 
-def _oracle_image(model, cam, c2w):
-    """march all -> query all -> composite with early-out -> finalise, on the CPU oracle (same sample set as the chunked loop)."""
+def _oracle_image(model, cam, c2w, with_t_far=False):
+    """march all -> query all -> composite with early-out -> finalise, on the CPU oracle (same sample set as the chunked loop).
+    with_t_far: the largest t of the march as a fifth value."""
     w, h = cam.width, cam.height
     from nerficg_amd.raygen import generate_rays
     rays = generate_rays(w, h, cam.focal_x, cam.focal_y, cam.center_x, cam.center_y, c2w, want_direction=False)
@@ -68,7 +69,23 @@ def _oracle_image(model, cam, c2w):
     T = 1 - alpha
     col = np.clip(col + T[:, None] * cam.background_color.numpy()[None], 0, 1)
     depth = np.where(T < 1, depth / np.where(alpha > 0, alpha, 1), 0)
+    if with_t_far:
+        return col, alpha, depth, int(counter[0]), float(ts.max())
     return col, alpha, depth, int(counter[0])
+
+
+def assert_depth_follows_the_oracle(depth, o_depth, o_alpha, eps_alpha, t_far, where=None):
+    """The inference depth (weighted mean, Renderer.py:137) against the oracle's, with the bound that follows from the alpha tolerance the
+    calling test already states: the weights differ by eps_alpha in sum at most, so the depth sum by eps_alpha * t_far and the quotient by
+    eps_alpha * (t_far + depth_ref) / alpha_ref -- applied where alpha_ref >= 0.05; and depth is exactly 0 wherever the oracle hit nothing."""
+    depth, o_depth, o_alpha = np.asarray(depth, np.float64), np.asarray(o_depth, np.float64), np.asarray(o_alpha, np.float64)
+    where = np.ones(depth.shape, bool) if where is None else where
+    assert (depth[where & (o_alpha == 0)] == 0).all()
+    m = where & (o_alpha >= 0.05)
+    assert m.sum() > 100
+    bound = eps_alpha * (t_far + o_depth[m]) / o_alpha[m]
+    err = np.abs(depth[m] - o_depth[m])
+    assert (err <= bound).all(), (float((err / bound).max()), int((err > bound).sum()))
 
 
 @pytest.mark.parametrize('w,h,pose', [(96, 80, (0.7, 0.4)), (64, 64, (2.9, -0.6))])
@@ -80,7 +97,7 @@ def test_fused_image_equals_ray_list_image_and_oracle(setup, w, h, pose):
     rays = generate_rays(w, h, cam.focal_x, cam.focal_y, cam.center_x, cam.center_y, c2w, want_direction=False)
     ref = renderer.render_rays(rays['origin'], rays['view_direction'], cam)  # ray-major ops on explicit ray tensors
     fused = renderer.render_image_fused(cam, c2w, return_stats=True)
-    o_rgb, o_alpha, o_depth, o_total = _oracle_image(model, cam, c2w)
+    o_rgb, o_alpha, o_depth, o_total, t_far = _oracle_image(model, cam, c2w, with_t_far=True)
     assert fused['n_samples'] == o_total  # bit-exact sample set (index parity)
     for name, a, b, tol in (('rgb', fused['rgb'], ref['rgb'].reshape(-1, 3), 2e-3), ('alpha', fused['alpha'], ref['alpha'].reshape(-1), 1e-3)):
         diff = (a - b).abs()
@@ -92,6 +109,7 @@ def test_fused_image_equals_ray_list_image_and_oracle(setup, w, h, pose):
     np.testing.assert_allclose(fused['rgb'].cpu().numpy(), o_rgb, rtol=0, atol=2e-3)
     np.testing.assert_allclose(fused['alpha'].cpu().numpy(), o_alpha, rtol=0, atol=1e-3)
     assert np.abs(fused['rgb'].cpu().numpy() - o_rgb).mean() <= 2e-4
+    assert_depth_follows_the_oracle(fused['depth'].cpu().numpy(), o_depth, o_alpha, 1e-3, t_far)
     # the scene is not trivial: some pixels hit, some miss, alpha varies
     assert 0.2 < hit.float().mean().item() < 0.8 and fused['alpha'].std().item() > 0.05
 
