@@ -35,8 +35,9 @@ enum {
  * nrc_photometric_loss_* are new; 5 = round 5: group 13 (the fused InstantNGP training iteration) is new; nrc_ngp_train_query_forward gained
  * n_samples_dev (NULL = every row, as before); 7 = the band entry points of group 4 (nrc_gs_*_band: one frame rendered and differentiated as bands of tile
  * rows) are new, every earlier signature is unchanged; 8 = nrc_gs_bin_render_aux_band / nrc_gs_backward_aux_band (group 4: differentiable depth and alpha maps
- * beside the colour) are new, float [3].w of a splat record carries the view-space depth, slot [9] of a gradient record dL/dz; every earlier signature is unchanged. */
-#define NRC_ABI_VERSION 8
+ * beside the colour) are new, float [3].w of a splat record carries the view-space depth, slot [9] of a gradient record dL/dz; every earlier signature is unchanged;
+ * 9 = group 15 (nrc_map_losses_*: the depth-smoothness and alpha-entropy losses on the rasterizer's maps) is new, every earlier signature is unchanged. */
+#define NRC_ABI_VERSION 9
 /* library identification; also used by the loader's symbol check */
 int nrc_abi_version(void);
 const char* nrc_build_info(void);
@@ -871,6 +872,33 @@ int nrc_amp_adam_slices(float* param_a, const float* grad_a, float* exp_avg_a, f
                         int64_t l2_count_a, float* param_b, const float* grad_b, float* exp_avg_b, float* exp_avg_sq_b, void* param_f16_b, int64_t n_b,
                         float l2_coeff_b, int64_t l2_count_b, float lr, const float* lr_dev, float beta1, float beta2, float eps, float weight_decay,
                         int32_t adam_w_mode, const float* bias_corrections, const float* state4, nrc_stream_t stream);
+
+/* =====================================================================================================
+ * Group 15 -- the regularisers on the 3DGS depth and alpha maps as three launches: replaces depth_smoothness_loss
+ *            (src/Optim/Losses/DepthSmoothness.py:31-43), background_entropy (src/Optim/Losses/BackgroundEntropy.py:6-8) and the
+ *            depth / (alpha + 1e-6) normalisation in front of them (InstantNGP/Renderer.py:82), ~30 tensor operations forward and as many backward.
+ *            All f32, contiguous: depth (B, H, W) -- the rasterizer's accumulated depth sum w z, or any depth map --, alpha (B, H, W),
+ *            image (B, C, H, W), 1 <= C <= 4.
+ *              d = normalize ? depth / (alpha + 1e-6f) : depth;   lap_x = d[x-1] + d[x+1] - 2 d[x], x in [1, W-2];   w_x = exp(-mean_c |I_c[x] - I_c[x-1]|);
+ *              S_x = mean over B H (W-2) of |lap_x w_x|, S_y the same along y over B (H-2) W;   a = clamp(alpha, 1e-6f, 1 - 1e-6f) (the bounds as f32);
+ *              E = mean(-a log a), with symmetrical mean(-a log a - (1-a) log(1-a));   loss = lambda_smooth (S_x + S_y) + lambda_entropy E.
+ *   _forward : a stencil launch writes per-workgroup partial sums (no atomics), one workgroup adds them in a fixed order with double accumulators:
+ *              loss4 (DEVICE float[4]) = {loss, S_x, S_y, E}, bit-identical from call to call.  workspace: nrc_map_losses_ws_floats(B, H, W) floats,
+ *              16-byte aligned.
+ *   _backward: one stencil launch, a gather (no atomics).  dL_ddepth (B,H,W), dL_dalpha (B,H,W), dL_dimage (B,C,H,W): each is written when its pointer
+ *              is non-null (at least one must be).  dL_dalpha = the normalisation's -g_d depth / (alpha + 1e-6)^2 (with normalize) + the entropy term (zero
+ *              outside the clamp, passed at the bounds like torch.clamp); sign(0) = 0 throughout.  upstream_dev: the gradient of the loss VALUE, a DEVICE
+ *              scalar (NULL: 1), as for nrc_photometric_loss_backward.
+ *   A weight of zero skips that term's work: lambda_smooth == 0 allows depth == image == NULL (and writes neither dL_ddepth nor dL_dimage),
+ *   lambda_entropy == 0 skips the entropy.  NRC_ERR_INVALID before any HIP call: a null required pointer, B < 1 (or > 65535), C outside 1..4, H < 3 or
+ *   W < 3 (the reference's mean over an empty set is NaN there), both weights zero.
+ * ===================================================================================================== */
+int64_t nrc_map_losses_ws_floats(int64_t B, int32_t H, int32_t W);
+int nrc_map_losses_forward(const float* depth, const float* alpha, const float* image, int64_t B, int32_t C, int32_t H, int32_t W, int32_t normalize,
+                           float lambda_smooth, float lambda_entropy, int32_t symmetrical, float* workspace, float* loss4, nrc_stream_t stream);
+int nrc_map_losses_backward(const float* depth, const float* alpha, const float* image, int64_t B, int32_t C, int32_t H, int32_t W, int32_t normalize,
+                            float lambda_smooth, float lambda_entropy, int32_t symmetrical, const float* upstream_dev, float* dL_ddepth, float* dL_dalpha,
+                            float* dL_dimage, nrc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -561,14 +561,33 @@ def render_image_inference(gaussians: Gaussians, cam: PerspectiveCamera, c2w: np
 FUSED_PHOTOMETRIC_LOSS = True   # training_loss as one node (nerficg_amd.fused_ssim.photometric_loss); False: l1_loss + fused_ssim as tensor operations
 
 
-def training_loss(image: torch.Tensor, target: torch.Tensor, lambda_l1: float = 0.8, lambda_dssim: float = 0.2) -> torch.Tensor:
+def training_loss(image: torch.Tensor, target: torch.Tensor, lambda_l1: float = 0.8, lambda_dssim: float = 0.2, depth: torch.Tensor | None = None,
+                  alpha: torch.Tensor | None = None, lambda_smooth: float = 0.0, lambda_entropy: float = 0.0, entropy_symmetrical: bool = False) -> torch.Tensor:
     """GaussianSplattingLoss (src/Methods/GaussianSplatting/Loss.py:11-23, weights Trainer.py:34-35): lambda_l1 * L1 + lambda_dssim *
-    (1 - SSIM) on (3, H, W) images, SSIM through the HIP kernels (nerficg_amd.fused_ssim; DSSIM.py:11-18 adds the batch dimension)."""
+    (1 - SSIM) on (3, H, W) images, SSIM through the HIP kernels (nerficg_amd.fused_ssim; DSSIM.py:11-18 adds the batch dimension).
+
+    lambda_smooth / lambda_entropy (both 0 by default: the photometric loss alone, unchanged) add the map regularisers of nerficg_amd.map_losses as one more
+    node: lambda_smooth * depth_smoothness_loss(depth / (alpha + 1e-6), image) + lambda_entropy * background_entropy(alpha, entropy_symmetrical)
+    (src/Optim/Losses/DepthSmoothness.py:31-43, BackgroundEntropy.py:6-8).  `depth` is the rasterizer's ACCUMULATED depth (sum w z), NOT the normalised
+    'depth' of render_image_training(..., depth_alpha=True): the kernel divides by alpha + 1e-6 itself, so the normalisation costs no launch and its
+    gradient reaches both maps.  The raw maps come from the rasterizer call:
+
+        image, radii, depth_sum, alpha = rasterizer(means3D=..., ..., return_depth_alpha=True)        # (3, H, W), (P,), (H, W), (H, W)
+        loss = training_loss(image, target, depth=depth_sum, alpha=alpha, lambda_smooth=0.1, lambda_entropy=0.01)
+
+    The image gradient of the smoothness weights flows into `image` as in the reference.  CPU tensors and other dtypes take the tensor formula."""
     from .fused_ssim import fused_ssim, photometric_loss
     a = image[None] if image.dim() == 3 else image
     b = target[None] if target.dim() == 3 else target
     if FUSED_PHOTOMETRIC_LOSS and a.is_cuda and a.dtype == torch.float32 and b.dtype == torch.float32 and a.dim() == 4 and a.shape == b.shape:
         # one autograd node, three launches (stencil + reduction, stencil) instead of ~22 tensor operations around the SSIM kernels
-        return photometric_loss(a.contiguous(), b.contiguous(), lambda_l1, lambda_dssim)
-    l1 = torch.nn.functional.l1_loss(image, target)
-    return lambda_l1 * l1 + lambda_dssim * (1.0 - fused_ssim(a, b))
+        loss = photometric_loss(a.contiguous(), b.contiguous(), lambda_l1, lambda_dssim)
+    else:
+        l1 = torch.nn.functional.l1_loss(image, target)
+        loss = lambda_l1 * l1 + lambda_dssim * (1.0 - fused_ssim(a, b))
+    if lambda_smooth == 0.0 and lambda_entropy == 0.0:
+        return loss
+    from .map_losses import map_regularizer
+    if alpha is None or (lambda_smooth != 0.0 and depth is None):
+        raise RuntimeError('training_loss: lambda_smooth needs depth= and alpha= (the rasterizer\'s return_depth_alpha maps), lambda_entropy needs alpha=')
+    return loss + map_regularizer(depth, alpha, a, lambda_smooth, lambda_entropy, normalize=True, symmetrical=entropy_symmetrical)
