@@ -36,8 +36,9 @@ enum {
  * n_samples_dev (NULL = every row, as before); 7 = the band entry points of group 4 (nrc_gs_*_band: one frame rendered and differentiated as bands of tile
  * rows) are new, every earlier signature is unchanged; 8 = nrc_gs_bin_render_aux_band / nrc_gs_backward_aux_band (group 4: differentiable depth and alpha maps
  * beside the colour) are new, float [3].w of a splat record carries the view-space depth, slot [9] of a gradient record dL/dz; every earlier signature is unchanged;
- * 9 = group 15 (nrc_map_losses_*: the depth-smoothness and alpha-entropy losses on the rasterizer's maps) is new, every earlier signature is unchanged. */
-#define NRC_ABI_VERSION 9
+ * 9 = group 15 (nrc_map_losses_*: the depth-smoothness and alpha-entropy losses on the rasterizer's maps) is new, every earlier signature is unchanged;
+ * 10 = nrc_ngp_set_encoder_xcd_run (group 6) is new, every earlier signature is unchanged. */
+#define NRC_ABI_VERSION 10
 /* library identification; also used by the loader's symbol check */
 int nrc_abi_version(void);
 const char* nrc_build_info(void);
@@ -546,6 +547,12 @@ int nrc_ngp_render_layers(const float* ts, int32_t* row_tile, const float* ray_o
  * Both < 0: back to the default.  A setting of the CALLING HOST THREAD, read when that thread launches the encoder (set it on the thread that
  * enqueues the frame); the features are identical for every shape. */
 int nrc_ngp_set_encoder_shape(int32_t log2_x, int32_t log2_y);
+/* k_grid_encode deals its workgroups to the 8 XCDs in runs: inside a run of 8 * `workgroups` workgroups every XCD takes `workgroups` consecutive ones, so
+ * that the XCDs work inside the same part of the frame at the same time (what is left behind the last whole run is split in eight the same way).
+ * 0: the library's default (a compile-time constant, the measured best).  A positive multiple of 4 (blocks of 1024 slots stay whole); anything else is
+ * refused.  A setting of the CALLING HOST THREAD like the shape above; the features are identical for every value -- it exists so that tests reach run
+ * boundaries with small frames, the renderer does not call it. */
+int nrc_ngp_set_encoder_xcd_run(int32_t workgroups);
 int nrc_ngp_encode_samples(const float* ts, const int32_t* row_tile, const float* ray_od, int64_t first_row, int64_t n_rows, const float* xyz_min3,
                            const float* xyz_size3, const void* table_f16, int32_t n_levels, int32_t log2_hashmap_size,
                            int32_t base_resolution, float per_level_scale, void* features_f16, const int32_t* arena_tile_off,

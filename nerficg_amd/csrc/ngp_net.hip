@@ -327,13 +327,22 @@ __device__ __forceinline__ void fetch_dir(const QueryIn& in, int64_t i, float& d
 // channels (measured: 0.262 ms vs 0.22 ms per 2 Mi samples).  One lane per sample, all 16 levels.
 template <int SRC>
 __global__ void __launch_bounds__(256) k_grid_encode(QueryIn in, int64_t base, int64_t n, const __half2* __restrict__ table, GridCfg g,
-                                                         uint4* __restrict__ feat, int narrow_levels, int lvl_range, int lane_shape = 0) {
+                                                         uint4* __restrict__ feat, int narrow_levels, int lvl_range, int lane_shape = 0, int xcd_run = 0) {
     int64_t bid = blockIdx.x;
     if constexpr (SRC == SRC_TILED) {
-        // workgroups are dealt round-robin over the 8 XCDs; each XCD takes a CONTIGUOUS eighth of the launch's slots instead of every eighth
-        // workgroup, so that neighbouring bricks (which share table lines) meet in the same L2.  Measured: 612 -> 591 us per launch (mean of 24 poses)
-        const int64_t g8 = (int64_t)gridDim.x >> 3;
-        if (bid < 8 * g8) bid = (bid & 7) * g8 + (bid >> 3);
+        // workgroups are dealt round-robin over the 8 XCDs; each XCD takes a CONTIGUOUS eighth of a range of slots instead of every eighth
+        // workgroup, so that neighbouring bricks (which share table lines) meet in the same L2.  Measured: 612 -> 591 us per launch (mean of 24 poses).
+        // The range is a RUN of 8 * xcd_run workgroups (xcd_run = 0: the whole launch): the eight XCDs then work inside the same run of the
+        // frame at the same time, as they did when the frame was encoded in launches of 8 Mi slots (NRC_ENC_XCD_RUN).  What is left behind the last
+        // whole run is split the same way, and the last < 8 workgroups of a range stay where they are.
+        int64_t first = 0, span = gridDim.x;
+        if (xcd_run > 0) {
+            const int64_t run = 8 * (int64_t)xcd_run;
+            first = bid / run * run;
+            span = first + run <= (int64_t)gridDim.x ? run : (int64_t)gridDim.x - first;
+        }
+        const int64_t g8 = span >> 3, r = bid - first;
+        if (r < 8 * g8) bid = first + (r & 7) * g8 + (r >> 3);
     }
     int64_t j = bid * 256 + threadIdx.x;
     bool remapped = false;
@@ -808,7 +817,8 @@ __global__ void __launch_bounds__(1024) k_tile_chunks(const int32_t* __restrict_
     const int c = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid < 2) {   // first tile whose first row is >= the bound (tile_off ascends); the last chunk ends at n_tiles
         int64_t lo = 0, hi = n_tiles;
-        if (tid == 1 && c + 1 == (int)gridDim.x) lo = n_tiles;
+        if (gridDim.x == 1) lo = tid ? n_tiles : 0;   // one chunk = the whole frame: no search (20 dependent loads: 3 of the kernel's 17 us)
+        else if (tid == 1 && c + 1 == (int)gridDim.x) lo = n_tiles;
         else {
             const int64_t bound = (int64_t)(c + tid) * span;
             while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if ((int64_t)tile_off[mid] < bound) lo = mid + 1; else hi = mid; }
@@ -980,6 +990,11 @@ static int64_t query_feat_bytes(int64_t M) {
 
 static thread_local int g_enc_shape_override = 0;   // nrc_ngp_set_encoder_shape: (log2 pixels along x) << 4 | (log2 pixels along y) of a wave's brick, 0 = the default;
                                                     // per host thread: the renderer sets it and enqueues the frame from the same thread
+// nrc_ngp_set_encoder_xcd_run: workgroups per XCD and run of k_grid_encode<SRC_TILED>, 0 = NRC_ENC_XCD_RUN; per host thread like the shape
+#ifndef NRC_ENC_XCD_RUN
+#define NRC_ENC_XCD_RUN 4096   // measured: the whole launch (0), 4096, 1024, 256 -- LABBOOK R11.  A multiple of 4: blocks of 1024 slots stay whole
+#endif
+static thread_local int g_enc_xcd_run_override = 0;
 template <int SRC>
 static void launch_encode(const QueryIn& in, int64_t base, int64_t n, const void* table, const GridCfg& g, uint4* feat, hipStream_t s) {
     // levels whose cells are larger than a wave's footprint: narrow gathers (see grid_level_features_narrow)
@@ -1008,7 +1023,7 @@ static void launch_encode(const QueryIn& in, int64_t base, int64_t n, const void
     const int lane_shape = (3 << 4) | 1;
     const int lanes = (SRC == SRC_TILED && (base & 1023) == 0) ? (g_enc_shape_override ? g_enc_shape_override : lane_shape) : 0;
     hipLaunchKernelGGL(k_grid_encode<SRC>, dim3((unsigned)(lanes ? 4 * nrc_cdiv(n, 1024) : nrc_cdiv(n, 256)), rows), dim3(256), 0, s, in, base, n, (const __half2*)table, g, feat,
-                       narrow, lvl_range, lanes);
+                       narrow, lvl_range, lanes, g_enc_xcd_run_override ? g_enc_xcd_run_override : NRC_ENC_XCD_RUN);
 }
 
 template <int SRC>
@@ -1150,6 +1165,11 @@ int nrc_ngp_set_encoder_shape(int32_t log2_x, int32_t log2_y) {
     if (log2_x < 0 && log2_y < 0) { g_enc_shape_override = 0; return NRC_OK; }
     if (log2_x < 0 || log2_x > NRC_TILE_W_LOG2 || log2_y < 0 || log2_y > 6 - NRC_TILE_W_LOG2 || log2_x + log2_y < 2 || log2_x + log2_y == 6) return NRC_ERR_INVALID;
     g_enc_shape_override = (log2_x << 4) | log2_y;
+    return NRC_OK;
+}
+int nrc_ngp_set_encoder_xcd_run(int32_t workgroups) {
+    if (workgroups < 0 || (workgroups & 3) != 0 || workgroups > (1 << 24)) return NRC_ERR_INVALID;
+    g_enc_xcd_run_override = workgroups;
     return NRC_OK;
 }
 int nrc_ngp_encode_samples(const float* ts, const int32_t* row_tile, const float* ray_od, int64_t first_row, int64_t n_rows, const float* xyz_min3,
