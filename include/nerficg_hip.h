@@ -37,8 +37,10 @@ enum {
  * rows) are new, every earlier signature is unchanged; 8 = nrc_gs_bin_render_aux_band / nrc_gs_backward_aux_band (group 4: differentiable depth and alpha maps
  * beside the colour) are new, float [3].w of a splat record carries the view-space depth, slot [9] of a gradient record dL/dz; every earlier signature is unchanged;
  * 9 = group 15 (nrc_map_losses_*: the depth-smoothness and alpha-entropy losses on the rasterizer's maps) is new, every earlier signature is unchanged;
- * 10 = nrc_ngp_set_encoder_xcd_run (group 6) is new, every earlier signature is unchanged. */
-#define NRC_ABI_VERSION 10
+ * 10 = nrc_ngp_set_encoder_xcd_run (group 6) is new, every earlier signature is unchanged;
+ * 11 = nrc_ngp_set_encoder_block_levels / _block_view, nrc_ngp_block_view_bytes, nrc_ngp_build_block_view (group 6: the cell-block view of the dense
+ * levels) are new, every earlier signature is unchanged. */
+#define NRC_ABI_VERSION 11
 /* library identification; also used by the loader's symbol check */
 int nrc_abi_version(void);
 const char* nrc_build_info(void);
@@ -537,7 +539,9 @@ int nrc_ngp_render_layers(const float* ts, int32_t* row_tile, const float* ray_o
                           int32_t cascades, float exp_step_factor, int32_t grid_size, int32_t max_samples, float T_threshold,
                           const float* bg3_host, void* packed_f16, float* rgb, float* alpha, float* depth, int32_t* skipped_rows,
                           void* workspace, const int32_t* arena_row_k, int32_t arena_rows, nrc_stream_t stream);
-/* stage 3a on its own (the dominant kernel of the pipeline; used by bench.py's roofline leg): hash-grid features of the n_rows (<= 131072) rows
+/* stage 3a on its own (the dominant kernel of the pipeline; used by bench.py's roofline leg -- which sets no block view, see
+ * nrc_ngp_set_encoder_block_view below: its figure is the kernel with every level read from the table, ~3 % above the kernel as the frame runs it):
+ * hash-grid features of the n_rows (<= 131072) rows
  * first_row .. first_row + n_rows - 1 of the frame -- ts / row_tile are the FRAME's arrays, not offset ones (ABI 4) --, fragment-major: the 16-byte
  * vector [((j>>5)*4 + ((g + (j>>5))&3))*32 + (j&31)] = levels 4g..4g+3 (fp16x2) of slot j of the chunk.  arena_tile_off / arena_rows: as for
  * nrc_ngp_query_samples (NULL / 0: compact rows), so that the kernel is timed in the form the frame runs it */
@@ -553,6 +557,29 @@ int nrc_ngp_set_encoder_shape(int32_t log2_x, int32_t log2_y);
  * refused.  A setting of the CALLING HOST THREAD like the shape above; the features are identical for every value -- it exists so that tests reach run
  * boundaries with small frames, the renderer does not call it. */
 int nrc_ngp_set_encoder_xcd_run(int32_t workgroups);
+/* Cell-block view of the table's leading dense levels (at most 5, the levels in front of the first hashed one; 11.29 MB for the shipped grid): for
+ * every cell (gx, gy, gz) in [0, res]^3 of such a level one 32-byte record with the fp16 pairs of its eight corners (corner k: x + (k & 1),
+ * y + ((k >> 1) & 1), z + (k >> 2)), record gx + (res + 1) * (gy + (res + 1) * gz), the levels one behind the other.  The image encoder
+ * (k_grid_encode of the four entry points below) reads a sample's corners at these levels as two 16-byte loads of one address instead of eight
+ * gathers; the features are identical with and without the view for every sample inside the model box (normalised position in [0, 1]^3, cell
+ * in [0, res]^3).  A position outside it gets meaningless features either way, and not the same ones: the view clamps the cell coordinates to res,
+ * the table path wraps and clamps the linear index.
+ *   nrc_ngp_block_view_bytes  : size of the view of a grid (0: no level qualifies; < 0: an error code)
+ *   nrc_ngp_build_block_view  : fills `view` from table_f16 -- again whenever the table's VALUES change (one pass over the view)
+ *   nrc_ngp_set_encoder_block_view : hands the view of the table that the NEXT call of nrc_ngp_render_frame / _render_layers / _query_samples /
+ *       _encode_samples on the calling host thread is given.  That call takes it, whichever way it ends: a call without a view set in front of
+ *       it (or with NULL) reads the table at every level, and so does a grid whose level 0 is hashed.  The library cannot check whose view it is
+ *       given (no size, no identity): it must be the view of THAT call's table_f16, built since the table's values last changed.  A caller whose
+ *       entry-point call may not happen after the view was set (an exception in between) sets NULL again itself -- InstantNGPRenderer does, behind
+ *       every call -- or the next entry point on the thread, perhaps for another table, would take it.
+ *   nrc_ngp_set_encoder_block_levels : how many of the view's levels the encoder reads through it (0 .. 5; the levels a view does not hold are
+ *       read from the table whatever is asked for), -1: the library's default, the measured best.  A setting of the CALLING HOST THREAD like the
+ *       shape above; it exists for tests and measurements, the renderer does not call it. */
+int64_t nrc_ngp_block_view_bytes(int32_t n_levels, int32_t log2_hashmap_size, int32_t base_resolution, float per_level_scale);
+int nrc_ngp_build_block_view(const void* table_f16, int32_t n_levels, int32_t log2_hashmap_size, int32_t base_resolution, float per_level_scale,
+                             void* view, nrc_stream_t stream);
+int nrc_ngp_set_encoder_block_view(const void* view);
+int nrc_ngp_set_encoder_block_levels(int32_t levels);
 int nrc_ngp_encode_samples(const float* ts, const int32_t* row_tile, const float* ray_od, int64_t first_row, int64_t n_rows, const float* xyz_min3,
                            const float* xyz_size3, const void* table_f16, int32_t n_levels, int32_t log2_hashmap_size,
                            int32_t base_resolution, float per_level_scale, void* features_f16, const int32_t* arena_tile_off,

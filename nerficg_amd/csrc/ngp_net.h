@@ -32,6 +32,18 @@ struct GridCfg {
     float scale[NRC_MAX_LEVELS];
 };
 
+// Cell-block view of the leading dense levels (image encoder only): for every cell (gx, gy, gz) in [0, res]^3 of level l < levels one 32-byte record,
+// dword k = the fp16 pair of corner k in Corner8 order, record gx + (res + 1) * (gy + (res + 1) * gz) behind byte first[l] of the view.  Built from the
+// fp16 table by k_build_block_view whenever the table is refreshed; a lane reads its eight corners as two 16-byte loads of ONE address.
+#define NRC_ENC_BLOCK_MAX 5                   // levels a view holds at most: five dense levels of the shipped grid (16 .. 59) are 11.29 MB
+#define NRC_ENC_BLOCK_MAX_BYTES (64u << 20)   // ... and the view of any other grid stops in front of the level that would pass this
+struct BlockView {
+    const void* ptr;                        // nullptr: no view, every level reads the table
+    uint32_t bytes;
+    int32_t levels;                         // levels < this read the view
+    uint32_t first[NRC_ENC_BLOCK_MAX + 1];  // byte offset of the level's first record; [levels] = bytes
+};
+
 __device__ __forceinline__ f16v zero16() {
     f16v z;
 #pragma unroll
@@ -187,16 +199,24 @@ __device__ __forceinline__ void grid_corners(float px, float py, float pz, float
         c.e[k] = off + (hashed ? h : d);
     }
 }
+// The cell of a sample at one level and its eight trilinear weights in Corner8 order (corner k: x + (k & 1), y + ((k >> 1) & 1), z + (k >> 2)); the
+// one statement of both for grid_corners_u and for the levels that are read through the cell-block view (grid_level_features_block)
+__device__ __forceinline__ void grid_cell(float px, float py, float pz, float scale, uint32_t& gx, uint32_t& gy, uint32_t& gz, float (&w)[8]) {
+    const float fx = fmaf(scale, px, 0.5f), fy = fmaf(scale, py, 0.5f), fz = fmaf(scale, pz, 0.5f);
+    const float flx = floorf(fx), fly = floorf(fy), flz = floorf(fz);
+    gx = (uint32_t)(int32_t)flx; gy = (uint32_t)(int32_t)fly; gz = (uint32_t)(int32_t)flz;
+    const float wx1 = fx - flx, wy1 = fy - fly, wz1 = fz - flz;
+    const float wx0 = 1.f - wx1, wy0 = 1.f - wy1, wz0 = 1.f - wz1;
+    const float wxy[4] = {wx0 * wy0, wx1 * wy0, wx0 * wy1, wx1 * wy1};
+#pragma unroll
+    for (int k = 0; k < 8; k++) w[k] = wxy[k & 3] * ((k & 4) ? wz1 : wz0);
+}
 // Same corners when the level (hence `hashed`) is uniform over the wave: the index form is a template argument chosen by a
 // scalar branch, which halves the integer work per corner (k_grid_encode / k_grid_bwd are VALU co-limited: profiles/).
 template <bool HASHED>
 __device__ __forceinline__ void grid_corners_u(float px, float py, float pz, float scale, uint32_t res, uint32_t size, uint32_t off, Corner8& c) {
-    const float fx = fmaf(scale, px, 0.5f), fy = fmaf(scale, py, 0.5f), fz = fmaf(scale, pz, 0.5f);
-    const float flx = floorf(fx), fly = floorf(fy), flz = floorf(fz);
-    const uint32_t gx = (uint32_t)(int32_t)flx, gy = (uint32_t)(int32_t)fly, gz = (uint32_t)(int32_t)flz;
-    const float wx1 = fx - flx, wy1 = fy - fly, wz1 = fz - flz;
-    const float wx0 = 1.f - wx1, wy0 = 1.f - wy1, wz0 = 1.f - wz1;
-    const float wxy[4] = {wx0 * wy0, wx1 * wy0, wx0 * wy1, wx1 * wy1};
+    uint32_t gx, gy, gz;
+    grid_cell(px, py, pz, scale, gx, gy, gz, c.w);
     const uint32_t my = HASHED ? 2654435761u : res, mz = HASHED ? 805459861u : res * res;
     const uint32_t ty0 = gy * my, tz0 = gz * mz;
     const uint32_t ty[2] = {ty0, ty0 + my}, tz[2] = {tz0, tz0 + mz};
@@ -216,7 +236,6 @@ __device__ __forceinline__ void grid_corners_u(float px, float py, float pz, flo
                 e = e >= size ? e - size : e;
                 e = min(e, mask);
             }
-            c.w[k] = wxy[k & 3] * ((k & 4) ? wz1 : wz0);
             c.e[k] = off + e;
         }
     }
@@ -307,6 +326,25 @@ __device__ __forceinline__ void grid_level_features_narrow(__amdgpu_buffer_rsrc_
     f0 = 0.f; f1 = 0.f;
 #pragma unroll
     for (int k = 0; k < 8; k++) fma_half2(c.w[k], v[k], f0, f1);
+}
+
+// dense levels through the cell-block view (BlockView): the eight corners are a function of the cell alone, so the lane computes ONE record address
+// (no per-corner index, wrap, clamp or level offset -- about 50 of the narrow form's vector instructions) and fetches it with two 16-byte loads
+// (2 L1 lookups instead of 8).  Same fp16 values, same weights, same FMA order as the table forms: identical features for every position whose
+// cell lies in [0, res]^3 -- what positions in [0, 1]^3 (and a rounding beyond) never leave.  The level's first byte rides in the loads' scalar
+// offset.  A cell coordinate is clamped to `res`, so that the record stays inside the level whatever the position is; for such a position
+// OUTSIDE the box the table forms wrap the linear index at `size` and clamp it to `size - 1` instead, and the two give different (equally
+// meaningless) features.
+__device__ __forceinline__ void grid_level_features_block(__amdgpu_buffer_rsrc_t view, uint32_t first_byte, uint32_t gx, uint32_t gy, uint32_t gz,
+                                                          uint32_t res, const float (&w)[8], float& f0, float& f1) {
+    const uint32_t r1 = res + 1u;
+    const uint32_t rec = __umul24(__umul24(min(gz, res), r1) + min(gy, res), r1) + min(gx, res);
+    const auto lo = __builtin_amdgcn_raw_buffer_load_b128(view, rec << 5, first_byte, 0);
+    const auto hi = __builtin_amdgcn_raw_buffer_load_b128(view, rec << 5, first_byte + 16u, 0);
+    const uint32_t v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    f0 = 0.f; f1 = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; k++) fma_half2(w[k], v[k], f0, f1);
 }
 
 // ---- SH degree 4 (16 coefficients) of a direction in [-1,1]^3 ------------------------------------------------------

@@ -327,7 +327,8 @@ __device__ __forceinline__ void fetch_dir(const QueryIn& in, int64_t i, float& d
 // channels (measured: 0.262 ms vs 0.22 ms per 2 Mi samples).  One lane per sample, all 16 levels.
 template <int SRC>
 __global__ void __launch_bounds__(256) k_grid_encode(QueryIn in, int64_t base, int64_t n, const __half2* __restrict__ table, GridCfg g,
-                                                         uint4* __restrict__ feat, int narrow_levels, int lvl_range, int lane_shape = 0, int xcd_run = 0) {
+                                                         uint4* __restrict__ feat, int narrow_levels, int lvl_range, int lane_shape = 0, int xcd_run = 0,
+                                                         BlockView bv = BlockView{}) {
     int64_t bid = blockIdx.x;
     if constexpr (SRC == SRC_TILED) {
         // workgroups are dealt round-robin over the 8 XCDs; each XCD takes a CONTIGUOUS eighth of a range of slots instead of every eighth
@@ -384,6 +385,7 @@ __global__ void __launch_bounds__(256) k_grid_encode(QueryIn in, int64_t base, i
     if (state < 0) return;   // a row of a finished tile (slab order): the MLP kernel skips it too, nothing reads its features
     const bool live = state > 0;
     const __amdgpu_buffer_rsrc_t trs = make_table_rsrc(table, g.total_entries * 4u);
+    const __amdgpu_buffer_rsrc_t vrs = make_table_rsrc(bv.ptr, bv.bytes);   // (SRC_TILED: the cell-block view of levels < bv.levels, see BlockView)
     uint4* out = feat + ((j >> 5) * 4) * 32 + (j & 31);
     const int rot = (int)((j >> 5) & 3);
     const int lvl_lo = lvl_range & 0xff, lvl_hi = (lvl_range >> 8) & 0xff;   // NRC_ENC_LEVELS (measurement only; 0 .. 16 normally)
@@ -400,7 +402,11 @@ __global__ void __launch_bounds__(256) k_grid_encode(QueryIn in, int64_t base, i
                 if (level < lvl_lo || level >= lvl_hi) continue;   // scalar, wave-uniform
                 Corner8 c;
                 float f0, f1;
-                if (g.hashed[level]) {   // (the narrow levels are the leading dense ones: launch_encode)
+                if (SRC == SRC_TILED && level < bv.levels) {   // (scalar, like the branches below; the view's levels are leading dense ones: block_view_cfg)
+                    uint32_t gx, gy, gz;
+                    grid_cell(px, py, pz, g.scale[level], gx, gy, gz, c.w);
+                    grid_level_features_block(vrs, bv.first[level], gx, gy, gz, g.res[level], c.w, f0, f1);
+                } else if (g.hashed[level]) {   // (the narrow levels are the leading dense ones: launch_encode)
                     grid_corners_u<true>(px, py, pz, g.scale[level], g.res[level], g.size[level], g.offset[level], c);
                     grid_level_features_hashed(trs, c, f0, f1);
                 } else {
@@ -457,6 +463,22 @@ __global__ void __launch_bounds__(256) k_grid_encode_pairs(QueryIn in, int64_t n
         const int grp = level >> 2;
         out32[(((j >> 5) * 4 + ((grp + rot) & 3)) * 32 + (j & 31)) * 4 + (level & 3)] = *reinterpret_cast<const uint32_t*>(&h);
     }
+}
+
+// Fills the cell-block view (BlockView) from the fp16 table: one thread per record.  The eight entries are the ones grid_corners_u<false> names for a
+// position in the middle of the cell -- the index form, the wrap at `size` and the clamp to `size - 1` are the encoder's own, stated nowhere else.
+__global__ void __launch_bounds__(256) k_build_block_view(const uint32_t* __restrict__ table, GridCfg g, BlockView bv, uint4* __restrict__ view) {
+    const uint32_t rec = blockIdx.x * 256u + threadIdx.x;
+    if (rec >= bv.bytes / 32u) return;
+    int level = 0;
+    while (level + 1 < bv.levels && rec * 32u >= bv.first[level + 1]) level++;
+    const uint32_t r = rec - bv.first[level] / 32u, r1 = g.res[level] + 1u;
+    const uint32_t gx = r % r1, gy = r / r1 % r1, gz = r / (r1 * r1);
+    const float scale = g.scale[level];   // >= 1 (block_view_cfg): fmaf(scale, gx / scale, 0.5f) lies within a rounding of gx + 0.5
+    Corner8 c;
+    grid_corners_u<false>((float)gx / scale, (float)gy / scale, (float)gz / scale, scale, g.res[level], g.size[level], g.offset[level], c);
+    view[2 * rec] = make_uint4(table[c.e[0]], table[c.e[1]], table[c.e[2]], table[c.e[3]]);
+    view[2 * rec + 1] = make_uint4(table[c.e[4]], table[c.e[5]], table[c.e[6]], table[c.e[7]]);
 }
 
 // SH degree 4 of the ray direction as the colour net's k-step-0 B fragments, once per RAY of the tiled layout:
@@ -964,6 +986,23 @@ int make_grid_cfg(int n_levels, int log2_T, int base_res, float pls, GridCfg& g,
     return NRC_OK;
 }
 
+// The levels a cell-block view of this grid holds, and where: the leading dense levels, at most NRC_ENC_BLOCK_MAX of them, while the view stays below
+// NRC_ENC_BLOCK_MAX_BYTES.  (scale >= 1: the builder places its position by a division by the scale.)  bv.ptr stays null.
+void block_view_cfg(const GridCfg& g, int n_levels, BlockView& bv) {
+    bv = BlockView{};
+    uint64_t bytes = 0;
+    int l = 0;
+    for (; l < n_levels && l < NRC_ENC_BLOCK_MAX && !g.hashed[l] && g.scale[l] >= 1.f; l++) {
+        const uint64_t r1 = (uint64_t)g.res[l] + 1u, level_bytes = r1 * r1 * r1 * 32u;
+        if (bytes + level_bytes > NRC_ENC_BLOCK_MAX_BYTES) break;
+        bv.first[l] = (uint32_t)bytes;
+        bytes += level_bytes;
+    }
+    bv.levels = l;
+    bv.bytes = (uint32_t)bytes;
+    for (int k = l; k <= NRC_ENC_BLOCK_MAX; k++) bv.first[k] = (uint32_t)bytes;
+}
+
 int pick_blocks(int64_t M) {
     // every workgroup stages the network's weight fragments in LDS (24 KB) before its first tile: few workgroups with several tiles per wave beat
     // one tile per wave (cap on the number of workgroups: 512 below 1 Mi samples, 2 048 above)
@@ -995,8 +1034,32 @@ static thread_local int g_enc_shape_override = 0;   // nrc_ngp_set_encoder_shape
 #define NRC_ENC_XCD_RUN 4096   // measured: the whole launch (0), 4096, 1024, 256 -- LABBOOK R11.  A multiple of 4: blocks of 1024 slots stay whole
 #endif
 static thread_local int g_enc_xcd_run_override = 0;
+// The cell-block view of the table (BlockView).  nrc_ngp_set_encoder_block_view hands the view of the table that the calling thread's NEXT frame entry
+// point is given; that entry point takes it (take_block_view) and the setting is gone, so that a view never outlives the call it was set for -- an
+// entry point called without one reads the table at every level.  nrc_ngp_set_encoder_block_levels: how many of the view's levels are read there,
+// -1 = NRC_ENC_BLOCK_LEVELS; per host thread like the shape.
+#ifndef NRC_ENC_BLOCK_LEVELS
+#define NRC_ENC_BLOCK_LEVELS 5   // measured: 0, 2, 3, 4, 5 -- LABBOOK R12
+#endif
+static thread_local const void* g_enc_block_view = nullptr;
+static thread_local int g_enc_block_levels_override = -1;
+static const void* take_block_view() {   // first thing in the entry point: the setting is gone whichever way the call ends
+    const void* view = g_enc_block_view;
+    g_enc_block_view = nullptr;
+    return view;
+}
+static BlockView block_view_of(const void* view, const GridCfg& g, int n_levels) {
+    BlockView bv;
+    block_view_cfg(g, n_levels, bv);
+    const int want = g_enc_block_levels_override >= 0 ? g_enc_block_levels_override : NRC_ENC_BLOCK_LEVELS;
+    bv.ptr = view;
+    if (want < bv.levels) bv.levels = want;   // (the levels behind it stay in the view, unread)
+    if (!bv.ptr || bv.levels <= 0) { bv.ptr = nullptr; bv.levels = 0; }
+    return bv;
+}
 template <int SRC>
-static void launch_encode(const QueryIn& in, int64_t base, int64_t n, const void* table, const GridCfg& g, uint4* feat, hipStream_t s) {
+static void launch_encode(const QueryIn& in, int64_t base, int64_t n, const void* table, const GridCfg& g, uint4* feat, hipStream_t s,
+                          const BlockView& bv = BlockView{}) {
     // levels whose cells are larger than a wave's footprint: narrow gathers (see grid_level_features_narrow)
     int narrow = 0;
     while (narrow < NRC_MAX_LEVELS && !g.hashed[narrow] && g.size[narrow] > 8) narrow++;
@@ -1023,7 +1086,7 @@ static void launch_encode(const QueryIn& in, int64_t base, int64_t n, const void
     const int lane_shape = (3 << 4) | 1;
     const int lanes = (SRC == SRC_TILED && (base & 1023) == 0) ? (g_enc_shape_override ? g_enc_shape_override : lane_shape) : 0;
     hipLaunchKernelGGL(k_grid_encode<SRC>, dim3((unsigned)(lanes ? 4 * nrc_cdiv(n, 1024) : nrc_cdiv(n, 256)), rows), dim3(256), 0, s, in, base, n, (const __half2*)table, g, feat,
-                       narrow, lvl_range, lanes, g_enc_xcd_run_override ? g_enc_xcd_run_override : NRC_ENC_XCD_RUN);
+                       narrow, lvl_range, lanes, g_enc_xcd_run_override ? g_enc_xcd_run_override : NRC_ENC_XCD_RUN, bv);
 }
 
 template <int SRC>
@@ -1037,7 +1100,7 @@ static void launch_mlp(const QueryIn& in, int64_t base, int64_t n, const void* f
 // feature buffers -- 11.27 ms per image against 10.99 ms in one stream; the encode grid fills every CU, the MLP blocks only queue.)
 template <int SRC>
 static int run_query(const QueryIn& in, int64_t M, int64_t n_ray_tiles, const void* wd, const void* wc, const void* table, const GridCfg& g,
-                     float* sigmas, float* rgbs, void* packed, void* workspace, hipStream_t s) {
+                     float* sigmas, float* rgbs, void* packed, void* workspace, hipStream_t s, const BlockView& bv = BlockView{}) {
     uint4* feat = (uint4*)workspace;
     h8* ray_sh = (h8*)((char*)workspace + query_feat_bytes(M));
     if constexpr (SRC == SRC_TILED)
@@ -1046,7 +1109,7 @@ static int run_query(const QueryIn& in, int64_t M, int64_t n_ray_tiles, const vo
     NRC_STAGE(s, nullptr);      // (armed stage timer: the two kernels of every chunk IN the frame's own sequence -- bench.py's in-frame ruler)
     for (int64_t base = 0; base < M; base += NRC_QUERY_CHUNK) {
         const int64_t n = (M - base) < NRC_QUERY_CHUNK ? (M - base) : NRC_QUERY_CHUNK;
-        launch_encode<SRC>(in, base, n, table, g, feat, s);
+        launch_encode<SRC>(in, base, n, table, g, feat, s, bv);
         NRC_STAGE(s, "k_grid_encode");
         launch_mlp<SRC>(in, base, n, feat, ray_sh, wd, wc, sigmas, rgbs, packed, s);
         NRC_STAGE(s, "k_ngp_mlp");
@@ -1172,11 +1235,44 @@ int nrc_ngp_set_encoder_xcd_run(int32_t workgroups) {
     g_enc_xcd_run_override = workgroups;
     return NRC_OK;
 }
+int nrc_ngp_set_encoder_block_levels(int32_t levels) {
+    if (levels < -1 || levels > NRC_ENC_BLOCK_MAX) return NRC_ERR_INVALID;
+    g_enc_block_levels_override = levels;
+    return NRC_OK;
+}
+int nrc_ngp_set_encoder_block_view(const void* view) {
+    g_enc_block_view = view;
+    return NRC_OK;
+}
+int64_t nrc_ngp_block_view_bytes(int32_t n_levels, int32_t log2_hashmap_size, int32_t base_resolution, float per_level_scale) {
+    GridCfg g;
+    const int rc = make_grid_cfg(n_levels, log2_hashmap_size, base_resolution, per_level_scale, g, nullptr);
+    if (rc != NRC_OK) return rc;
+    BlockView bv;
+    block_view_cfg(g, n_levels, bv);
+    return (int64_t)bv.bytes;
+}
+int nrc_ngp_build_block_view(const void* table_f16, int32_t n_levels, int32_t log2_hashmap_size, int32_t base_resolution, float per_level_scale,
+                             void* view, nrc_stream_t stream) {
+    NRC_ENTER();
+    GridCfg g;
+    const int rc = make_grid_cfg(n_levels, log2_hashmap_size, base_resolution, per_level_scale, g, nullptr);
+    if (rc != NRC_OK) return rc;
+    BlockView bv;
+    block_view_cfg(g, n_levels, bv);
+    if (bv.bytes == 0) return NRC_OK;
+    if (!table_f16 || !view) return NRC_ERR_INVALID;
+    hipLaunchKernelGGL(k_build_block_view, dim3((unsigned)nrc_cdiv((int64_t)(bv.bytes / 32u), 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const uint32_t*)table_f16, g, bv, (uint4*)view);
+    NRC_LAUNCH_CHECK();
+    return NRC_OK;
+}
 int nrc_ngp_encode_samples(const float* ts, const int32_t* row_tile, const float* ray_od, int64_t first_row, int64_t n_rows, const float* xyz_min3,
                            const float* xyz_size3, const void* table_f16, int32_t n_levels, int32_t log2_hashmap_size,
                            int32_t base_resolution, float per_level_scale, void* features_f16, const int32_t* arena_tile_off, int32_t arena_rows,
                            nrc_stream_t stream) {
     NRC_ENTER();
+    const void* view = take_block_view();
     const int64_t n = n_rows * 64;
     if (n_rows < 0 || first_row < 0 || n > NRC_QUERY_CHUNK || !table_f16 || !xyz_min3 || !xyz_size3) return NRC_ERR_INVALID;
     if ((arena_tile_off != nullptr) != (arena_rows > 0) || arena_rows < 0) return NRC_ERR_INVALID;
@@ -1189,7 +1285,7 @@ int nrc_ngp_encode_samples(const float* ts, const int32_t* row_tile, const float
     QueryIn in = {};
     in.ts = ts; in.row_tile = row_tile; in.ray_od = ray_od; in.tile_off = arena_tile_off; in.arena_rows = arena_rows;
     for (int k = 0; k < 3; k++) { in.mn[k] = xyz_min3[k]; in.sz[k] = xyz_size3[k]; }
-    launch_encode<SRC_TILED>(in, first_row * 64, n, table_f16, g, (uint4*)features_f16, (hipStream_t)stream);
+    launch_encode<SRC_TILED>(in, first_row * 64, n, table_f16, g, (uint4*)features_f16, (hipStream_t)stream, block_view_of(view, g, n_levels));
     NRC_LAUNCH_CHECK();
     return NRC_OK;
 }
@@ -1219,6 +1315,7 @@ int nrc_ngp_query_samples(const float* ts, int32_t* row_tile, const float* ray_o
                           float per_level_scale, void* packed_f16, void* workspace, const int32_t* n_rows_dev, const int32_t* arena_tile_off,
                           int32_t arena_rows, nrc_stream_t stream) {
     NRC_ENTER();
+    const void* view = take_block_view();
     const int64_t M = n_rows * 64;
     if ((arena_tile_off != nullptr) != (arena_rows > 0) || arena_rows < 0) return NRC_ERR_INVALID;
     if (n_rows < 0 || n_ray_tiles < 0 || !density_weights_f16 || !color_weights_f16 || !table_f16 || !xyz_min3 || !xyz_size3) return NRC_ERR_INVALID;
@@ -1232,7 +1329,8 @@ int nrc_ngp_query_samples(const float* ts, int32_t* row_tile, const float* ray_o
     in.ts = ts; in.row_tile = row_tile; in.ray_od = ray_od; in.n_rows_dev = n_rows_dev;
     in.tile_off = arena_tile_off; in.arena_rows = arena_rows;
     for (int k = 0; k < 3; k++) { in.mn[k] = xyz_min3[k]; in.sz[k] = xyz_size3[k]; }
-    run_query<SRC_TILED>(in, M, n_ray_tiles, density_weights_f16, color_weights_f16, table_f16, g, nullptr, nullptr, packed_f16, workspace, (hipStream_t)stream);
+    run_query<SRC_TILED>(in, M, n_ray_tiles, density_weights_f16, color_weights_f16, table_f16, g, nullptr, nullptr, packed_f16, workspace, (hipStream_t)stream,
+                         block_view_of(view, g, n_levels));
     NRC_LAUNCH_CHECK();
     return NRC_OK;
 }
@@ -1255,6 +1353,7 @@ int nrc_ngp_render_layers(const float* ts, int32_t* row_tile, const float* ray_o
                           void* packed_f16, float* rgb, float* alpha, float* depth, int32_t* skipped_rows, void* workspace, const int32_t* arena_row_k,
                           int32_t arena_rows, nrc_stream_t stream) {
     NRC_ENTER();
+    const void* view = take_block_view();
     const int64_t M = n_rows * 64;
     if ((arena_row_k != nullptr) != (arena_rows > 0) || arena_rows < 0) return NRC_ERR_INVALID;
     if (n_rows < 0 || n_ray_tiles < 1 || !density_weights_f16 || !color_weights_f16 || !table_f16 || !xyz_min3 || !xyz_size3 || !bg3_host ||
@@ -1280,6 +1379,7 @@ int nrc_ngp_render_layers(const float* ts, int32_t* row_tile, const float* ray_o
     in.ts = ts; in.row_tile = row_tile; in.ray_od = ray_od;
     in.row_k = arena_row_k; in.arena_rows = arena_rows;
     for (int k = 0; k < 3; k++) { in.mn[k] = xyz_min3[k]; in.sz[k] = xyz_size3[k]; }
+    const BlockView bv = block_view_of(view, g, n_levels);
     nrc_launch_layers_init(n_ray_tiles, ray_cnt, state, ray_alive, next_k, tile_alive, skipped_rows, s);
     hipLaunchKernelGGL(k_ray_sh, dim3((unsigned)nrc_cdiv(n_ray_tiles * 64, 256)), dim3(256), 0, s, ray_od, n_ray_tiles, ray_sh);
     // front to back: encode + MLP on a slab of rows, composite it, finished tiles drop out of the following slabs.  No host
@@ -1288,7 +1388,7 @@ int nrc_ngp_render_layers(const float* ts, int32_t* row_tile, const float* ray_o
     do {
         const int64_t cn = (M - base) < NRC_QUERY_CHUNK ? (M - base) : NRC_QUERY_CHUNK;
         if (cn > 0) {
-            launch_encode<SRC_TILED>(in, base, cn, table_f16, g, feat, s);
+            launch_encode<SRC_TILED>(in, base, cn, table_f16, g, feat, s, bv);
             launch_mlp<SRC_TILED>(in, base, cn, feat, ray_sh, density_weights_f16, color_weights_f16, nullptr, nullptr, packed_f16, s);
         }
         nrc_launch_composite_layers(packed_f16, ts, ray_cnt, tile_rows, tile_off, row_of, row_tile, (base + cn) / 64, width, height, tile_begin, n_ray_tiles, cascades,
@@ -1325,6 +1425,7 @@ int nrc_ngp_render_frame(const float* ts_arena, int32_t* row_tile, const float* 
                          float T_threshold, const float* bg3_host, float* rgb, float* alpha, float* depth, int64_t row_budget, void* workspace,
                          nrc_stream_t stream) {
     NRC_ENTER();
+    const void* view = take_block_view();
     const int64_t budget = frame_budget(row_budget);
     if (n_rows < 0 || n_ray_tiles < 1 || width < 1 || height < 1 || tile_begin < 0 || cascades < 1 || grid_size < 1 || max_samples < 1 ||
         budget < 2 * (int64_t)max_samples || !density_weights_f16 || !color_weights_f16 || !table_f16 || !xyz_min3 || !xyz_size3 || !bg3_host)
@@ -1359,6 +1460,7 @@ int nrc_ngp_render_frame(const float* ts_arena, int32_t* row_tile, const float* 
     hipGetDevice(&dev);
     hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
     const int64_t resident = (int64_t)(n_cu > 0 ? n_cu : 256) * NRC_MLP_WAVES, mlp_blocks = nrc_cdiv(n_ray_tiles, 4) < resident ? nrc_cdiv(n_ray_tiles, 4) : resident;
+    const BlockView bv = block_view_of(view, g, n_levels);
     NRC_STAGE(s, nullptr);
     // SH of every ray + the ray tile of every row (for the encoder)
     hipLaunchKernelGGL(k_ray_sh, dim3((unsigned)nrc_cdiv(n_ray_tiles * 64, 256)), dim3(256), 0, s, ray_od, n_ray_tiles, ray_sh, tile_off, row_tile, n_rows);
@@ -1369,7 +1471,7 @@ int nrc_ngp_render_frame(const float* ts_arena, int32_t* row_tile, const float* 
     for (int64_t c = 0; c < chunks; c++) {
         if (n_rows > 0) {
             in.chunk_rows = chunk_tab + 4 * c + 2;
-            launch_encode<SRC_TILED>(in, 0, feat_rows * 64, table_f16, g, feat, s);
+            launch_encode<SRC_TILED>(in, 0, feat_rows * 64, table_f16, g, feat, s, bv);
             NRC_STAGE(s, "k_grid_encode");
         }
         hipLaunchKernelGGL(k_ngp_mlp_composite, dim3((unsigned)mlp_blocks), dim3(256), 0, s, feat, ray_sh, (const __half*)density_weights_f16,

@@ -74,9 +74,13 @@ class GraphedIteration:
             if p.requires_grad and p.is_leaf:
                 p.grad = None
                 p.requires_grad_(False).requires_grad_(True)
+        owners = [o for o in (getattr(p, '_nrc_half_owner', lambda: None)() for p in leaves) if o is not None]
+        captures = [o._half_captures for o in owners]
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):   # records, does not execute
             self.outputs = self.body(**self.inputs)
+        self._written = list(leaves)
+        self._half_written = [o for o, c in zip(owners, captures) if o._half_captures != c]   # their fp16 copies are rewritten by the recorded optimizer step
 
     def __call__(self, **inputs: torch.Tensor) -> dict[str, torch.Tensor]:
         self._load(inputs)
@@ -88,6 +92,12 @@ class GraphedIteration:
         if self.before_replay is not None:
             self.before_replay()
         self.graph.replay()
+        # the replayed kernels wrote the parameters (and these fp16 copies) through raw pointers and no Python ran: tell autograd and every
+        # version-keyed cache, as the eager optimizer step does
+        for p in self._written:
+            torch.autograd.graph.increment_version(p)
+        for owner in self._half_written:
+            owner._half_written_by_optimizer(owner.params)
         return self.outputs
 
     @property

@@ -348,6 +348,22 @@ class InstantNGPRenderer:
             _lib.stream_of(ws['ray_od'])), 'ngp_render_count')
         return ticket
 
+    def _block_view_ptr(self):
+        """The cell-block view of the grid's dense levels for the image encoder (tinycudann._block_view: built here if the fp16 table changed, valid
+        from frame to frame otherwise).  Taken where a frame's arguments are marshalled -- ahead of the wait for the row count."""
+        return _lib.ptr(self.model.encoding_xyz._block_view())
+
+    @staticmethod
+    def _frame_entry(fn, args, what: str, view) -> None:
+        """One of the library's frame entry points with the view handed over in front of it (nrc_ngp_set_encoder_block_view: the call takes it).
+        Cleared behind the call as well: a call that never reached the library (an argument ctypes refuses) must not leave it to the next one."""
+        lib = _lib.load()
+        lib.nrc_ngp_set_encoder_block_view(view)
+        try:
+            _lib.check(fn(*args), what)
+        finally:
+            lib.nrc_ngp_set_encoder_block_view(None)
+
     def _fused_size_rows(self, ws: dict, rows: int, nt: int) -> None:
         if rows > ws['cap']:
             lib = _lib.load()
@@ -363,6 +379,7 @@ class InstantNGPRenderer:
         """argument list of nrc_ngp_query_samples with the row count (index 3) still open: marshalled BEFORE the host waits for that count, so that
         nothing but the call itself stands between the count's arrival and the launch"""
         m, vp, g = self.model, ctypes.c_void_p, fc['grid']
+        ws['block_view'] = self._block_view_ptr()
         return [_lib.ptr(ws['ts_prov'] if arena else ws['ts']), _lib.ptr(ws['row_tile']), _lib.ptr(ws['ray_od']), 0, nt, ctypes.cast(fc['mn'], vp),
                 ctypes.cast(fc['sz'], vp), _lib.ptr(m.encoding_xyz._half_params()), _lib.ptr(m.color_mlp_with_encoding._half_params()),
                 _lib.ptr(m.encoding_xyz._table16()), g['n_levels'], g['log2_hashmap_size'], g['base_resolution'], float(g['per_level_scale']),
@@ -385,7 +402,7 @@ class InstantNGPRenderer:
         args[3] = rows
         if self.POSE_ENCODER_SHAPE:
             lib.nrc_ngp_set_encoder_shape(*fc['enc_shape'])
-        _lib.check(lib.nrc_ngp_query_samples(*args), 'ngp_query_samples')
+        self._frame_entry(lib.nrc_ngp_query_samples, args, 'ngp_query_samples', ws['block_view'])
 
     def _frame_args(self, fc: dict, ws: dict, out: dict, tile_begin: int, nt: int) -> list:
         """argument list of nrc_ngp_render_frame (the single pass from the arena: MLP and compositing in one kernel) with the row count (index 3)
@@ -396,6 +413,7 @@ class InstantNGPRenderer:
             ws['fws'] = None
             ws['fws'] = torch.empty(int(lib.nrc_ngp_render_frame_ws_bytes(ws['cap'], nt, self.MAX_SAMPLES, budget)), dtype=torch.uint8, device=ws['ray_od'].device)
             ws['fws_key'] = (ws['cap'], budget)
+        ws['block_view'] = self._block_view_ptr()
         return [_lib.ptr(ws['ts_prov']), _lib.ptr(ws['row_tile']), _lib.ptr(ws['ray_od']), 0, nt, ctypes.cast(fc['mn'], vp), ctypes.cast(fc['sz'], vp),
                 _lib.ptr(m.encoding_xyz._half_params()), _lib.ptr(m.color_mlp_with_encoding._half_params()), _lib.ptr(m.encoding_xyz._table16()),
                 g['n_levels'], g['log2_hashmap_size'], g['base_resolution'], float(g['per_level_scale']), _lib.ptr(ws['ray_cnt']), _lib.ptr(ws['tile_off']),
@@ -409,7 +427,7 @@ class InstantNGPRenderer:
         args[3] = rows
         if self.POSE_ENCODER_SHAPE:
             lib.nrc_ngp_set_encoder_shape(*fc['enc_shape'])
-        _lib.check(lib.nrc_ngp_render_frame(*args), 'ngp_render_frame')
+        self._frame_entry(lib.nrc_ngp_render_frame, args, 'ngp_render_frame', ws['block_view'])
 
     def _fused_composite(self, fc: dict, ws: dict, out: dict, tile_begin: int, nt: int, row_capacity: int = 0, arena: bool = False) -> None:
         m, lib, cam = self.model, _lib.load(), fc['camera']
@@ -475,11 +493,11 @@ class InstantNGPRenderer:
             if rows > 0:
                 g = fc['grid']
                 vp = ctypes.c_void_p
-                _lib.check(_lib.load().nrc_ngp_query_samples(
+                self._frame_entry(_lib.load().nrc_ngp_query_samples, (
                     _lib.ptr(ws['ts']), _lib.ptr(ws['row_tile']), _lib.ptr(ws['ray_od']), rows, nt, ctypes.cast(fc['mn'], vp), ctypes.cast(fc['sz'], vp),
                     _lib.ptr(m.encoding_xyz._half_params()), _lib.ptr(m.color_mlp_with_encoding._half_params()), _lib.ptr(m.encoding_xyz._table16()),
                     g['n_levels'], g['log2_hashmap_size'], g['base_resolution'], float(g['per_level_scale']), _lib.ptr(ws['packed']), _lib.ptr(ws['qws']),
-                    None, None, 0, _lib.stream_of(ws['ray_od'])), 'ngp_query_samples')
+                    None, None, 0, _lib.stream_of(ws['ray_od'])), 'ngp_query_samples', self._block_view_ptr())
             self._fused_composite(fc, ws, out, b, nt)
             if k + 1 < shards:     # the next range's count pass starts now, under the kernels just enqueued; its buffers were last used a frame ago
                 nb, ne = ranges[k + 1]
@@ -596,14 +614,15 @@ class InstantNGPRenderer:
                 ws['qws'] = torch.empty(int(lib.nrc_ngp_render_layers_ws_bytes(0, nt)), dtype=torch.uint8, device=dev)
             if self.POSE_ENCODER_SHAPE:
                 lib.nrc_ngp_set_encoder_shape(*fc['enc_shape'])
-            _lib.check(lib.nrc_ngp_render_layers(
+            self._frame_entry(lib.nrc_ngp_render_layers, (
                 _lib.ptr(ws.get('ts_prov') if arena else ws.get('ts')), _lib.ptr(ws.get('row_tile')), _lib.ptr(ws['ray_od']), rows, nt, ctypes.cast(fc['mn'], vp),
                 ctypes.cast(fc['sz'], vp), _lib.ptr(m.encoding_xyz._half_params()), _lib.ptr(m.color_mlp_with_encoding._half_params()),
                 _lib.ptr(m.encoding_xyz._table16()), g['n_levels'], g['log2_hashmap_size'], g['base_resolution'], float(g['per_level_scale']),
                 _lib.ptr(ws['ray_cnt']), _lib.ptr(ws['tile_rows']), _lib.ptr(ws['tile_off']), _lib.ptr(ws.get('row_of')), camera.width, camera.height,
                 int(tile_begin), m.cascades, float(esf), m.RESOLUTION, self.MAX_SAMPLES, 1e-4, ctypes.cast(fc['bg'], vp),
                 _lib.ptr(ws.get('packed')), _lib.ptr(out['rgb']), _lib.ptr(out['alpha']), _lib.ptr(out['depth']), _lib.ptr(ws['skipped']),
-                _lib.ptr(ws['qws']), _lib.ptr(ws['row_k']) if (arena and rows > 0) else None, self.MAX_SAMPLES if (arena and rows > 0) else 0, st), 'ngp_render_layers')
+                _lib.ptr(ws['qws']), _lib.ptr(ws['row_k']) if (arena and rows > 0) else None, self.MAX_SAMPLES if (arena and rows > 0) else 0, st), 'ngp_render_layers',
+                self._block_view_ptr())
             if 'skipped_host' not in ws:
                 ws['skipped_host'] = torch.zeros(1, dtype=torch.int32).pin_memory()
             ws['skipped_host'].copy_(ws['skipped'], non_blocking=True)   # for the next frame's policy; ordered behind this frame on the stream

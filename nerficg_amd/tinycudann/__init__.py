@@ -203,6 +203,9 @@ class NetworkWithInputEncoding(torch.nn.Module):
         self.params = torch.nn.Parameter(torch.cat(chunks).to(torch.float32), requires_grad=True)
         self._half = None
         self._half_key = None
+        self._view = None       # _block_view
+        self._view_key = None
+        self._half_captures = 0  # times the fp16 copy was handed to an optimizer step that a HIP graph was recording (_half_for_optimizer)
         # nerficg_amd.apex_optimizers.FusedAdam updates `params` through a raw pointer: it finds this module through the parameter and
         # has the step kernel rewrite the fp16 copy as well (_half_for_optimizer / _half_written_by_optimizer)
         self.params._nrc_half_owner = weakref.ref(self)
@@ -217,6 +220,11 @@ class NetworkWithInputEncoding(torch.nn.Module):
         if p is not self.params or not p.is_cuda or self._w0_cols is not None:   # (a remapped first layer: the copy is not a 1:1 mirror, rebuilt on use instead)
             return None
         self._refresh_half()
+        if torch.cuda.is_current_stream_capturing():
+            # a replay of that graph rewrites parameters and copy with no Python in between: nothing bumps a version.  The copy itself stays current
+            # (the kernel writes it), anything DERIVED from it under a version key does not -- see _block_view; graphs.GraphedIteration reads the
+            # counter to know whose copy its recording writes
+            self._half_captures += 1
         return self._half
 
     def _half_written_by_optimizer(self, p) -> None:
@@ -261,6 +269,32 @@ class NetworkWithInputEncoding(torch.nn.Module):
 
     def _table16(self):
         return self._half[self._n_kernel_mlp:] if self.encoding == 0 else None
+
+    def _block_view(self):
+        """Cell-block view of the fp16 table's leading dense levels for the image encoder (include/nerficg_hip.h, nrc_ngp_build_block_view), cached
+        next to the fp16 copy under the same key: rebuilt (one pass over ~11 MB) when the copy was -- by _refresh_half or in place by the optimizer --
+        and valid from frame to frame otherwise.  Once a recorded HIP graph writes the copy (_half_captures: a replay changes the table and no
+        version), the key says nothing any more and the view is rebuilt for every frame; and a frame that is being RECORDED carries the build in
+        its recording, so that a replay reads the table of its own time as the table path does.  None for a grid without such levels."""
+        if self.encoding != 0 or not self.default_layout:
+            return None
+        self._refresh_half()
+        key = (self._half_key, self._half.data_ptr())
+        if self._view_key != key or self._half_captures or torch.cuda.is_current_stream_capturing():
+            lib, g = _lib.load(), self.grid_cfg
+            cfg = (g['n_levels'], g['log2_hashmap_size'], g['base_resolution'], float(g['per_level_scale']))
+            nbytes = int(lib.nrc_ngp_block_view_bytes(*cfg))
+            if nbytes < 0:
+                _lib.check(nbytes, 'ngp_block_view_bytes')
+            view = self._view
+            if nbytes == 0:
+                view = None
+            elif view is None or view.numel() != nbytes or view.device != self._half.device:
+                view = torch.empty(nbytes, dtype=torch.uint8, device=self._half.device)
+            if view is not None:
+                _lib.check(lib.nrc_ngp_build_block_view(_lib.ptr(self._table16()), *cfg, _lib.ptr(view), _lib.stream_of(view)), 'ngp_build_block_view')
+            self._view, self._view_key = view, key
+        return self._view
 
     @property
     def default_layout(self) -> bool:
