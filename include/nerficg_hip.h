@@ -39,8 +39,9 @@ enum {
  * 9 = group 15 (nrc_map_losses_*: the depth-smoothness and alpha-entropy losses on the rasterizer's maps) is new, every earlier signature is unchanged;
  * 10 = nrc_ngp_set_encoder_xcd_run (group 6) is new, every earlier signature is unchanged;
  * 11 = nrc_ngp_set_encoder_block_levels / _block_view, nrc_ngp_block_view_bytes, nrc_ngp_build_block_view (group 6: the cell-block view of the dense
- * levels) are new, every earlier signature is unchanged. */
-#define NRC_ABI_VERSION 11
+ * levels) are new, every earlier signature is unchanged;
+ * 12 = nrc_ngp_render_count_rays (group 6: the count pass for a caller's own ray list) is new, every earlier signature is unchanged. */
+#define NRC_ABI_VERSION 12
 /* library identification; also used by the loader's symbol check */
 int nrc_abi_version(void);
 const char* nrc_build_info(void);
@@ -496,6 +497,22 @@ int nrc_ngp_render_count(int32_t width, int32_t height, const double* intrinsics
  * tile): the count pass parks every sample's t there and steps 2 copy them into their final rows instead of marching the rays a
  * second time (pass the same buffer to both calls).  HBM is plentiful on this part: 2.6 GB for an 800x800 image. */
 int64_t nrc_ngp_render_provisional_bytes(int64_t n_tiles, int32_t max_samples);
+/* ABI 12, the count pass for a caller's own rays: nrc_ngp_render_count with the ray of pixel p read from row p of origin / view_direction (DEVICE,
+ * (n_rays,3) f32 each) instead of derived from a camera.  The origin is shifted by center3, the direction is used AS GIVEN (not normalised: the reference
+ * hands rays.view_direction through untouched, Renderer.py:40), box test / near-far clamp / march and every output are those of nrc_ngp_render_count, so
+ * steps 2-4 (and the layer / frame variants) follow unchanged -- they read rays from ray_od only.  A lane whose pixel has no row (p >= n_rays) is an
+ * out-of-image pixel: no samples, background.  Refused (NRC_ERR_INVALID): n_rays < 0, n_rays > width * height, a NULL ray array with n_rays > 0, and
+ * whatever nrc_ngp_render_count refuses.  Two ways to use it:
+ *   a ray list            width = nrc_ngp_tile_width(), height = nrc_ngp_tile_height() * ceil(N / 64): the virtual image is one tile wide, so pixel index
+ *                         = ray index and tile T holds rays 64 T .. 64 T + 63; every later stage is called with this width / height and with output
+ *                         buffers of 64 * n_tiles entries (the first N are the rays').
+ *   a row-major image of  (what View.get_rays() returns) the real width, height and n_rays = width * height: tiles are the 8x8 pixel blocks of the camera
+ *   rays                  path, so the encoder sees the same spatial coherence -- any camera model, its ray generator stays the caller's. */
+int nrc_ngp_render_count_rays(int32_t width, int32_t height, int64_t n_rays, const float* origin, const float* view_direction, const float* center3,
+                              const float* half3, float near_plane, float far_plane, int64_t tile_begin, int64_t n_tiles,
+                              const uint8_t* density_bitfield, int32_t cascades, float scale, float exp_step_factor, int32_t grid_size,
+                              int32_t max_samples, float* ray_od, float* ray_t, int32_t* ray_cnt, int32_t* tile_rows, int32_t* tile_off,
+                              int32_t* counter, float* ts_provisional, int64_t* count_mailbox, int64_t mailbox_ticket, nrc_stream_t stream);
 int nrc_ngp_render_write(int64_t n_tiles, const uint8_t* density_bitfield, int32_t cascades, float scale,
                          float exp_step_factor, int32_t grid_size, int32_t max_samples, const float* ray_od,
                          const float* ray_t, const int32_t* ray_cnt, const int32_t* tile_off, float* ts, int32_t* row_tile,

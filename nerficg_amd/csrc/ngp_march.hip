@@ -60,6 +60,21 @@ __device__ __forceinline__ Ray load_ray(const float* __restrict__ o, const float
     q.dxi = 1.0f / q.dx; q.dyi = 1.0f / q.dy; q.dzi = 1.0f / q.dz;
     return q;
 }
+// A box-centred ray (o, d set) against the box [-h, h]: the reciprocals of d, the slab test (intersection.cu:5-22; hits_t keeps -1 unless t2 > 0,
+// :48-53) and the near/far clamp (Renderer.py:42-43).  A miss is (near, -1): an empty interval.  The ONE copy behind k_clip_rays, camera_ray and
+// k_render_count_rays: the ray-list ops and both doors of the fused frame clip a ray with the same f32 sequence.
+__device__ __forceinline__ void clip_ray_to_box(Ray& q, float hx, float hy, float hz, float near_plane, float far_plane, float& t1, float& t2) {
+    q.dxi = 1.0f / q.dx; q.dyi = 1.0f / q.dy; q.dzi = 1.0f / q.dz;
+    const float ax = (0.f - hx - q.ox) * q.dxi, bx = (0.f + hx - q.ox) * q.dxi;
+    const float ay = (0.f - hy - q.oy) * q.dyi, by = (0.f + hy - q.oy) * q.dyi;
+    const float az = (0.f - hz - q.oz) * q.dzi, bz = (0.f + hz - q.oz) * q.dzi;
+    float a = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz));
+    float b = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
+    if (a > b) { a = -1.0f; b = -1.0f; }
+    if (b > 0) a = fmaxf(a, 0.0f); else { a = -1.0f; b = -1.0f; }
+    t1 = fmaxf(a, near_plane);
+    t2 = fminf(b, far_plane);
+}
 
 struct MarchCfg {
     const uint8_t* __restrict__ bitfield;
@@ -250,19 +265,14 @@ __global__ void __launch_bounds__(256) k_clip_rays(int64_t n, const float* __res
                                                    float* __restrict__ span) {
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (r >= n) return;
-    const float ox = origin[3 * r] - cx, oy = origin[3 * r + 1] - cy, oz = origin[3 * r + 2] - cz;
-    o_out[3 * r] = ox; o_out[3 * r + 1] = oy; o_out[3 * r + 2] = oz;
-    const float ix = 1.0f / dirs[3 * r], iy = 1.0f / dirs[3 * r + 1], iz = 1.0f / dirs[3 * r + 2];
-    const float ax = (0.0f - hx - ox) * ix, bx = (0.0f + hx - ox) * ix;
-    const float ay = (0.0f - hy - oy) * iy, by = (0.0f + hy - oy) * iy;
-    const float az = (0.0f - hz - oz) * iz, bz = (0.0f + hz - oz) * iz;
-    float t1 = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz));
-    float t2 = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
-    if (t1 > t2) { t1 = -1.0f; t2 = -1.0f; }
-    float s0 = -1.0f, s1 = -1.0f;
-    if (t2 > 0) { s0 = fmaxf(t1, 0.0f); s1 = t2; }
-    span[2 * r] = fmaxf(s0, near_plane);      // a miss stays (near, -1): an empty interval
-    span[2 * r + 1] = fminf(s1, far_plane);
+    Ray q;
+    q.ox = origin[3 * r] - cx; q.oy = origin[3 * r + 1] - cy; q.oz = origin[3 * r + 2] - cz;
+    q.dx = dirs[3 * r]; q.dy = dirs[3 * r + 1]; q.dz = dirs[3 * r + 2];
+    o_out[3 * r] = q.ox; o_out[3 * r + 1] = q.oy; o_out[3 * r + 2] = q.oz;
+    float t1, t2;
+    clip_ray_to_box(q, hx, hy, hz, near_plane, far_plane, t1, t2);
+    span[2 * r] = t1;      // a miss stays (near, -1): an empty interval
+    span[2 * r + 1] = t2;
 }
 
 // ------------------------------------------------------------------------------------------------ ray marching (train)
@@ -858,16 +868,7 @@ __device__ __forceinline__ void camera_ray(const RenderCam& cam, int64_t pix, Ra
     const float nrm = fmaxf(sqrtf(dx * dx + dy * dy + dz * dz), 1e-12f);
     q.dx = dx / nrm; q.dy = dy / nrm; q.dz = dz / nrm;
     q.ox = cam.g.pos[0] - cam.center[0]; q.oy = cam.g.pos[1] - cam.center[1]; q.oz = cam.g.pos[2] - cam.center[2];
-    q.dxi = 1.0f / q.dx; q.dyi = 1.0f / q.dy; q.dzi = 1.0f / q.dz;
-    const float ax = (0.f - cam.half[0] - q.ox) * q.dxi, bx = (0.f + cam.half[0] - q.ox) * q.dxi;
-    const float ay = (0.f - cam.half[1] - q.oy) * q.dyi, by = (0.f + cam.half[1] - q.oy) * q.dyi;
-    const float az = (0.f - cam.half[2] - q.oz) * q.dzi, bz = (0.f + cam.half[2] - q.oz) * q.dzi;
-    float a = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fminf(az, bz));
-    float b = fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz));
-    if (a > b) { a = -1.0f; b = -1.0f; }
-    if (b > 0) a = fmaxf(a, 0.0f); else { a = -1.0f; b = -1.0f; }  // hits_t keeps -1 unless t2 > 0 (intersection.cu:48-53)
-    t1 = fmaxf(a, cam.near_plane);
-    t2 = fminf(b, cam.far_plane);
+    clip_ray_to_box(q, cam.half[0], cam.half[1], cam.half[2], cam.near_plane, cam.far_plane, t1, t2);
 }
 // Tile-interleaved sample layout (the MI355X-native core of the image pipeline).
 // A tile = 8x8 pixels = one wave, lane = pixel (lx = lane & 7, ly = lane >> 3).  Sample k of the ray on lane l of tile T lives
@@ -885,21 +886,14 @@ __device__ __forceinline__ int64_t tile_pixel(const RayGenCfg& g, int64_t tile, 
     const int px = tx * NRC_TILE_W + (lane & (NRC_TILE_W - 1)), py = ty * NRC_TILE_H + (lane >> NRC_TILE_W_LOG2);
     return (px < g.width && py < g.height) ? (int64_t)py * g.width + px : -1;
 }
-__global__ void __launch_bounds__(256) k_render_count(RenderCam cam, MarchCfg c, int tiles_x, int64_t tile_begin, int64_t n_tiles,
-                                                      float* __restrict__ ray_od, float* __restrict__ ray_t,
-                                                      int32_t* __restrict__ ray_cnt, int32_t* __restrict__ tile_rows, float* __restrict__ ts_prov) {
-    __shared__ uint32_t s_lut[MARCH_LUT_MAX];
-    march_lut(c, s_lut);
-    const int lane = threadIdx.x & 63;
-    const int64_t lt = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);  // local tile
-    if (lt >= n_tiles) return;
-    const int64_t pix = tile_pixel(cam.g, tile_begin + lt, lane, tiles_x);
+// What a lane of the count pass does once it has its ray (has_ray false: a lane without one -- count 0, the finite default Ray, t2 = -1): DDA march with the
+// samples parked in the arena, the per-ray records, the holes of the tile's rows and the tile's totals.  Shared by both count kernels below.
+__device__ __forceinline__ void count_pass_lane(bool has_ray, const Ray& ry, float t1, float t2, const MarchCfg& c, const uint32_t* s_lut, int64_t lt, int lane,
+                                                int64_t n_tiles, float* __restrict__ ray_od, float* __restrict__ ray_t, int32_t* __restrict__ ray_cnt,
+                                                int32_t* __restrict__ tile_rows, float* __restrict__ ts_prov) {
     const int64_t q = lt * 64 + lane;
     int n = 0;
-    Ray ry = {0.f, 0.f, 0.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
-    float t1 = 0.f, t2 = -1.f;
-    if (pix >= 0) {
-        camera_ray(cam, pix, ry, t1, t2);
+    if (has_ray) {
         float t = t1, x, y, z, dt;
         if (ts_prov) {
             // the samples are parked in a per-tile arena of max_samples rows (sample k of lane l at (lt * max_samples + k) * 64 + l):
@@ -927,6 +921,43 @@ __global__ void __launch_bounds__(256) k_render_count(RenderCam cam, MarchCfg c,
     }
     const int tile_samples = nrc_group_sum_i<64>(n);
     if (lane == 0) { tile_rows[lt] = m; tile_rows[n_tiles + lt] = tile_samples; }   // second half of the array: samples per tile (for the total)
+}
+__global__ void __launch_bounds__(256) k_render_count(RenderCam cam, MarchCfg c, int tiles_x, int64_t tile_begin, int64_t n_tiles,
+                                                      float* __restrict__ ray_od, float* __restrict__ ray_t,
+                                                      int32_t* __restrict__ ray_cnt, int32_t* __restrict__ tile_rows, float* __restrict__ ts_prov) {
+    __shared__ uint32_t s_lut[MARCH_LUT_MAX];
+    march_lut(c, s_lut);
+    const int lane = threadIdx.x & 63;
+    const int64_t lt = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);  // local tile
+    if (lt >= n_tiles) return;
+    const int64_t pix = tile_pixel(cam.g, tile_begin + lt, lane, tiles_x);
+    Ray ry = {0.f, 0.f, 0.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
+    float t1 = 0.f, t2 = -1.f;
+    if (pix >= 0) camera_ray(cam, pix, ry, t1, t2);
+    count_pass_lane(pix >= 0, ry, t1, t2, c, s_lut, lt, lane, n_tiles, ray_od, ray_t, ray_cnt, tile_rows, ts_prov);
+}
+// The count pass for a caller's own rays (nrc_ngp_render_count_rays): k_render_count with the ray of pixel p read from row p of (n_rays, 3) origin /
+// view_direction arrays instead of derived from a camera.  The direction is taken as given (Renderer.py:40 passes rays.view_direction untouched); a lane
+// whose pixel is outside the image or has no row (p >= n_rays) behaves as an out-of-image pixel does.  cam: g.width / g.height, center, half, near / far only.
+__global__ void __launch_bounds__(256) k_render_count_rays(RenderCam cam, const float* __restrict__ origin, const float* __restrict__ view_dir, int64_t n_rays,
+                                                           MarchCfg c, int tiles_x, int64_t tile_begin, int64_t n_tiles, float* __restrict__ ray_od,
+                                                           float* __restrict__ ray_t, int32_t* __restrict__ ray_cnt, int32_t* __restrict__ tile_rows,
+                                                           float* __restrict__ ts_prov) {
+    __shared__ uint32_t s_lut[MARCH_LUT_MAX];
+    march_lut(c, s_lut);
+    const int lane = threadIdx.x & 63;
+    const int64_t lt = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);  // local tile
+    if (lt >= n_tiles) return;
+    const int64_t pix = tile_pixel(cam.g, tile_begin + lt, lane, tiles_x);
+    const bool has_ray = pix >= 0 && pix < n_rays;
+    Ray ry = {0.f, 0.f, 0.f, 1.f, 1.f, 1.f, 1.f, 1.f, 1.f};
+    float t1 = 0.f, t2 = -1.f;
+    if (has_ray) {
+        ry.ox = origin[3 * pix] - cam.center[0]; ry.oy = origin[3 * pix + 1] - cam.center[1]; ry.oz = origin[3 * pix + 2] - cam.center[2];
+        ry.dx = view_dir[3 * pix]; ry.dy = view_dir[3 * pix + 1]; ry.dz = view_dir[3 * pix + 2];
+        clip_ray_to_box(ry, cam.half[0], cam.half[1], cam.half[2], cam.near_plane, cam.far_plane, t1, t2);
+    }
+    count_pass_lane(has_ray, ry, t1, t2, c, s_lut, lt, lane, n_tiles, ray_od, ray_t, ray_cnt, tile_rows, ts_prov);
 }
 // exclusive scan of tile_rows[0..n_tiles) -> tile_off[0..n_tiles] (tile_off[n_tiles] = total rows); counter = (total rows, total samples: the
 // sum of tile_rows[n_tiles..2 n_tiles)), so that the caller's ONE host read sizes the sample buffers and reports the marched samples.
@@ -1368,30 +1399,56 @@ static void fill_raygen(RayGenCfg& g, int32_t width, int32_t height, const doubl
 int64_t nrc_ngp_render_provisional_bytes(int64_t n_tiles, int32_t max_samples) {
     return (n_tiles < 0 || max_samples < 1) ? -1 : n_tiles * (int64_t)max_samples * 256 + 256;
 }
-int nrc_ngp_render_count(int32_t width, int32_t height, const double* intr, const double* c2w, const float* center3, const float* half3,
-                         float near_plane, float far_plane, int64_t tile_begin, int64_t n_tiles, const uint8_t* bitfield,
-                         int32_t cascades, float scale, float esf, int32_t grid_size, int32_t max_samples, float* ray_od,
-                         float* ray_t, int32_t* ray_cnt, int32_t* tile_rows, int32_t* tile_off, int32_t* counter, float* ts_provisional,
-                         int64_t* count_mailbox, int64_t mailbox_ticket, nrc_stream_t stream) {
-    NRC_ENTER();
-    if (width < 1 || height < 1 || !intr || !c2w || !center3 || !half3 || n_tiles < 0 || tile_begin < 0 || cascades < 1 ||
-        grid_size < 1 || max_samples < 1 || !counter || !tile_off)
+// the two doors of the count pass: intr != NULL -> rays of the camera (intr, c2w), otherwise rows of the caller's (n_rays, 3) arrays
+static int render_count_any(int32_t width, int32_t height, const double* intr, const double* c2w, int64_t n_rays, const float* origin,
+                            const float* view_direction, const float* center3, const float* half3, float near_plane, float far_plane, int64_t tile_begin,
+                            int64_t n_tiles, const uint8_t* bitfield, int32_t cascades, float scale, float esf, int32_t grid_size, int32_t max_samples,
+                            float* ray_od, float* ray_t, int32_t* ray_cnt, int32_t* tile_rows, int32_t* tile_off, int32_t* counter, float* ts_provisional,
+                            int64_t* count_mailbox, int64_t mailbox_ticket, nrc_stream_t stream) {
+    if (width < 1 || height < 1 || !center3 || !half3 || n_tiles < 0 || tile_begin < 0 || cascades < 1 || grid_size < 1 || max_samples < 1 || !counter ||
+        !tile_off)
         return NRC_ERR_INVALID;
     const int tiles_x = (width + NRC_TILE_W - 1) / NRC_TILE_W, tiles_y = (height + NRC_TILE_H - 1) / NRC_TILE_H;
     if (tile_begin + n_tiles > (int64_t)tiles_x * tiles_y) return NRC_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     if (n_tiles > 0 && (!bitfield || !ray_od || !ray_t || !ray_cnt || !tile_rows)) return NRC_ERR_INVALID;
     RenderCam cam;
-    fill_raygen(cam.g, width, height, intr, c2w);
+    if (intr) fill_raygen(cam.g, width, height, intr, c2w);
+    else { cam.g = RayGenCfg{}; cam.g.width = width; cam.g.height = height; }
     for (int k = 0; k < 3; k++) { cam.center[k] = center3[k]; cam.half[k] = half3[k]; }
     cam.near_plane = near_plane; cam.far_plane = far_plane; cam.ray_begin = 0;
     const MarchCfg c = make_cfg(bitfield, cascades, scale, esf, grid_size, max_samples, (float)cascades);
-    if (n_tiles > 0)
+    if (n_tiles > 0 && intr)
         hipLaunchKernelGGL(k_render_count, dim3(nrc_cdiv(n_tiles, 4)), dim3(256), 0, s, cam, c, tiles_x, tile_begin, n_tiles, ray_od, ray_t,
                            ray_cnt, tile_rows, ts_provisional);
+    else if (n_tiles > 0)
+        hipLaunchKernelGGL(k_render_count_rays, dim3(nrc_cdiv(n_tiles, 4)), dim3(256), 0, s, cam, origin, view_direction, n_rays, c, tiles_x, tile_begin,
+                           n_tiles, ray_od, ray_t, ray_cnt, tile_rows, ts_provisional);
     hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(1024), 0, s, tile_rows, n_tiles, tile_off, counter, count_mailbox, mailbox_ticket);
     NRC_LAUNCH_CHECK();
     return NRC_OK;
+}
+int nrc_ngp_render_count(int32_t width, int32_t height, const double* intr, const double* c2w, const float* center3, const float* half3,
+                         float near_plane, float far_plane, int64_t tile_begin, int64_t n_tiles, const uint8_t* bitfield,
+                         int32_t cascades, float scale, float esf, int32_t grid_size, int32_t max_samples, float* ray_od,
+                         float* ray_t, int32_t* ray_cnt, int32_t* tile_rows, int32_t* tile_off, int32_t* counter, float* ts_provisional,
+                         int64_t* count_mailbox, int64_t mailbox_ticket, nrc_stream_t stream) {
+    NRC_ENTER();
+    if (!intr || !c2w) return NRC_ERR_INVALID;
+    return render_count_any(width, height, intr, c2w, 0, nullptr, nullptr, center3, half3, near_plane, far_plane, tile_begin, n_tiles, bitfield, cascades,
+                            scale, esf, grid_size, max_samples, ray_od, ray_t, ray_cnt, tile_rows, tile_off, counter, ts_provisional, count_mailbox,
+                            mailbox_ticket, stream);
+}
+int nrc_ngp_render_count_rays(int32_t width, int32_t height, int64_t n_rays, const float* origin, const float* view_direction, const float* center3,
+                              const float* half3, float near_plane, float far_plane, int64_t tile_begin, int64_t n_tiles, const uint8_t* bitfield,
+                              int32_t cascades, float scale, float esf, int32_t grid_size, int32_t max_samples, float* ray_od, float* ray_t,
+                              int32_t* ray_cnt, int32_t* tile_rows, int32_t* tile_off, int32_t* counter, float* ts_provisional, int64_t* count_mailbox,
+                              int64_t mailbox_ticket, nrc_stream_t stream) {
+    NRC_ENTER();
+    if (width < 1 || height < 1 || n_rays < 0 || n_rays > (int64_t)width * height || (n_rays > 0 && (!origin || !view_direction))) return NRC_ERR_INVALID;
+    return render_count_any(width, height, nullptr, nullptr, n_rays, origin, view_direction, center3, half3, near_plane, far_plane, tile_begin, n_tiles,
+                            bitfield, cascades, scale, esf, grid_size, max_samples, ray_od, ray_t, ray_cnt, tile_rows, tile_off, counter, ts_provisional,
+                            count_mailbox, mailbox_ticket, stream);
 }
 int nrc_ngp_render_write(int64_t n_tiles, const uint8_t* bitfield, int32_t cascades, float scale, float esf, int32_t grid_size,
                          int32_t max_samples, const float* ray_od, const float* ray_t, const int32_t* ray_cnt, const int32_t* tile_off,

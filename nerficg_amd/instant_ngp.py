@@ -12,6 +12,8 @@ the reference's configuration keys and method names where a caller would look fo
                                                loop's two ops raymarching_test / composite_test_fw stay in the C ABI for the reference's own
                                                Renderer.py and are tested against the oracle directly).
                          render_image[_fused]: the tile-interleaved device pipeline (include/nerficg_hip.h group 6), one host sync.
+                         render_rays_fused   : the same pipeline entered with the caller's own rays (any camera model, any ray subset): only the
+                                               count pass differs (nrc_ngp_render_count_rays); render_rays(eval, fused=True) routes here.
                          update_occupancy_grid / carve_occupancy_grid: cell choice, query positions, EMA, threshold, packing and carving
                                                are device ops (group 11); nothing is read back.
 """
@@ -215,9 +217,11 @@ class InstantNGPRenderer:
         return o, d, span
 
     def render_rays(self, origin: torch.Tensor, view_direction: torch.Tensor, camera: Camera, train_mode: bool = False,
-                    custom_bg_color: torch.Tensor | None = None, noise: torch.Tensor | None = None) -> dict[str, torch.Tensor]:
+                    custom_bg_color: torch.Tensor | None = None, noise: torch.Tensor | None = None, fused: bool = False) -> dict[str, torch.Tensor]:
         """rgb / alpha / depth (+ 'rm_samples' when training) for a list of rays.  `noise` (one value in [0,1) per ray) replaces the
-        training jitter draw."""
+        training jitter draw.  fused (inference only): the rays go through the tile pipeline of the image path (render_rays_fused)."""
+        if fused and not train_mode:
+            return self.render_rays_fused(origin, view_direction, camera, custom_bg_color=custom_bg_color)
         bg = (custom_bg_color if custom_bg_color is not None else camera.background_color).to(origin.device)
         step_growth = 1 / 256 if self.EXPONENTIAL_STEPS else 0.0
         o, d, span = self.clip_rays(origin.float(), view_direction.float(), camera)
@@ -291,10 +295,12 @@ class InstantNGPRenderer:
 
     # -- the stages of the fused image pipeline (one frame = frame constants + a workspace per rendered tile range) --------------------------
     def _frame_constants(self, camera: Camera, c2w) -> dict:
+        """c2w None: a frame of the caller's own rays (render_rays_fused) -- no intrinsics, no pose, the encoder's default brick"""
         m = self.model
-        c2w = np.ascontiguousarray(np.asarray(c2w, dtype=np.float64))
-        if c2w.shape == (3, 4):
-            c2w = np.vstack([c2w, [0.0, 0.0, 0.0, 1.0]])
+        if c2w is not None:
+            c2w = np.ascontiguousarray(np.asarray(c2w, dtype=np.float64))
+            if c2w.shape == (3, 4):
+                c2w = np.vstack([c2w, [0.0, 0.0, 0.0, 1.0]])
         f3 = lambda t: (ctypes.c_float * 3)(*[float(v) for v in t.reshape(-1).tolist()])
         g = m.encoding_xyz.grid_cfg
         # the model's box lives in device buffers: read ONCE per renderer (host copies, _box / _scene_box).  Until round 4 every frame read the four
@@ -312,10 +318,14 @@ class InstantNGPRenderer:
         # the brick that shares the most cache lines depends on which of the camera's axes runs along x: image rows (the default 8 x 2 pixels x 4 steps),
         # image columns (4 x 4 x 1), or the viewing direction (4 x 2 x 8).  Measured per pose on the bench orbit (tools/exp_pose_shapes.py): the choice
         # below loses to the best of twelve shapes by < 1 % on every pose and saves 2 % of the encoder over the fixed default.
-        right_x, down_x = abs(float(c2w[0, 0])), abs(float(c2w[0, 1]))
-        shape = (3, 1) if right_x >= 0.6 else ((2, 2) if down_x >= 0.35 else (2, 1))
-        return dict(enc_shape=shape, intr=(ctypes.c_double * 4)(camera.focal_x, camera.focal_y, camera.center_x, camera.center_y),
-                    mat=(ctypes.c_double * 16)(*c2w.reshape(-1).tolist()), center=f3(center), half=f3(half), mn=f3(mn), sz=f3(sz),
+        if c2w is None:
+            shape, intr, mat = (-1, -1), None, None   # (both < 0: the library's default brick)
+        else:
+            right_x, down_x = abs(float(c2w[0, 0])), abs(float(c2w[0, 1]))
+            shape = (3, 1) if right_x >= 0.6 else ((2, 2) if down_x >= 0.35 else (2, 1))
+            intr = (ctypes.c_double * 4)(camera.focal_x, camera.focal_y, camera.center_x, camera.center_y)
+            mat = (ctypes.c_double * 16)(*c2w.reshape(-1).tolist())
+        return dict(enc_shape=shape, intr=intr, mat=mat, center=f3(center), half=f3(half), mn=f3(mn), sz=f3(sz),
                     bg=f3(bg.float()), esf=1 / 256 if self.EXPONENTIAL_STEPS else 0.0, grid=g, camera=camera,
                     hw=camera.width * camera.height)
 
@@ -346,6 +356,21 @@ class InstantNGPRenderer:
             m.RESOLUTION, self.MAX_SAMPLES, _lib.ptr(ws['ray_od']), _lib.ptr(ws['ray_t']), _lib.ptr(ws['ray_cnt']), _lib.ptr(ws['tile_rows']),
             _lib.ptr(ws['tile_off']), _lib.ptr(ws['counter']), _lib.ptr(ws.get('ts_prov')), mailbox.ptr if mailbox is not None else None, ticket,
             _lib.stream_of(ws['ray_od'])), 'ngp_render_count')
+        return ticket
+
+    def _fused_count_rays(self, fc: dict, ws: dict, tile_begin: int, nt: int, mailbox=None) -> int:
+        """the count pass over the caller's rays fc['rays'] = (origin, view_direction, n) instead of the camera's (nrc_ngp_render_count_rays); fc['camera']
+        carries the (virtual) image size the tiles are cut from"""
+        m, lib, cam = self.model, _lib.load(), fc['camera']
+        vp = ctypes.c_void_p
+        origin, view_direction, n = fc['rays']
+        ticket = mailbox.next_ticket() if mailbox is not None else 0
+        _lib.check(lib.nrc_ngp_render_count_rays(
+            cam.width, cam.height, n, _lib.ptr(origin), _lib.ptr(view_direction), ctypes.cast(fc['center'], vp), ctypes.cast(fc['half'], vp),
+            float(cam.near_plane), float(cam.far_plane), int(tile_begin), nt, _lib.ptr(m.occupancy_bitfield), m.cascades, float(m.SCALE), float(fc['esf']),
+            m.RESOLUTION, self.MAX_SAMPLES, _lib.ptr(ws['ray_od']), _lib.ptr(ws['ray_t']), _lib.ptr(ws['ray_cnt']), _lib.ptr(ws['tile_rows']),
+            _lib.ptr(ws['tile_off']), _lib.ptr(ws['counter']), _lib.ptr(ws.get('ts_prov')), mailbox.ptr if mailbox is not None else None, ticket,
+            _lib.stream_of(ws['ray_od'])), 'ngp_render_count_rays')
         return ticket
 
     def _block_view_ptr(self):
@@ -533,7 +558,6 @@ class InstantNGPRenderer:
                 raise RuntimeError('render_image_fused: tile shards / fixed-capacity frames need the default HASHGRID_N_LEVELS = 16, HASHGRID_N_FEATURES_PER_LEVEL = 2, '
                                    'DIR_SH_ENCODING_DEGREE = 4; this model renders whole frames through the general path')
             return self._render_image_general(camera, c2w)
-        lib = _lib.load()
         dev = m.center.device
         total_tiles = self.n_image_tiles(camera)
         nt = total_tiles - tile_begin if n_tiles is None else int(n_tiles)
@@ -545,11 +569,6 @@ class InstantNGPRenderer:
         ws = self._fused_workspace(self._fused_ws, key, nt, hw, dev, images=True)
         if out is None:
             out = {'rgb': ws['rgb'], 'alpha': ws['alpha'], 'depth': ws['depth']}
-        st = _lib.stream_of(ws['ray_od'])
-        esf = fc['esf']
-        # the frame's one host read: the row count that sizes the sample buffers.  Through a host mailbox (the closing scan of the count pass stores
-        # the totals in mapped host memory and this thread polls them) when the runtime offers one -- no device-to-host copy, no stream wait:
-        # 42 -> ~10 us of idle GPU between the count pass and the write pass
         if row_capacity is not None:
             self._fused_count(fc, ws, tile_begin, nt)
             cap = int(row_capacity)
@@ -566,12 +585,24 @@ class InstantNGPRenderer:
             res = dict(out)
             res['counter'] = ws['counter']
             return res
+        return self._fused_counted_frame(self._fused_count, fc, ws, out, tile_begin, nt, return_stats, early_termination)
+
+    def _fused_counted_frame(self, count, fc: dict, ws: dict, out: dict, tile_begin: int, nt: int, return_stats: bool, early_termination) -> dict:
+        """A frame with its one host read, from the count pass on: `count` is _fused_count (the camera's rays) or _fused_count_rays (the caller's);
+        everything behind it reads rays from the workspace and is the same for both."""
+        m, lib = self.model, _lib.load()
+        dev = m.center.device
+        camera, esf = fc['camera'], fc['esf']
+        st = _lib.stream_of(ws['ray_od'])
+        # the frame's one host read: the row count that sizes the sample buffers.  Through a host mailbox (the closing scan of the count pass stores
+        # the totals in mapped host memory and this thread polls them) when the runtime offers one -- no device-to-host copy, no stream wait:
+        # 42 -> ~10 us of idle GPU between the count pass and the write pass
         mailbox = _lib.HostMailbox.for_device(dev) if self.COUNT_MAILBOX else None
         arena = self.ARENA_IN_PLACE and ws.get('ts_prov') is not None   # the parked samples are queried where they are: no copy into compact rows
         if mailbox is not None:
             mailbox.lock.acquire()    # one call in flight per mailbox
         try:
-            ticket = self._fused_count(fc, ws, tile_begin, nt, mailbox)
+            ticket = count(fc, ws, tile_begin, nt, mailbox)
             # what does not depend on the count is prepared before the wait (the sample buffers exist from the previous frame; a frame that needs
             # more regrows them below and marshals again)
             ready = None
@@ -636,6 +667,55 @@ class InstantNGPRenderer:
             res['n_rows'] = rows
             res['n_slots'] = rows * 64
             res['n_samples'] = n_samples
+        return res
+
+    @torch.no_grad()
+    def render_rays_fused(self, origin: torch.Tensor, view_direction: torch.Tensor, camera: Camera, custom_bg_color: torch.Tensor | None = None,
+                          image_shape: tuple[int, int] | None = None, early_termination: bool | str = 'auto',
+                          return_stats: bool = False) -> dict[str, torch.Tensor]:
+        """rgb (N,3) / alpha (N,) / depth (N,) of the caller's own rays through the fused image pipeline: render_image_fused with the count pass reading
+        row p of `origin` / `view_direction` (the direction as given, Renderer.py:40) where the camera path derives pixel p's ray -- any camera model,
+        any subset of rays.  near / far planes and the background come from `camera` (or custom_bg_color), as in render_rays; its size is not looked at.
+        image_shape = (H, W) with N == H * W: the rays are a row-major image (View.get_rays()) and are tiled as its 8x8 pixel blocks, like the camera
+        path.  None: a plain list -- tile T takes rays 64 T .. 64 T + 63 (a virtual image one tile wide).  Same values per ray either way; the tensors
+        are views of the renderer's workspace, valid until its next frame."""
+        m = self.model
+        from .ngp import default_layout
+        if not default_layout(m.encoding_xyz, m.color_mlp_with_encoding):   # (see render_image_fused: the tile kernels are built for the shipped layout)
+            return self.render_rays(origin, view_direction, camera, train_mode=False, custom_bg_color=custom_bg_color)
+        dev = m.center.device
+        n = int(origin.shape[0])
+        if tuple(origin.shape) != (n, 3) or tuple(view_direction.shape) != (n, 3):
+            raise RuntimeError(f'render_rays_fused: origin and view_direction must both be (N, 3), got {tuple(origin.shape)} and {tuple(view_direction.shape)}')
+        if image_shape is not None and int(image_shape[0]) * int(image_shape[1]) != n:
+            raise RuntimeError(f'render_rays_fused: image_shape {tuple(image_shape)} does not hold {n} rays')
+        if n == 0:
+            return {'rgb': torch.empty(0, 3, device=dev), 'alpha': torch.empty(0, device=dev), 'depth': torch.empty(0, device=dev)}
+        origin, view_direction = origin.float().contiguous(), view_direction.float().contiguous()
+        _lib.check_input(origin, 'origin', torch.float32)
+        _lib.check_input(view_direction, 'view_direction', torch.float32)
+        lib = _lib.load()
+        tw, th = int(lib.nrc_ngp_tile_width()), int(lib.nrc_ngp_tile_height())
+        if image_shape is not None:
+            height, width = int(image_shape[0]), int(image_shape[1])
+        else:
+            width, height = tw, th * ((n + tw * th - 1) // (tw * th))
+        # the (virtual) image the tiles are cut from, with the caller's depth range and background
+        bg = custom_bg_color if custom_bg_color is not None else camera.background_color
+        image = Camera(width=width, height=height, focal_x=camera.focal_x, focal_y=camera.focal_y, near_plane=camera.near_plane, far_plane=camera.far_plane,
+                       background_color=bg)
+        nt = self.n_image_tiles(image)
+        fc = self._frame_constants(image, None)
+        fc['rays'] = (origin, view_direction, n)
+        hw = fc['hw']   # (a list's virtual image is whole tiles: 64 * nt pixels, the first N of them the rays')
+        key = (nt, hw, str(dev))
+        if key not in self._fused_ws:
+            self._fused_ws = {}
+        ws = self._fused_workspace(self._fused_ws, key, nt, hw, dev, images=True)
+        out = {'rgb': ws['rgb'], 'alpha': ws['alpha'], 'depth': ws['depth']}
+        res = self._fused_counted_frame(self._fused_count_rays, fc, ws, out, 0, nt, return_stats, early_termination)
+        for k in out:
+            res[k] = res[k][:n]
         return res
 
     # ---------------------------------------------------------------- occupancy grid
