@@ -40,8 +40,10 @@ enum {
  * 10 = nrc_ngp_set_encoder_xcd_run (group 6) is new, every earlier signature is unchanged;
  * 11 = nrc_ngp_set_encoder_block_levels / _block_view, nrc_ngp_block_view_bytes, nrc_ngp_build_block_view (group 6: the cell-block view of the dense
  * levels) are new, every earlier signature is unchanged;
- * 12 = nrc_ngp_render_count_rays (group 6: the count pass for a caller's own ray list) is new, every earlier signature is unchanged. */
-#define NRC_ABI_VERSION 12
+ * 12 = nrc_ngp_render_count_rays (group 6: the count pass for a caller's own ray list) is new, every earlier signature is unchanged;
+ * 13 = nrc_grid_backward_input / nrc_sh_identity_backward_input (group 3: the encodings' derivatives with respect to their input) are new, every
+ * earlier signature is unchanged. */
+#define NRC_ABI_VERSION 13
 /* library identification; also used by the loader's symbol check */
 int nrc_abi_version(void);
 const char* nrc_build_info(void);
@@ -249,6 +251,23 @@ int nrc_grid_backward(const float* x01, int64_t M, const float* d_features, int3
 int nrc_grid_backward_live(const float* x01, int64_t M, const float* d_features, int32_t d_features_pair_major, int32_t n_levels,
                            int32_t log2_hashmap_size, int32_t base_resolution, float per_level_scale, float* grad_table, void* workspace,
                            const int32_t* n_samples_dev, nrc_stream_t stream);
+/* Gradients with respect to the encodings' INPUT (ABI 13): what tiny-cuda-nn's NetworkWithInputEncoding hands back for `x`, behind the d_in of
+ * nrc_nwie_backward.  Both validate before any launch (NRC_ERR_INVALID: M < 0, a null pointer with M > 0, n_features outside {2, 4},
+ * n_levels * n_features > 32, the pair-major layout with n_features = 4, input_ld < 19, a grid nrc_grid_layout refuses), use no atomics and no
+ * workspace, write every row of their output (nothing to zero) and give the same bits on every call.
+ *
+ * nrc_grid_backward_input: d_x01 (M,3) f32 = sum over levels and features of d_features * d(feature)/d(x01).  d_features is d_in in either layout
+ *   nrc_nwie_backward writes -- (M,32) f32 rows with column level * F + c (16-byte aligned), or pair-major [n_levels][M][2] (F = 2 only).  The
+ *   derivative is the piecewise one of the cell the forward pass interpolated in (cell and fractions: fmaf(scale, x, 0.5) in f32 and its floor) and
+ *   ignores the forward's final fp16 rounding of the feature, as tiny-cuda-nn does.  table_f16: the forward's table, (entries, F) fp16.  A row of
+ *   d_features that is all zero reads nothing from the table and yields zeros.
+ * nrc_sh_identity_backward_input: input_f16 (M,input_ld >= 19) fp16 rows [d01(3) | features(16)] as nrc_nwie_forward (encoding 1) read them; d_in
+ *   (M,32) f32, sample-major; d_input (M,19) f32: columns 0-2 = sum_c d_in[c] dSH_c/dd01 at the fp16 input (d = 2 d01 - 1, the 16 coefficients of
+ *   degree 4), columns 3-18 = d_in[16:32]. */
+int nrc_grid_backward_input(const float* x01, int64_t M, const float* d_features, int32_t d_features_pair_major, const void* table_f16,
+                            int32_t n_levels, int32_t n_features, int32_t log2_hashmap_size, int32_t base_resolution, float per_level_scale,
+                            float* d_x01, nrc_stream_t stream);
+int nrc_sh_identity_backward_input(const void* input_f16, int32_t input_ld, int64_t M, const float* d_in, float* d_input, nrc_stream_t stream);
 /* query_model (src/Methods/InstantNGP/Renderer.py:48-53) for TRAINING as one forward and one backward call instead of ~55 small
  * launches: world positions xyzs (M,3) / directions dirs (M,3) f32 -> sigmas (M), rgbs (M,3) f32 (what VolumeRenderer consumes), and
  * dL/dsigmas, dL/drgbs -> gradients of both parameter vectors (ACCUMULATED; caller zeroes; layout of the tinycudann modules).

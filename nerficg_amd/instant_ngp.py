@@ -188,8 +188,14 @@ class InstantNGPRenderer:
 
     def query(self, xyzs: torch.Tensor, dirs: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
         """(density, colour) of box-centred sample positions seen along unit directions.  With autograd on: one node that reaches both
-        parameter vectors (nerficg_amd.ngp.query_train); otherwise the two-kernel inference query."""
+        parameter vectors (nerficg_amd.ngp.query_train); otherwise the two-kernel inference query.  Positions or directions that require
+        grad take the module-by-module path of the reference's query_model (Renderer.py:48-53), whose modules differentiate their input."""
         m = self.model
+        if torch.is_grad_enabled() and (xyzs.requires_grad or dirs.requires_grad):
+            h = m.encoding_xyz((xyzs.float() - m.xyz_min) / m.xyz_size)
+            sigmas = VolumeRenderingCuda.TruncExp.apply(h[:, 0].float())
+            rgbs = m.color_mlp_with_encoding(torch.cat([(dirs.float() * 0.5 + 0.5).to(h.dtype), h], dim=-1), direction_gradient=True)
+            return sigmas, rgbs.float()
         if torch.is_grad_enabled() and m.encoding_xyz.params.requires_grad:
             return query_train(m.encoding_xyz, m.color_mlp_with_encoding, xyzs, dirs, *self._box())
         unit = ((xyzs.float() - m.xyz_min) / m.xyz_size).contiguous()
@@ -200,6 +206,19 @@ class InstantNGPRenderer:
         """exp (in f32) of the first output of the density network at box-centred positions."""
         m = self.model
         return m.encoding_xyz((xyzs - m.xyz_min) / m.xyz_size)[:, 0].float().exp()
+
+    def density_gradient(self, xyzs: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+        """(sigma (M) f32, d sigma / d xyzs (M, 3) f32) at box-centred positions: normals are -gradient / |gradient|.  The parameters are
+        detached: no table scatter runs and no weight gradient is handed out.  Computed as sigma * d(log sigma)/dx with the product in f32: the
+        network's backward pass carries its upstream gradient in fp16 behind a loss scale of 128, so d(sum sigma)/dx pushed through it directly
+        overflows (inf / NaN) wherever sigma exceeds 65504 / 128 -- inside any opaque surface; the log-density's upstream gradient is 1."""
+        m = self.model
+        x = xyzs.detach().float().requires_grad_(True)
+        with torch.enable_grad():
+            h0 = m.encoding_xyz((x - m.xyz_min) / m.xyz_size, detach_params=True)[:, 0].float()
+            grad, = torch.autograd.grad(h0.sum(), x)
+        sigma = h0.detach().exp()
+        return sigma, sigma[:, None] * grad
 
     # ---------------------------------------------------------------- rays
     def clip_rays(self, origin: torch.Tensor, view_direction: torch.Tensor, camera: Camera):
@@ -224,6 +243,8 @@ class InstantNGPRenderer:
             return self.render_rays_fused(origin, view_direction, camera, custom_bg_color=custom_bg_color)
         bg = (custom_bg_color if custom_bg_color is not None else camera.background_color).to(origin.device)
         step_growth = 1 / 256 if self.EXPONENTIAL_STEPS else 0.0
+        if train_mode and torch.is_grad_enabled() and (origin.requires_grad or view_direction.requires_grad):
+            return self._render_training_batch_for_rays(origin.float(), view_direction.float(), camera, bg, step_growth, noise)
         o, d, span = self.clip_rays(origin.float(), view_direction.float(), camera)
         if train_mode:
             return self._render_training_batch(o, d, span, bg, step_growth, noise)
@@ -247,6 +268,25 @@ class InstantNGPRenderer:
         if cut:   # fixed sample capacity: how many samples did not fit (device int64)
             out['sample_overflow'] = cut[0]
         return out
+
+    def _render_training_batch_for_rays(self, origin, view_direction, camera, bg, step_growth, noise):
+        """A training batch whose rays are being optimised (camera poses): the span of every ray comes from clip_rays, which is not differentiable
+        (as in the reference, where the intersector hands back no gradient); the samples come through VolumeRenderingV2.RayMarcher, whose backward
+        folds the per-sample position and direction gradients into the caller's origin / view_direction."""
+        if self.sample_capacity is not None:
+            raise RuntimeError('render_rays(train_mode=True) with rays that require grad sizes its sample buffers from the marched count: '
+                               'sample_capacity must be None (a fixed sample_capacity is the graph-captured iteration, which does not differentiate rays)')
+        m = self.model
+        with torch.no_grad():
+            _, _, span = self.clip_rays(origin, view_direction, camera)
+        o = origin - m.center
+        d = view_direction.contiguous()
+        jitter = torch.rand(o.shape[0], device=o.device) if noise is None else noise.to(torch.float32).contiguous()
+        rays_a, xyzs, dirs, deltas, ts, _ = VolumeRenderingCuda.RayMarcher.apply(o, d, span, m.occupancy_bitfield, m.cascades, m.SCALE, step_growth, m.RESOLUTION,
+                                                                                 self.MAX_SAMPLES, jitter)
+        sigmas, rgbs = self.query(xyzs, dirs)
+        rgb, alpha, depth = composite_over_background(sigmas, rgbs, deltas, ts, rays_a, bg, self.T_THRESHOLD)
+        return {'rgb': rgb, 'alpha': alpha, 'depth': depth, 'rm_samples': torch.tensor(xyzs.shape[0], dtype=torch.int32)}
 
     @torch.no_grad()
     def _render_ray_list(self, o, d, span, bg, step_growth):

@@ -6,7 +6,10 @@ src/Thirdparty/TinyCudaNN.py (`from tinycudann import *`) and uses in src/Method
         __call__((M, n_input_dims) CUDA tensor) -> (M, n_output_dims) fp16
     free_temporary_memory(), supports_jit_fusion()
 
-backed by hand-written gfx950 kernels (libnerficg_hip.so: nrc_nwie_forward / nrc_nwie_backward / nrc_grid_backward).
+backed by hand-written gfx950 kernels (libnerficg_hip.so: nrc_nwie_forward / nrc_nwie_backward / nrc_grid_backward).  Like tiny-cuda-nn the backward
+pass hands back the gradient of the INPUT too when the input requires grad -- the grid network's sample positions (nrc_grid_backward_input) always, the
+composite network's directions (nrc_sh_identity_backward_input) when the module's `direction_gradient` is set (default off: zeros there, as before;
+the identity dims always) -- and skips the table scatter when the parameters do not require grad; first derivatives only.
 Supported configurations = the family src/Methods/InstantNGP/Model.py:18-29,58-114 can instantiate from its yaml keys (anything else raises, by key name):
   encoding  {'otype':'Grid','type':'Hash', interpolation 'Linear', n_levels L, n_features_per_level F in {2, 4} with L x F <= 32, any
              log2_hashmap_size / base_resolution / per_level_scale}   with n_input_dims == 3
@@ -52,7 +55,7 @@ def _grid_offsets(cfg: dict) -> list[int]:
 
 class _NWIEFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, params, module):
+    def forward(ctx, x, params, module, direction_gradient=False):
         m = x.shape[0]
         dev = x.device
         lib = _lib.load()
@@ -78,7 +81,7 @@ class _NWIEFunction(torch.autograd.Function):
         if need_grad:
             ctx.module = module
             ctx.x_dtype = x.dtype
-            ctx.x_requires_grad = x.requires_grad
+            ctx.direction_gradient = bool(direction_gradient)
             ctx.save_for_backward(xin, out, save_in, save_acts, w16)
         return out
 
@@ -99,24 +102,38 @@ class _NWIEFunction(torch.autograd.Function):
         _lib.check(lib.nrc_nwie_backward(
             m, _lib.ptr(w16), module.n_hidden, module.out_act, _PAD, _lib.ptr(d_out), _lib.ptr(out), module._out_ld,
             _lib.ptr(save_in), _lib.ptr(save_acts), LOSS_SCALE, _lib.ptr(grad_params), _lib.ptr(d_in), pair_major, st), 'nwie_backward')
+        need_x, need_params = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         grad_x = None
         if module.encoding == 0:
             g = module.grid_cfg
+            cfg = (g['log2_hashmap_size'], g['base_resolution'], float(g['per_level_scale']))
             table_grad = grad_params[module._n_kernel_mlp:]
-            if general_grid:
-                _lib.check(lib.nrc_grid_backward_general(_lib.ptr(xin), m, _lib.ptr(d_in), g['n_levels'], module.n_features, g['log2_hashmap_size'],
-                                                         g['base_resolution'], float(g['per_level_scale']), _lib.ptr(table_grad), st), 'grid_backward_general')
-                return grad_x, module._grad_to_master(grad_params), None
-            gws = torch.empty(int(lib.nrc_grid_backward_ws_bytes(m, g['n_levels'], g['log2_hashmap_size'], g['base_resolution'], float(g['per_level_scale']))),
-                              dtype=torch.uint8, device=dev)
-            _lib.check(lib.nrc_grid_backward(_lib.ptr(xin), m, _lib.ptr(d_in), pair_major, g['n_levels'], g['log2_hashmap_size'],
-                                             g['base_resolution'], float(g['per_level_scale']), _lib.ptr(table_grad), _lib.ptr(gws), st), 'grid_backward')
-        elif ctx.x_requires_grad:
-            # gradient w.r.t. the identity-encoded dims; the SH-encoded direction dims get zeros (view directions are data,
-            # never optimised by the reference: Renderer.py:40 feeds rays.view_direction)
+            if not need_params:   # parameters detached or frozen: no table scatter
+                pass
+            elif general_grid:
+                _lib.check(lib.nrc_grid_backward_general(_lib.ptr(xin), m, _lib.ptr(d_in), g['n_levels'], module.n_features, *cfg, _lib.ptr(table_grad), st),
+                           'grid_backward_general')
+            else:
+                gws = torch.empty(int(lib.nrc_grid_backward_ws_bytes(m, g['n_levels'], *cfg)), dtype=torch.uint8, device=dev)
+                _lib.check(lib.nrc_grid_backward(_lib.ptr(xin), m, _lib.ptr(d_in), pair_major, g['n_levels'], *cfg, _lib.ptr(table_grad), _lib.ptr(gws), st),
+                           'grid_backward')
+            if need_x:
+                # d(features)/d(x) of the cell the forward pass interpolated in, contracted with the same d_in (the table of the forward pass: the saved copy)
+                grad_x = torch.empty(m, 3, dtype=torch.float32, device=dev)
+                _lib.check(lib.nrc_grid_backward_input(_lib.ptr(xin), m, _lib.ptr(d_in), pair_major, _lib.ptr(w16[module._n_kernel_mlp:]), g['n_levels'],
+                                                       module.n_features, *cfg, _lib.ptr(grad_x), st), 'grid_backward_input')
+                grad_x = grad_x.to(ctx.x_dtype)
+        elif need_x and ctx.direction_gradient:
+            # [d(SH)/d(d01) . d_in[:16] | d_in[16:32]]: the direction dims at the fp16 input the forward pass read, the identity dims as they are
+            grad_x = torch.empty(m, 19, dtype=torch.float32, device=dev)
+            _lib.check(lib.nrc_sh_identity_backward_input(_lib.ptr(xin), xin.shape[1], m, _lib.ptr(d_in), _lib.ptr(grad_x), st), 'sh_identity_backward_input')
+            grad_x = grad_x.to(ctx.x_dtype)
+        elif need_x:
+            # the module's default (direction_gradient off): gradient w.r.t. the identity-encoded dims; the SH-encoded direction dims get zeros (view
+            # directions are data, never optimised by the reference: Renderer.py:40 feeds rays.view_direction)
             grad_x = torch.zeros(m, xin.shape[1], dtype=ctx.x_dtype, device=dev)
             grad_x[:, 3:19] = d_in[:, 16:32].to(ctx.x_dtype)
-        return grad_x, module._grad_to_master(grad_params), None
+        return grad_x, (module._grad_to_master(grad_params) if need_params else None), None, None
 
 
 class NetworkWithInputEncoding(torch.nn.Module):
@@ -129,6 +146,9 @@ class NetworkWithInputEncoding(torch.nn.Module):
         self.seed = int(seed)
         self.jit_fusion = False
         self.loss_scale = LOSS_SCALE
+        # SH + identity network: whether x.grad carries the gradient of the three direction columns (nrc_sh_identity_backward_input) or zeros there.
+        # Off by default: callers of this module have always received zeros; set it (or pass forward(..., direction_gradient=True)) to optimise directions
+        self.direction_gradient = False
         # ---- network
         if network_config.get('otype') not in ('FullyFusedMLP', 'CutlassMLP'):
             raise RuntimeError(f"nerficg_amd.tinycudann: unsupported network otype {network_config.get('otype')!r}")
@@ -301,12 +321,17 @@ class NetworkWithInputEncoding(torch.nn.Module):
         """The configuration the fused InstantNGP paths are built for (16 x 2 grid / degree-4 SH): the general ones go through this module's forward."""
         return self._w0_cols is None and (self.encoding != 0 or (self.grid_cfg['n_levels'] == 16 and self.n_features == 2))
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, detach_params: bool = False, direction_gradient: bool | None = None) -> torch.Tensor:
+        """Two keywords that are not part of tiny-cuda-nn's interface.  detach_params: differentiate the input only -- the backward pass then runs no
+        table scatter and hands out no parameter gradient.  direction_gradient (SH + identity network; None = the module's `direction_gradient`
+        attribute, off by default): hand back d(SH)/d(d01) . d_in in the three direction columns of x.grad, as tiny-cuda-nn does; off, those
+        columns are zeros, as they have always been here (view directions are data in the reference)."""
         if not x.is_cuda:
             raise RuntimeError('nerficg_amd.tinycudann: input must be a CUDA tensor (no CPU fallback)')
         if x.dim() != 2 or x.shape[1] != self.n_input_dims:
             raise RuntimeError(f'nerficg_amd.tinycudann: expected input of shape (M, {self.n_input_dims}), got {tuple(x.shape)}')
-        out = _NWIEFunction.apply(x, self.params, self)
+        out = _NWIEFunction.apply(x, self.params.detach() if detach_params else self.params, self,
+                                  self.direction_gradient if direction_gradient is None else direction_gradient)
         return out[:, :self.n_output_dims]
 
     def extra_repr(self) -> str:
