@@ -42,8 +42,10 @@ enum {
  * levels) are new, every earlier signature is unchanged;
  * 12 = nrc_ngp_render_count_rays (group 6: the count pass for a caller's own ray list) is new, every earlier signature is unchanged;
  * 13 = nrc_grid_backward_input / nrc_sh_identity_backward_input (group 3: the encodings' derivatives with respect to their input) are new, every
+ * earlier signature is unchanged;
+ * 14 = nrc_gs_pose_partials_floats / nrc_gs_backward_pose_band / nrc_gs_camera_block_backward (group 4: gradients to the camera pose) are new, every
  * earlier signature is unchanged. */
-#define NRC_ABI_VERSION 13
+#define NRC_ABI_VERSION 14
 /* library identification; also used by the loader's symbol check */
 int nrc_abi_version(void);
 const char* nrc_build_info(void);
@@ -469,6 +471,30 @@ int nrc_gs_backward_aux_band(int32_t P, int32_t D, int32_t M, int32_t W, int32_t
                     float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
                     float* dL_dcov3D, float* dL_dsh, float* dL_dsh_rest, float* dL_dscale, float* dL_drot, float* grad_records,
                     int32_t records_clear, int32_t tile_row_begin, int32_t n_tile_rows, const float* dL_ddepth_alpha, nrc_stream_t stream);
+/* Gradients to the camera (ABI 14).  dL_dcamera: DEVICE float[35] in the layout of camera_dev without the background -- dL/dviewmatrix (16), dL/dprojmatrix (16),
+ * dL/dcampos (3) -- always fully written; viewmatrix[.][3] and projmatrix[.][2] (the column of the clip-space z, which the rasterizer does not use) receive exact
+ * zeros.  It is the gradient of the same scalar as the other outputs (the band's share for a band: the shares of a partition sum to the frame's), a reduction over
+ * all Gaussians of quantities the per-Gaussian backward forms anyway, computed by two extra launches between the blend backward and the per-Gaussian backward; the
+ * other outputs and the cleared records are bit for bit those of nrc_gs_backward_aux_band.  Deterministic: no float atomics, fixed summation order.
+ *   nrc_gs_pose_partials_floats : floats of the WORKSPACE pose_partials for P Gaussians (one 32-float slab per workgroup of the reduction; 16-byte aligned).
+ *   nrc_gs_backward_pose_band   : nrc_gs_backward_aux_band (dL_ddepth_alpha may be NULL) + pose_partials + dL_dcamera.  dL_dcamera == NULL: nrc_gs_backward_aux_band
+ *                       itself.  P == 0: 35 zeros.  The pose may come from the host arrays or from camera_dev.  NRC_ERR_INVALID before any HIP call for a bad band,
+ *                       for dL_dcamera without pose_partials and for a misaligned workspace.  There is no camera gradient in nrc_gs_backward_rest_step.
+ *   nrc_gs_camera_block_backward : the transpose of nrc_gs_camera_block -- dL_dcamera (35) -> dL_dc2w_out (12 floats = the (3, 4) rows of the pose), with the c2w_dev
+ *                       and proj_t_dev the block was made from. */
+int64_t nrc_gs_pose_partials_floats(int32_t P);
+int nrc_gs_backward_pose_band(int32_t P, int32_t D, int32_t M, int32_t W, int32_t H, const float* bg, const float* means3D, const float* shs,
+                    const float* shs_rest, int32_t raw_parameters, const float* opacities, const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
+                    const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix, const float* campos,
+                    const float* camera_dev, float tan_fovx, float tan_fovy, const int32_t* radii, const float* points_xy, const float* conic_opacity,
+                    const float* rgb, const uint8_t* clamped, const float* cov3D, const int32_t* point_list,
+                    const uint32_t* ranges, const float* splat_records, const uint32_t* tile_order, const uint32_t* n_contrib,
+                    const float* final_T, const float* dL_dpix,
+                    float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
+                    float* dL_dcov3D, float* dL_dsh, float* dL_dsh_rest, float* dL_dscale, float* dL_drot, float* grad_records,
+                    int32_t records_clear, int32_t tile_row_begin, int32_t n_tile_rows, const float* dL_ddepth_alpha, float* pose_partials,
+                    float* dL_dcamera, nrc_stream_t stream);
+int nrc_gs_camera_block_backward(const float* c2w_dev, const float* proj_t_dev, const float* dL_dcamera, float* dL_dc2w_out, nrc_stream_t stream);
 
 /* =====================================================================================================
  * Group 5 -- ray generation (replaces PerspectiveCamera.compute_local_ray_directions src/Cameras/Perspective.py:64-94

@@ -2043,6 +2043,223 @@ __global__ void __launch_bounds__(PBW_BLOCK) k_preprocess_bw(int P, GsCam cam_ar
     }
 }
 
+// ------------------------------------------------------------------------------------------------ 7b. camera (pose) backward
+// dL/d(viewmatrix, projmatrix, campos) of a frame: a reduction over all Gaussians of quantities preprocess_bw_one forms on its way to dL/dmean3D and
+// drops.  With V[k][j] = view[j + 4k], Pm[k][c] = proj[c + 4k], m the mean, gz = record slot [9]:
+//   t_j = sum_k m_k V[k][j] + V[3][j]                    ->  dV[k][j] += m_k dt_j,  dV[3][j] += dt_j        (dt = (dtx, dty, dtz + gz))
+//   Mx[k] = J00 V[k][0] + J02 V[k][2], My likewise       ->  dV[k][0] += J00 dMx[k],  dV[k][1] += J11 dMy[k],  dV[k][2] += J02 dMx[k] + J12 dMy[k]
+//   mh_c = sum_k m_k Pm[k][c] + Pm[3][c]                 ->  dPm[k][c] += m_k dmh_c,  dPm[3][c] += dmh_c    (dmh = (mw g2x, mw g2y, 0, -(mul1 g2x + mul2 g2y)))
+//   SH direction = (m - campos) / |m - campos|           ->  dcampos -= (the SH part of dmean)
+// V[.][3] and Pm[.][2] receive nothing: 27 live sums.  The record is READ, not cleared (k_preprocess_bw, launched behind this kernel, still does that), and
+// every intermediate is formed by the statements of preprocess_bw_one in their order from the same inputs.
+// Slab layout (POSE_SLAB floats per workgroup): [3k + j] dV[k][j] (k 0..3, j 0..2) | [12 + 3k + cc] dPm[k][c], c = (0, 1, 3)[cc] | [24..26] dcampos | [27..31] zero.
+#define POSE_BLOCK PBW_BLOCK     // the chunk and the SH staging of k_preprocess_bw
+#define POSE_SUMS 27
+#define POSE_SLAB 32
+#ifndef POSE_GRID_MAX
+#define POSE_GRID_MAX 1536       // workgroups = slabs: 6 per CU, what 3 waves per SIMD (156-163 VGPRs) and 26 KB of LDS hold at once; 1024 / 1536 / 2048 -> 89 / 83 / 91 us at 1 M Gaussians
+#endif
+__device__ __forceinline__ void pose_bw_one(int i, const GsCam& cam, const float* __restrict__ means3D, const float* sh_row, int use_sh,
+                                            const uint8_t* __restrict__ clamped, const float* __restrict__ cov3D, const float* __restrict__ grad_rec,
+                                            float* acc) {
+    const float4 r0 = *reinterpret_cast<const float4*>(grad_rec + (size_t)i * GREC), r1 = *reinterpret_cast<const float4*>(grad_rec + (size_t)i * GREC + 4);
+    const float2 r2 = *reinterpret_cast<const float2*>(grad_rec + (size_t)i * GREC + 8);
+    const float r2x = r2.x;
+    const float gcol[3] = {r0.x, r0.y, r0.z};
+    const float mean[3] = {means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2]};
+    float c3[6];
+#pragma unroll
+    for (int k = 0; k < 6; k++) c3[k] = cov3D[6 * i + k];
+    const float fx = cam.focal_x, fy = cam.focal_y;
+    const float* vm = cam.view;
+    float t[3], tc[3], Mx[3], My[3], sx[3], sy[3];
+    int gmx, gmy;
+    xform43(mean, vm, t);
+    proj_jac(t, fx, fy, cam.tan_fovx, cam.tan_fovy, vm, Mx, My, tc, &gmx, &gmy);
+    const float j00 = fx / tc[2], j02 = -(fx * tc[0]) / (tc[2] * tc[2]);   // the entries proj_jac builds Mx / My from
+    const float j11 = fy / tc[2], j12 = -(fy * tc[1]) / (tc[2] * tc[2]);
+    sym_mul(c3, Mx, sx); sym_mul(c3, My, sy);
+    const float a = Mx[0] * sx[0] + Mx[1] * sx[1] + Mx[2] * sx[2] + 0.3f;
+    const float b = Mx[0] * sy[0] + Mx[1] * sy[1] + Mx[2] * sy[2];
+    const float c = My[0] * sy[0] + My[1] * sy[1] + My[2] * sy[2] + 0.3f;
+    const float gcx = r1.z, gcy = r1.w, gcz = r2x;
+    const float denom = a * c - b * b;
+    const float denom2inv = 1.0f / (denom * denom + 0.0000001f);
+    float dL_da = 0, dL_db = 0, dL_dc = 0;
+    if (denom2inv != 0) {
+        dL_da = denom2inv * (-c * c * gcx + 2 * b * c * gcy + (denom - a * c) * gcz);
+        dL_dc = denom2inv * (-a * a * gcz + 2 * a * b * gcy + (denom - a * c) * gcx);
+        dL_db = denom2inv * 2 * (b * c * gcx - (denom + 2 * b * b) * gcy + a * b * gcz);
+    }
+    float dMx[3], dMy[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) { dMx[k] = 2 * sx[k] * dL_da + sy[k] * dL_db; dMy[k] = 2 * sy[k] * dL_dc + sx[k] * dL_db; }
+    float dJ00 = 0, dJ02 = 0, dJ11 = 0, dJ12 = 0;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        dJ00 += vm[0 + 4 * k] * dMx[k]; dJ02 += vm[2 + 4 * k] * dMx[k];
+        dJ11 += vm[1 + 4 * k] * dMy[k]; dJ12 += vm[2 + 4 * k] * dMy[k];
+    }
+    const float tz = 1.0f / tc[2], tz2 = tz * tz, tz3 = tz2 * tz;
+    const float dtx = (float)gmx * -fx * tz2 * dJ02;
+    const float dty = (float)gmy * -fy * tz2 * dJ12;
+    const float dtz = -fx * tz2 * dJ00 - fy * tz2 * dJ11 + (2 * fx * tc[0]) * tz3 * dJ02 + (2 * fy * tc[1]) * tz3 * dJ12;
+    const float dtzg = dtz + r2.y;   // the depth map's dL/dz enters t_z directly
+    const float* pm = cam.proj;
+    float mh[4];
+    xform44(mean, pm, mh);
+    const float mw = 1.0f / (mh[3] + 0.0000001f);
+    const float mul1 = mh[0] * mw * mw, mul2 = mh[1] * mw * mw;
+    const float g2x = r1.x, g2y = r1.y;
+    const float dmh[3] = {mw * g2x, mw * g2y, -(mul1 * g2x + mul2 * g2y)};   // columns 0, 1, 3 (column 2, the clip-space z, is not used)
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        acc[3 * k + 0] += j00 * dMx[k] + mean[k] * dtx;
+        acc[3 * k + 1] += j11 * dMy[k] + mean[k] * dty;
+        acc[3 * k + 2] += j02 * dMx[k] + j12 * dMy[k] + mean[k] * dtzg;
+#pragma unroll
+        for (int cc = 0; cc < 3; cc++) acc[12 + 3 * k + cc] += mean[k] * dmh[cc];
+    }
+    acc[9] += dtx; acc[10] += dty; acc[11] += dtzg;
+#pragma unroll
+    for (int cc = 0; cc < 3; cc++) acc[21 + cc] += dmh[cc];
+    if (use_sh) {
+        const float dir0[3] = {mean[0] - cam.campos[0], mean[1] - cam.campos[1], mean[2] - cam.campos[2]};
+        const float sum2 = dir0[0] * dir0[0] + dir0[1] * dir0[1] + dir0[2] * dir0[2];
+        const float len = sqrtf(sum2);
+        const float x = dir0[0] / len, y = dir0[1] / len, z = dir0[2] / len;
+        const uint8_t cl = clamped[i];
+        float dRGB[3], ddir[3] = {0, 0, 0};
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) dRGB[ch] = ((cl >> ch) & 1) ? 0.f : gcol[ch];
+        float Bx[16], By[16], Bz[16];
+#pragma unroll
+        for (int k = 0; k < 16; k++) { Bx[k] = 0; By[k] = 0; Bz[k] = 0; }
+        const int D = cam.D;
+        if (D > 0) {
+            By[1] = -SH_C1;
+            Bz[2] = SH_C1;
+            Bx[3] = -SH_C1;
+            if (D > 1) {
+                const float xx = x * x, yy = y * y, zz = z * z;
+                const float c0 = SH_C2[0], c1 = SH_C2[1], c2 = SH_C2[2], c3_ = SH_C2[3], c4 = SH_C2[4];
+                Bx[4] = c0 * y; By[4] = c0 * x;
+                By[5] = c1 * z; Bz[5] = c1 * y;
+                Bx[6] = c2 * -2 * x; By[6] = c2 * -2 * y; Bz[6] = c2 * 4 * z;
+                Bx[7] = c3_ * z; Bz[7] = c3_ * x;
+                Bx[8] = c4 * 2 * x; By[8] = c4 * -2 * y;
+                if (D > 2) {
+                    const float e0 = SH_C3[0], e1 = SH_C3[1], e2 = SH_C3[2], e3 = SH_C3[3], e4 = SH_C3[4], e5 = SH_C3[5], e6 = SH_C3[6];
+                    Bx[9] = e0 * 6 * x * y; By[9] = e0 * (3 * xx - 3 * yy);
+                    Bx[10] = e1 * y * z; By[10] = e1 * x * z; Bz[10] = e1 * x * y;
+                    Bx[11] = e2 * -2 * x * y; By[11] = e2 * (4 * zz - xx - 3 * yy); Bz[11] = e2 * 8 * y * z;
+                    Bx[12] = e3 * -6 * x * z; By[12] = e3 * -6 * y * z; Bz[12] = e3 * (6 * zz - 3 * xx - 3 * yy);
+                    Bx[13] = e4 * (4 * zz - 3 * xx - yy); By[13] = e4 * -2 * x * y; Bz[13] = e4 * 8 * x * z;
+                    Bx[14] = e5 * 2 * x * z; By[14] = e5 * -2 * y * z; Bz[14] = e5 * (xx - yy);
+                    Bx[15] = e6 * (3 * xx - 3 * yy); By[15] = e6 * -6 * x * y;
+                }
+            }
+        }
+        const int nb = (D + 1) * (D + 1);
+        for (int k = 0; k < nb; k++)
+#pragma unroll
+            for (int ch = 0; ch < 3; ch++) {
+                const float shv = sh_row[3 * k + ch];
+                ddir[0] += Bx[k] * shv * dRGB[ch];
+                ddir[1] += By[k] * shv * dRGB[ch];
+                ddir[2] += Bz[k] * shv * dRGB[ch];
+            }
+        const float inv32 = 1.0f / sqrtf(sum2 * sum2 * sum2);
+        acc[24] -= ((sum2 - dir0[0] * dir0[0]) * ddir[0] - dir0[1] * dir0[0] * ddir[1] - dir0[2] * dir0[0] * ddir[2]) * inv32;
+        acc[25] -= (-dir0[0] * dir0[1] * ddir[0] + (sum2 - dir0[1] * dir0[1]) * ddir[1] - dir0[2] * dir0[1] * ddir[2]) * inv32;
+        acc[26] -= (-dir0[0] * dir0[2] * ddir[0] - dir0[1] * dir0[2] * ddir[1] + (sum2 - dir0[2] * dir0[2]) * ddir[2]) * inv32;
+    }
+}
+
+// Workgroup = POSE_BLOCK lanes walking 128-Gaussian chunks with the stride of the grid; the 27 sums stay in registers until the walk is over, then ONE reduction:
+// DPP butterfly inside each row of 16 lanes, the eight rows of the workgroup through LDS in a fixed order, one slab of plain stores.  No float atomics: 35
+// addresses under thousands of workgroups is the shape the memory side serialises, and the sum would depend on the arrival order.  A chunk without a visible
+// Gaussian (the whole workgroup agrees) skips the SH staging and the arithmetic.
+template <bool SPLIT>   // the SH form: one (P, M, 3) tensor, or dc + rest
+__global__ void __launch_bounds__(POSE_BLOCK) k_pose_bw(int P, GsCam cam_arg, const float* __restrict__ pose, const float* __restrict__ means3D, const float* __restrict__ shs,
+                                                        const float* __restrict__ shs_rest, int use_sh, const int32_t* __restrict__ radii, const uint8_t* __restrict__ clamped,
+                                                        const float* __restrict__ cov3D, const float* __restrict__ grad_rec, float* __restrict__ partials) {
+    __shared__ float s_sh[POSE_BLOCK * (3 * PBW_MAXM + 1)];
+    __shared__ float s_red[POSE_BLOCK / 16][POSE_SLAB];
+    const GsCam cam = cam_with_pose(cam_arg, pose);
+    const int row_len = 3 * cam.M, pitch = row_len + 1;
+    const float* sh_row = s_sh + threadIdx.x * pitch;
+    float acc[POSE_SUMS];
+#pragma unroll
+    for (int k = 0; k < POSE_SUMS; k++) acc[k] = 0.f;
+    const int64_t stride = (int64_t)gridDim.x * POSE_BLOCK;
+    for (int64_t first64 = (int64_t)blockIdx.x * POSE_BLOCK; first64 < P; first64 += stride) {
+        const int first = (int)first64, i = first + (int)threadIdx.x;
+        const bool visible = i < P && radii[i] > 0;
+        if (!__syncthreads_or(visible ? 1 : 0)) continue;      // (the barrier also separates this chunk's staging from the previous chunk's reads)
+        if (use_sh) {
+            sh_rows_copy<true, (SPLIT ? PBW_SHB_U : SHB_U), SPLIT>(s_sh, pitch, row_len, min(POSE_BLOCK, P - first), (size_t)first, const_cast<float*>(shs),
+                                                                  const_cast<float*>(shs_rest), POSE_BLOCK);
+            __syncthreads();
+        }
+        if (visible) pose_bw_one(i, cam, means3D, sh_row, use_sh, clamped, cov3D, grad_rec, acc);
+    }
+    const int row = threadIdx.x >> 4;
+#pragma unroll
+    for (int k = 0; k < POSE_SUMS; k++) {
+        float v = dpp_add<0x140>(acc[k], acc[k]);
+        v = dpp_add<0x141>(v, v);
+        v = dpp_add<0x1b>(v, v);
+        v = dpp_add<0xb1>(v, v);
+        if ((threadIdx.x & 15) == 0) s_red[row][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < POSE_SLAB) {
+        float v = 0.f;
+        if (threadIdx.x < POSE_SUMS) {
+#pragma unroll
+            for (int r = 0; r < POSE_BLOCK / 16; r++) v += s_red[r][threadIdx.x];
+        }
+        partials[(size_t)blockIdx.x * POSE_SLAB + threadIdx.x] = v;
+    }
+}
+
+// One workgroup: the slabs added in a fixed order in f64, written in the layout of the camera block (dV 16 | dPm 16 | dcampos 3); the entries no Gaussian
+// reaches (V[.][3], Pm[.][2]) are written as exact zeros.  n_slabs == 0 (no Gaussians): 35 zeros.  32 groups of 32 lanes: group g adds slabs g, g + 32, ...
+// (eight loads in flight), then lane k adds the 32 group sums of its entry.  A second launch, not a last-workgroup ticket in k_pose_bw: no fences there.
+#define POSE_CAMERA_FLOATS 35
+#define POSE_FIN_GROUPS 32
+__global__ void __launch_bounds__(POSE_FIN_GROUPS * POSE_SLAB) k_pose_finish(int n_slabs, const float* __restrict__ partials, float* __restrict__ dL_dcamera) {
+    __shared__ double s_sum[POSE_FIN_GROUPS][POSE_SLAB];
+    const int g = threadIdx.x >> 5, c = threadIdx.x & 31;
+    double a = 0.0;
+    int s = g;
+    for (; s + 7 * POSE_FIN_GROUPS < n_slabs; s += 8 * POSE_FIN_GROUPS) {
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) v[u] = partials[(size_t)(s + u * POSE_FIN_GROUPS) * POSE_SLAB + c];
+#pragma unroll
+        for (int u = 0; u < 8; u++) a += (double)v[u];
+    }
+    for (; s < n_slabs; s += POSE_FIN_GROUPS) a += (double)partials[(size_t)s * POSE_SLAB + c];
+    s_sum[g][c] = a;
+    __syncthreads();
+    const int k = threadIdx.x;
+    if (k < POSE_CAMERA_FLOATS) {
+        int src = -1;
+        if (k < 16) { if ((k & 3) < 3) src = 3 * (k >> 2) + (k & 3); }
+        else if (k < 32) { const int cc = (k - 16) & 3; if (cc != 2) src = 12 + 3 * ((k - 16) >> 2) + (cc == 3 ? 2 : cc); }
+        else src = 24 + (k - 32);
+        double v = 0.0;
+        if (src >= 0) {
+#pragma unroll
+            for (int r = 0; r < POSE_FIN_GROUPS; r++) v += s_sum[r][src];
+        }
+        dL_dcamera[k] = (float)v;
+    }
+}
+int pose_slabs(int P) { return (int)(P > 0 ? (nrc_cdiv(P, POSE_BLOCK) < POSE_GRID_MAX ? nrc_cdiv(P, POSE_BLOCK) : POSE_GRID_MAX) : 0); }
+
 // slices = waves; all of them should be resident at once: 160 KB of LDS per CU, (4 B x n_tiles) per wave, 256 CUs
 // binning workspace (u32 words): [keyA P][valA P][rectA P][keyB P][valB P][rectB P][header RS_HDR_WORDS][status 4 x nblk x 256][group totals 4 x ngroups x 256] -- the depth pre-sort --
 // [rowtot gy][roff gy][nitems gy][ioff gy][meta 4][tcount n_tiles][cnt2 item_cap x gx][spans 2 x cap]
@@ -2100,6 +2317,29 @@ __global__ void k_camera_block(const float* __restrict__ c2w, const float* __res
         out[16 + k] = a;
     }
     if (k < 3) { out[32 + k] = c2w[4 * k + 3]; out[35 + k] = bg3 ? bg3[k] : 0.f; }
+}
+// The transpose of k_camera_block: dL/d(camera block) (dV 16 | dPm 16 | dcampos 3) -> dL/dc2w (3, 4), one wave.
+//   proj = view @ P^T            ->  dV[r][j] += sum_c dPm[r][c] proj_t[4 j + c]
+//   view[r][c] = c2w[r][c]       ->  dc2w[r][c] = dV[r][c] - dV[3][c] c2w[r][3]                (r, c < 3; the second term: view[3][c] = -(R^T t)_c)
+//   campos = t, view[3][.]       ->  dc2w[r][3] = dcampos[r] - sum_c dV[3][c] c2w[r][c]
+__global__ void k_camera_block_bw(const float* __restrict__ c2w, const float* __restrict__ proj_t, const float* __restrict__ dcam, float* __restrict__ dc2w) {
+    __shared__ float dv[16];
+    const int k = threadIdx.x;
+    if (k < 16) {
+        const int r = k >> 2, j = k & 3;
+        float a = dcam[k];
+#pragma unroll
+        for (int c = 0; c < 4; c++) a = fmaf(dcam[16 + 4 * r + c], proj_t[4 * j + c], a);
+        dv[k] = a;
+    }
+    __syncthreads();
+    if (k < 12) {
+        const int r = k >> 2, c = k & 3;
+        float v;
+        if (c < 3) v = dv[4 * r + c] - dv[12 + c] * c2w[4 * r + 3];
+        else v = dcam[32 + r] - (dv[12] * c2w[4 * r] + dv[13] * c2w[4 * r + 1] + dv[14] * c2w[4 * r + 2]);
+        dc2w[k] = v;
+    }
 }
 
 int make_cam(GsCam& cam, int W, int H, int D, int M, const float* view, const float* proj, const float* campos, const float* camera_dev, float tanx,
@@ -2368,13 +2608,21 @@ static int gs_backward_impl(int32_t P, int32_t D, int32_t M, int32_t W, int32_t 
                     const float* splat_records, const uint32_t* tile_order, const uint32_t* n_contrib, const float* final_T, const float* dL_dpix,
                     float* dL_dmean2D, float* dL_dconic,
                     float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dsh_rest, float* dL_dscale,
-                    float* dL_drot, float* grad_records, int32_t records_clear, nrc_stream_t stream, RestAdam ra, int32_t n_rows, const float* dL_ddepth_alpha) {
+                    float* dL_drot, float* grad_records, int32_t records_clear, nrc_stream_t stream, RestAdam ra, int32_t n_rows, const float* dL_ddepth_alpha,
+                    float* pose_partials = nullptr, float* dL_dcamera = nullptr) {
     GsCam cam;
     const int rc = make_cam(cam, W, H, D, M, viewmatrix_host, projmatrix_host, campos_host, camera_dev, tan_fovx, tan_fovy, scale_modifier, raw_parameters);
     if (rc != NRC_OK) return rc;
     if (P < 0 || (!bg_host && !camera_dev)) return NRC_ERR_INVALID;
     const float bg[3] = {bg_host ? bg_host[0] : 0.f, bg_host ? bg_host[1] : 0.f, bg_host ? bg_host[2] : 0.f};
-    if (P == 0) return NRC_OK;
+    if (dL_dcamera && (!pose_partials || ra.p)) return NRC_ERR_INVALID;   // (there is no camera gradient in the form that steps `rest`)
+    if (P == 0) {
+        if (dL_dcamera) {   // no Gaussians: the camera gradient is 35 zeros
+            hipLaunchKernelGGL(k_pose_finish, dim3(1), dim3(POSE_FIN_GROUPS * POSE_SLAB), 0, (hipStream_t)stream, 0, (const float*)pose_partials, dL_dcamera);
+            NRC_LAUNCH_CHECK();
+        }
+        return NRC_OK;
+    }
     if (!means3D || !radii || !points_xy || !conic_opacity || !rgb || !clamped || !cov3D || !point_list || !ranges || !n_contrib || !final_T ||
         !dL_dpix || !dL_dmean2D || !dL_dopacity || !dL_dmean3D || !dL_dcov3D || !grad_records || (reinterpret_cast<uintptr_t>(grad_records) & 63u))
         return NRC_ERR_INVALID;
@@ -2398,6 +2646,17 @@ static int gs_backward_impl(int32_t P, int32_t D, int32_t M, int32_t W, int32_t 
         hipLaunchKernelGGL(k_render_bw<false>, dim3(cam.gx * n_rows), dim3(256), 0, s, cam, ranges, point_list, (const float4*)splat_records, tile_order, bg[0], bg[1], bg[2],
                            camera_dev, n_contrib, final_T, dL_dpix, grad_records, (const float*)nullptr);
     NRC_STAGE(s, "k_render_bw");
+    if (dL_dcamera) {
+        // the camera gradient reads the records the blend backward just filled, before k_preprocess_bw consumes and clears them
+        const int n_slabs = pose_slabs(P);
+        if (shs_rest) hipLaunchKernelGGL(k_pose_bw<true>, dim3(n_slabs), dim3(POSE_BLOCK), 0, s, P, cam, camera_dev, means3D, shs, shs_rest, use_sh, radii, clamped, cov3D,
+                                         (const float*)grad_records, pose_partials);
+        else hipLaunchKernelGGL(k_pose_bw<false>, dim3(n_slabs), dim3(POSE_BLOCK), 0, s, P, cam, camera_dev, means3D, shs, shs_rest, use_sh, radii, clamped, cov3D,
+                                (const float*)grad_records, pose_partials);
+        NRC_STAGE(s, "k_pose_bw");
+        hipLaunchKernelGGL(k_pose_finish, dim3(1), dim3(POSE_FIN_GROUPS * POSE_SLAB), 0, s, n_slabs, (const float*)pose_partials, dL_dcamera);
+        NRC_STAGE(s, "k_pose_finish");
+    }
 #define GS_PBW_ARGS P, cam, camera_dev, means3D, shs, shs_rest, opacities, use_sh, scales, rotations, use_sr, radii, clamped, cov3D, grad_records, dL_dmean2D, dL_dconic, dL_dcolor, \
                     dL_dmean3D, dL_dcov3D, dL_dsh, dL_dsh_rest, dL_dscale, dL_drot, dL_dopacity, ra
     if (ra.p) hipLaunchKernelGGL(k_preprocess_bw<2>, dim3(nrc_cdiv(P, PBW_BLOCK)), dim3(PBW_BLOCK), 0, s, GS_PBW_ARGS);
@@ -2457,6 +2716,40 @@ int nrc_gs_backward_aux_band(int32_t P, int32_t D, int32_t M, int32_t W, int32_t
                             ranges, splat_records, tile_order, n_contrib, final_T, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
                             dL_dsh_rest, dL_dscale, dL_drot, grad_records, records_clear, stream, RestAdam{nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, 0.f, 1.f, 1.f}, n_tile_rows,
                             dL_ddepth_alpha);
+}
+
+/* floats of the slab workspace `pose_partials` of nrc_gs_backward_pose_band for P Gaussians (at least one slab) */
+int64_t nrc_gs_pose_partials_floats(int32_t P) {
+    if (P < 0) return NRC_ERR_INVALID;
+    const int n = pose_slabs(P);
+    return (int64_t)(n > 0 ? n : 1) * POSE_SLAB;
+}
+int nrc_gs_backward_pose_band(int32_t P, int32_t D, int32_t M, int32_t W, int32_t H, const float* bg_host, const float* means3D, const float* shs,
+                    const float* shs_rest, int32_t raw_parameters, const float* opacities, const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
+                    const float* cov3D_precomp, const float* viewmatrix_host, const float* projmatrix_host, const float* campos_host,
+                    const float* camera_dev, float tan_fovx, float tan_fovy, const int32_t* radii, const float* points_xy, const float* conic_opacity,
+                    const float* rgb, const uint8_t* clamped, const float* cov3D, const int32_t* point_list, const uint32_t* ranges,
+                    const float* splat_records, const uint32_t* tile_order, const uint32_t* n_contrib, const float* final_T, const float* dL_dpix,
+                    float* dL_dmean2D, float* dL_dconic,
+                    float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dsh_rest, float* dL_dscale,
+                    float* dL_drot, float* grad_records, int32_t records_clear, int32_t tile_row_begin, int32_t n_tile_rows, const float* dL_ddepth_alpha,
+                    float* pose_partials, float* dL_dcamera, nrc_stream_t stream) {
+    if (!gs_band_ok(H, tile_row_begin, n_tile_rows)) return NRC_ERR_INVALID;
+    if (dL_dcamera && (!pose_partials || (reinterpret_cast<uintptr_t>(pose_partials) & 15u))) return NRC_ERR_INVALID;
+    NRC_ENTER();
+    return gs_backward_impl(P, D, M, W, H, bg_host, means3D, shs, shs_rest, raw_parameters, opacities, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
+                            viewmatrix_host, projmatrix_host, campos_host, camera_dev, tan_fovx, tan_fovy, radii, points_xy, conic_opacity, rgb, clamped, cov3D, point_list,
+                            ranges, splat_records, tile_order, n_contrib, final_T, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
+                            dL_dsh_rest, dL_dscale, dL_drot, grad_records, records_clear, stream, RestAdam{nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, 0.f, 1.f, 1.f}, n_tile_rows,
+                            dL_ddepth_alpha, dL_dcamera ? pose_partials : nullptr, dL_dcamera);
+}
+
+int nrc_gs_camera_block_backward(const float* c2w_dev, const float* proj_t_dev, const float* dL_dcamera, float* dL_dc2w_out, nrc_stream_t stream) {
+    if (!c2w_dev || !proj_t_dev || !dL_dcamera || !dL_dc2w_out) return NRC_ERR_INVALID;
+    NRC_ENTER();
+    hipLaunchKernelGGL(k_camera_block_bw, dim3(1), dim3(64), 0, (hipStream_t)stream, c2w_dev, proj_t_dev, dL_dcamera, dL_dc2w_out);
+    NRC_LAUNCH_CHECK();
+    return NRC_OK;
 }
 
 /* nrc_gs_backward whose preprocessing backward applies the optimizer's Adam step to the `rest` SH tensor itself (shs_rest_param = the tensor passed as shs_rest in the

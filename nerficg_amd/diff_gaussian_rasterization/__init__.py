@@ -155,11 +155,17 @@ def _opt(t):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, sh_rest=None, raw=False, rest_step=None, tile_rows=None,
-                depth_alpha=False):
+                depth_alpha=False, viewmatrix=None, projmatrix=None, campos=None):
         rs = raster_settings
         lib = _lib.load()
         band = check_tile_rows(tile_rows, rs.image_height)
         depth_alpha = bool(depth_alpha)
+        # camera_grad: the three pose tensors of the settings arrive as tensor inputs as well, so that autograd asks this function for their gradients
+        ctx.camera = None
+        if viewmatrix is not None:     # (rasterize_gaussians has refused rest_step by now)
+            needs = tuple(ctx.needs_input_grad[14:17])
+            if any(needs):
+                ctx.camera = (needs, tuple((tuple(t.shape), t.dtype, t.device) for t in (viewmatrix, projmatrix, campos)))
         if depth_alpha and rest_step is not None:
             raise RuntimeError('return_depth_alpha together with rest_step: the backward pass that steps the `rest` SH tensor (nrc_gs_backward_rest_step) takes the '
                                'colour gradient only -- there is no depth-and-alpha form of it; render without rest_step and let the optimizer take that step')
@@ -398,7 +404,22 @@ class _RasterizeGaussians(torch.autograd.Function):
         dsh_rest = torch.empty(n1, M - 1, 3, dtype=f32, device=dev) if has_rest and rest_step is None else None
         dscale = torch.empty(n1, 3, dtype=f32, device=dev) if has_sr else None
         drot = torch.empty(n1, 4, dtype=f32, device=dev) if has_sr else None
-        if rest_step is not None:
+        dcam = None
+        if ctx.camera is not None:
+            # the same backward with two extra launches between the blend backward and the per-Gaussian backward: dL/d(viewmatrix | projmatrix | campos) as float[35]
+            b0, bn = ctx.band if ctx.band is not None else (0, (H + 15) // 16)
+            partials = torch.empty(int(lib.nrc_gs_pose_partials_floats(P)), dtype=f32, device=dev)
+            dcam = torch.empty(35, dtype=f32, device=dev)
+            _lib.check(lib.nrc_gs_backward_pose_band(
+                P, D, M, W, H, None, _lib.ptr(means3D), _lib.ptr(sh if has_sh else None), _lib.ptr(sh_rest if has_rest else None), int(raw),
+                _lib.ptr(opac if raw else None), _lib.ptr(col if has_col else None),
+                _lib.ptr(sc if has_sr else None), float(rs.scale_modifier), _lib.ptr(rot if has_sr else None), _lib.ptr(cov if has_cov else None),
+                None, None, None, _lib.ptr(cam_block), float(rs.tanfovx), float(rs.tanfovy), _lib.ptr(radii), _lib.ptr(points_xy), _lib.ptr(conic_opacity),
+                _lib.ptr(rgb), _lib.ptr(clamped), _lib.ptr(cov3D), _lib.ptr(point_list), _lib.ptr(ranges), _lib.ptr(splat), _lib.ptr(tile_order), _lib.ptr(n_contrib), _lib.ptr(final_T),
+                _lib.ptr(g), _lib.ptr(dmean2D), None, _lib.ptr(dopacity), _lib.ptr(dcolor), _lib.ptr(dmean3D), _lib.ptr(dcov3D),
+                _lib.ptr(dsh), _lib.ptr(dsh_rest), _lib.ptr(dscale), _lib.ptr(drot), _lib.ptr(grad_records), int(records_clear), b0, bn, _lib.ptr(g_aux),
+                _lib.ptr(partials), _lib.ptr(dcam), _lib.stream_of(g)), 'gs_backward_pose_band')
+        elif rest_step is not None:
             # the optimizer step of the `rest` SH tensor inside the preprocessing backward (nrc_gs_backward_rest_step): no gradient tensor for it
             param, m_rest, v_rest, lr, beta1, beta2, eps, bc1, bc2 = rest_step.take()
             if param.data_ptr() != sh_rest.data_ptr():
@@ -447,13 +468,32 @@ class _RasterizeGaussians(torch.autograd.Function):
         cut = (lambda t: t) if P == n1 else (lambda t: t[:P])     # (whole buffers when nothing is cut: a gradient that is not a view can be adopted as .grad without a copy)
         return (cut(dmean3D), cut(dmean2D), cut(dsh) if has_sh else None, cut(dcolor) if has_col else None,
                 cut(dopacity).reshape(ctx.opacity_shape), cut(dscale) if has_sr else None, cut(drot) if has_sr else None,
-                cut(dcov3D) if has_cov else None, None, cut(dsh_rest) if dsh_rest is not None else None, None, None, None, None)
+                cut(dcov3D) if has_cov else None, None, cut(dsh_rest) if dsh_rest is not None else None, None, None, None, None) + _camera_grads(ctx.camera, dcam)
+
+
+def _camera_grads(camera, dcam):
+    """The backward's float[35] as the gradients of viewmatrix, projmatrix and campos, each in its tensor's own shape, dtype and device (None where none is needed)."""
+    if camera is None:
+        return ()
+    needs, like = camera
+    parts = (dcam[:16], dcam[16:32], dcam[32:35])
+    return tuple(part.reshape(shape).to(device=device, dtype=dtype) if need else None for need, part, (shape, dtype, device) in zip(needs, parts, like))
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, sh_rest=None, raw=False, rest_step=None, tile_rows=None,
-                        return_depth_alpha=False):
+                        return_depth_alpha=False, camera_grad=False):
     """`tile_rows` = (begin, n): render and differentiate the band of 16-pixel tile rows [begin, begin + n) only (see GaussianRasterizer.forward); None: the frame.
-    `return_depth_alpha`: (image, radii, depth, alpha) instead of (image, radii) -- see GaussianRasterizer.forward."""
+    `return_depth_alpha`: (image, radii, depth, alpha) instead of (image, radii) -- see GaussianRasterizer.forward.
+    `camera_grad`: gradients to raster_settings.viewmatrix / projmatrix / campos, for those that require grad -- see GaussianRasterizer.forward."""
+    if camera_grad:
+        if rest_step is not None:
+            raise RuntimeError('camera_grad together with rest_step: the backward pass that steps the `rest` SH tensor (nrc_gs_backward_rest_step) has no camera '
+                               'gradient; render without rest_step and let the optimizer take that step')
+        rs = raster_settings
+        pose = (rs.viewmatrix, rs.projmatrix, rs.campos)
+        if torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in pose):
+            return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, sh_rest, raw, None,
+                                             None if tile_rows is None else tuple(int(v) for v in tile_rows), bool(return_depth_alpha), *pose)
     if return_depth_alpha:
         return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, sh_rest, raw, rest_step,
                                          None if tile_rows is None else tuple(int(v) for v in tile_rows), True)
@@ -476,7 +516,7 @@ class GaussianRasterizer(torch.nn.Module):
             return z > 0.2
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, shs_rest=None,
-                raw_parameters=False, rest_step=None, tile_rows=None, return_depth_alpha=False):
+                raw_parameters=False, rest_step=None, tile_rows=None, return_depth_alpha=False, camera_grad=False):
         """The reference's call (Renderer.py:75-81) plus two keyword extensions for callers that own the model tensors: `shs_rest` -- `shs` is then
         (`rest_step`, round 6: an object whose take() returns (parameter, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, bc1, bc2) -- the backward pass then applies
         the optimizer's Adam step to shs_rest itself and returns no gradient for it: nerficg_amd.gaussian_splatting.RestStep)
@@ -492,7 +532,12 @@ class GaussianRasterizer(torch.nn.Module):
         w_i = alpha_i T_i and background 0: depth = sum w_i z_i with z_i the view-space depth the sort orders by (ACCUMULATED, not normalised: divide by alpha
         for an expected depth), alpha = sum w_i = 1 - T_final.  Both are differentiable (a map that takes no part in the loss counts as a zero gradient); image,
         radii and everything the backward saves are bit for bit those of the call without the flag.  Works with every parameter form above, with `tile_rows`
-        (band rows written, zero elsewhere) and inside fixed_capacity; not together with `rest_step` (RuntimeError)."""
+        (band rows written, zero elsewhere) and inside fixed_capacity; not together with `rest_step` (RuntimeError).
+        `camera_grad=True`: the settings' `viewmatrix`, `projmatrix` and `campos` that require grad receive a gradient, each in its own shape, dtype and device
+        (`bg` and the intrinsics receive none).  Everything else the call returns is bit for bit that of the call without the flag, and every other gradient comes from the same
+        launches on the same per-Gaussian sums: the backward pass runs two more launches (a reduction over the Gaussians in a fixed order, no atomics) and reads nothing back.  Works with every parameter
+        form above, with `tile_rows` (the band's share), `return_depth_alpha` and inside fixed_capacity; not together with `rest_step` (RuntimeError).  When none
+        of the three requires grad the flag changes nothing.  A pose tensor: nerficg_amd.gaussian_splatting.make_raster_settings chains the gradient on to c2w."""
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
         if ((scales is None or rotations is None) and cov3D_precomp is None) or ((scales is not None or rotations is not None) and cov3D_precomp is not None):
@@ -500,4 +545,4 @@ class GaussianRasterizer(torch.nn.Module):
         empty = torch.Tensor([])
         return rasterize_gaussians(means3D, means2D, empty if shs is None else shs, empty if colors_precomp is None else colors_precomp, opacities,
                                    empty if scales is None else scales, empty if rotations is None else rotations,
-                                   empty if cov3D_precomp is None else cov3D_precomp, self.raster_settings, shs_rest, raw_parameters, rest_step, tile_rows, return_depth_alpha)
+                                   empty if cov3D_precomp is None else cov3D_precomp, self.raster_settings, shs_rest, raw_parameters, rest_step, tile_rows, return_depth_alpha, camera_grad)

@@ -73,10 +73,35 @@ def _projection_transposed(cam: PerspectiveCamera, device) -> torch.Tensor:
     return hit
 
 
+class _CameraBlock(torch.autograd.Function):
+    """The rasterizer's camera block (view | view @ P^T | position | background, float[38]) of a device pose that requires grad: forward nrc_gs_camera_block,
+    backward its transpose nrc_gs_camera_block_backward (one launch of one wave each).  The background receives no gradient."""
+
+    @staticmethod
+    def forward(ctx, pose, proj_t, bg):
+        from . import _lib
+        block = torch.empty(38, dtype=torch.float32, device=pose.device)
+        _lib.check(_lib.load().nrc_gs_camera_block(_lib.ptr(pose), _lib.ptr(proj_t), _lib.ptr(bg), _lib.ptr(block), _lib.stream_of(block)), 'gs_camera_block')
+        ctx.save_for_backward(pose, proj_t)
+        return block
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_block):
+        from . import _lib
+        pose, proj_t = ctx.saved_tensors
+        d_block = d_block.to(torch.float32).contiguous()
+        d_pose = torch.zeros_like(pose)      # ((4, 4): the last row is not read by the forward)
+        _lib.check(_lib.load().nrc_gs_camera_block_backward(_lib.ptr(pose), _lib.ptr(proj_t), _lib.ptr(d_block), _lib.ptr(d_pose), _lib.stream_of(d_pose)),
+                   'gs_camera_block_backward')
+        return d_pose, None, None
+
+
 def make_raster_settings(cam: PerspectiveCamera, c2w, sh_degree: int, scale_modifier: float = 1.0, device='cuda'):
     """GaussianSplatting/Renderer.py:60-74: viewmatrix = w2c.T, projmatrix = w2c.T @ P.T, tanfov = size / focal / 2.  `c2w`: a (4,4) / (3,4)
     array, or a device tensor -- the pose then never visits the host (w2c.T = [[R, 0], [-(R^T t)^T, 1]] is assembled by torch on the
-    device), which is what a recorded training step needs: it re-reads the tensor on every replay."""
+    device), which is what a recorded training step needs: it re-reads the tensor on every replay.  A device tensor that requires grad: the
+    settings' viewmatrix / projmatrix / campos carry the graph back to it (rasterize with camera_grad=True)."""
     from .diff_gaussian_rasterization import GaussianRasterizationSettings
     if torch.is_tensor(c2w) and c2w.is_cuda:
         # one launch writes the rasterizer's whole camera block (view | view @ P^T | position | background); the settings' tensors are views of it and
@@ -85,10 +110,15 @@ def make_raster_settings(cam: PerspectiveCamera, c2w, sh_degree: int, scale_modi
         from .diff_gaussian_rasterization import adopt_camera_block
         pose = c2w.to(device=device, dtype=torch.float32).contiguous()
         bg = cam.background_color.to(device=device, dtype=torch.float32).contiguous()
-        block = torch.empty(38, dtype=torch.float32, device=pose.device)
-        _lib.check(_lib.load().nrc_gs_camera_block(_lib.ptr(pose), _lib.ptr(_projection_transposed(cam, device)), _lib.ptr(bg), _lib.ptr(block), _lib.stream_of(block)),
-                   'gs_camera_block')
-        adopt_camera_block(block)
+        if pose.requires_grad and torch.is_grad_enabled():
+            if pose.shape[-2:] not in ((3, 4), (4, 4)) or pose.dim() != 2:
+                raise RuntimeError(f'make_raster_settings: c2w (3, 4) or (4, 4) expected, got {tuple(pose.shape)}')
+            block = _CameraBlock.apply(pose, _projection_transposed(cam, device), bg)
+        else:
+            block = torch.empty(38, dtype=torch.float32, device=pose.device)
+            _lib.check(_lib.load().nrc_gs_camera_block(_lib.ptr(pose), _lib.ptr(_projection_transposed(cam, device)), _lib.ptr(bg), _lib.ptr(block), _lib.stream_of(block)),
+                       'gs_camera_block')
+        adopt_camera_block(block.detach())      # (the rasterizer recognises the block by its address)
         return GaussianRasterizationSettings(
             image_height=cam.height, image_width=cam.width, tanfovx=cam.width / cam.focal_x * 0.5, tanfovy=cam.height / cam.focal_y * 0.5,
             bg=block[35:38], scale_modifier=scale_modifier, viewmatrix=block[:16].view(4, 4), projmatrix=block[16:32].view(4, 4), sh_degree=sh_degree,
@@ -434,8 +464,10 @@ class RestStep:
 
 
 def render_image_training(gaussians: Gaussians, cam: PerspectiveCamera, c2w: np.ndarray, fuse_rest_step: bool | None = None,
-                          band: tuple[int, int] | None = None, depth_alpha: bool = False) -> dict[str, torch.Tensor]:
-    """GaussianSplatting/Renderer.py:51-86.  depth_alpha: the outputs gain 'alpha' and 'depth', (1, H, W) like 'rgb' is (3, H, W), both differentiable: alpha = 1 - T of
+                          band: tuple[int, int] | None = None, depth_alpha: bool = False, camera_grad: bool | None = None) -> dict[str, torch.Tensor]:
+    """GaussianSplatting/Renderer.py:51-86.  camera_grad (default None: on exactly when `c2w` is a tensor that requires grad): the loss is differentiated with
+    respect to the pose as well (the rasterizer's `camera_grad`; pose refinement, tracking against a frozen model) -- refused together with the fused f_rest step
+    (RuntimeError), like a band.  depth_alpha: the outputs gain 'alpha' and 'depth', (1, H, W) like 'rgb' is (3, H, W), both differentiable: alpha = 1 - T of
     the blend, depth = (sum w z) / (alpha + 1e-6), the normalisation of InstantNGP/Renderer.py:82 (the rasterizer's `return_depth_alpha`).  Refused together with the
     fused f_rest step (RuntimeError), like a band.  band = (tile_row_begin, n_tile_rows): this call renders and differentiates that band of 16-pixel tile rows of
     the frame only (the rasterizer's `tile_rows`; parallel.tile_row_band): 'rgb' is zero outside the band, the gradients are the band's share, and the
@@ -450,6 +482,10 @@ def render_image_training(gaussians: Gaussians, cam: PerspectiveCamera, c2w: np.
     if band is not None and fuse:
         raise RuntimeError('render_image_training: band= together with the fused f_rest step -- the backward pass of a band holds that band\'s share of the '
                            'gradient only, and Adam applied to a partial gradient is not the optimizer\'s step; sum the shares over the bands and step then')
+    camera_grad = bool(torch.is_tensor(c2w) and c2w.requires_grad) if camera_grad is None else bool(camera_grad)
+    if camera_grad and fuse:
+        raise RuntimeError('render_image_training: camera_grad together with the fused f_rest step -- the backward pass that steps f_rest has no camera gradient '
+                           '(the rasterizer refuses camera_grad with rest_step); leave fuse_rest_step off for frames whose pose is optimised')
     if depth_alpha and fuse:
         raise RuntimeError('render_image_training: depth_alpha= together with the fused f_rest step -- the backward pass that steps f_rest takes the colour '
                            'gradient only (the rasterizer refuses return_depth_alpha with rest_step); leave fuse_rest_step off for frames with a depth or alpha loss')
@@ -460,12 +496,12 @@ def render_image_training(gaussians: Gaussians, cam: PerspectiveCamera, c2w: np.
     if gaussians.baked:  # a baked model holds activated values
         image, radii, *aux = rasterizer(means3D=positions, means2D=viewspace_points, shs=gaussians.get_features_dc, shs_rest=gaussians.get_features_rest,
                                         opacities=gaussians.get_opacities, scales=gaussians.get_scales, rotations=gaussians.get_rotations, tile_rows=band,
-                                        return_depth_alpha=depth_alpha)
+                                        return_depth_alpha=depth_alpha, camera_grad=camera_grad)
     else:  # raw parameters straight into the kernels: no get_features concatenation, no separate exp / sigmoid / normalize passes (a25)
         rest_step = RestStep(gaussians) if fuse and not getattr(gaussians.optimizer, 'capturable', False) and not torch.cuda.is_current_stream_capturing() and torch.is_grad_enabled() and gaussians._features_rest.requires_grad and gaussians._features_rest.shape[1] > 0 and torch.is_tensor(c2w) else None
         image, radii, *aux = rasterizer(means3D=positions, means2D=viewspace_points, shs=gaussians._features_dc, shs_rest=gaussians._features_rest,
                                         opacities=gaussians._opacities, scales=gaussians._scales, rotations=gaussians._rotations, raw_parameters=True, rest_step=rest_step,
-                                        tile_rows=band, return_depth_alpha=depth_alpha)
+                                        tile_rows=band, return_depth_alpha=depth_alpha, camera_grad=camera_grad)
     outputs = _TrainingOutputs({'rgb': image, 'viewspace_points': viewspace_points, 'radii': radii})
     if depth_alpha:
         outputs.update(_depth_alpha_outputs(aux[0], aux[1], True))
