@@ -2125,7 +2125,7 @@ __global__ void __launch_bounds__(OWN_THREADS) k_grid_bwd_owned_q(const float* _
 //                    on a training batch) into an 8 K-entry LDS slice, then a plain read-modify-write flush.  The slice accumulates
 //                    64-bit FIXED POINT: LDS float atomics run at 0.32 lane-operations per clock and CU on this chip, integer ones
 //                    (32 or 64 bit) at 1.33 (tools/micro/lds_atomics.hip) -- with f32 atomics this kernel took 380 us, 320 of them in
-//                    ds_add_f32.  scale = 2^(62 - ceil log2 max|g| - ceil log2 (2 M + 1)): no overflow whatever the collisions, LSB <=
+//                    ds_add_f32.  scale = 2^min(127, 62 - ceil log2 max|g| - ceil log2 (2 M + 1)): no overflow whatever the collisions, LSB <=
 //                    max|g| 2^-41 for M = 264 K, and the sums no longer depend on the order of the atomics: the hashed levels' gradient
 //                    is bit-reproducible.
 // (A first version with 4-byte (sample, pair) records still gathered positions / gradients per record -- spread over all samples, i.e.
@@ -2238,13 +2238,16 @@ __global__ void __launch_bounds__(OWN_THREADS) k_gb_split(const float* __restric
 #pragma unroll
             for (int w = 0; w < OWN_THREADS / 64; w++) { before += w < (t >> 6) ? wave_tot[w] : 0u; all += wave_tot[w]; }
             const uint32_t start = before + incl - cnt;
+            // start <= 1024 * 4 * 16 = 65536, count <= 4096.  65536 itself is reached: a workgroup whose 1024 samples are live on 16 bucketed levels fills
+            // its region, and every empty run behind its last record starts there -- one past the 16-bit field, so that the word read back as
+            // {start 0, count 1} and the accumulate added the workgroup's first record into that bucket.  An empty run is published as start 0.
             if (b < b_hi) {
                 gbase[b] = start;
-                seg[(int64_t)b * n_wg + v] = start | (c0 << 16);   // start < 1024 * 4 * 16 = 65536, count <= 4096
+                seg[(int64_t)b * n_wg + v] = (c0 ? start : 0u) | (c0 << 16);
             }
             if (b + 1 < b_hi) {
                 gbase[b + 1] = start + c0;
-                seg[(int64_t)(b + 1) * n_wg + v] = (start + c0) | (c1 << 16);
+                seg[(int64_t)(b + 1) * n_wg + v] = (c1 ? start + c0 : 0u) | (c1 << 16);
             }
             region += all;
         }
@@ -2306,14 +2309,17 @@ __global__ void __launch_bounds__(GBA_THREADS) k_gb_accumulate(GridCfg g, Bucket
     // run, the items past the 64th cost a second, nearly empty round of LDS atomics each): item p belongs to run u = #{t : p >= pre[t]}.
     // The records of batch m + 1 are requested before the atomics of batch m are issued (loads and LDS atomics of a wave overlap).
     struct Batch { uint32_t start[UNR], pre[UNR + 1]; int w0; uint4 r[PASSES]; };
-    // float -> 64-bit fixed point, round to nearest even, |v| < 2^62: six VALU instructions instead of the ~25 of the generic f32 -> i64
+    // float -> 64-bit fixed point, round to nearest even, |v| < 2^62: nine VALU instructions instead of the ~25 of the generic f32 -> i64
     // conversion (there is no such instruction; four conversions per record made this kernel VALU-bound).  rndne is exact, hi = floor(v / 2^32)
-    // fits an i32, v - hi 2^32 is an exact integer in [0, 2^32).
+    // fits an i32, v - hi 2^32 is an integer in [0, 2^32).  As an f32 it is exact only from |v| = 2^31 on (v is then a multiple of 2^8, and so
+    // is the difference); below, a NEGATIVE v gives 2^32 - |v|, which needs up to 32 bits and was rounded to a multiple of 2^8 -- up to 128
+    // LSB lost per negative addend (tests/test_gpu_grid_table_grad.py found it).  There the low word is the i32 conversion of v itself.
     auto to_fixed = [](float v) -> unsigned long long {
         const float vr = __builtin_rintf(v);
         const float hf = __builtin_floorf(vr * 2.3283064365386963e-10f);
         const int hi = (int)hf;
-        const uint32_t lo = (uint32_t)__builtin_fmaf(-hf, 4294967296.f, vr);
+        const uint32_t lo_big = (uint32_t)__builtin_fmaf(-hf, 4294967296.f, vr);
+        const uint32_t lo = __builtin_fabsf(vr) < 2147483648.f ? (uint32_t)(int)vr : lo_big;
         return ((unsigned long long)(uint32_t)hi << 32) | lo;
     };
     auto add_record = [&](const uint4& rr) {
@@ -2388,7 +2394,9 @@ __global__ void __launch_bounds__(GBA_THREADS) k_gb_accumulate(GridCfg g, Bucket
     int e_max = 0, e_cnt = 0;
     frexpf(mx > 0.f ? mx : 1.f, &e_max);      // mx < 2^e_max
     frexpf((float)(2 * M + 1), &e_cnt);        // 2 M + 1 <= 2^e_cnt (an entry receives at most 2 M values of <= mx)
-    scale = ldexpf(1.f, 62 - e_max - e_cnt);
+    // (the exponent stops at 127: the scale of a level whose largest |gradient| lies below 2^-(65 + e_cnt) was +inf, 1 / scale 0 and the level's
+    // gradient 0 where the f32 paths return the tiny values; such a level resolves 2^-127, its sums stay far below 2^62)
+    scale = ldexpf(1.f, min(127, 62 - e_max - e_cnt));
     for (int m = 0; m < n_batches; m++) {
         if (m + 1 < n_batches) open_batch(m + 1, nxt);
         NRC_PROBE_NW(10 + 2 * m);

@@ -17,22 +17,25 @@ prof() {
 }
 # MODE=gs (first argument): only the runs that cover the kernels of gs_raster.hip -- the bench command (all durations), the 3DGS frame at both sizes and the
 # 3DGS counter passes; tools/make_profile_summary.py ROUND gs_raster.hip then carries the other kernels' counters over (their sources are unchanged).
+# MODE=ngp: the reverse -- everything but the 3DGS-only runs, for a change confined to the InstantNGP sources (tools/make_profile_summary.py ROUND ngp_net.hip).
 MODE=${1:-all}
 # the full bench command (bench.py --full --steps 20 --warmup 5, every leg): the per-kernel averages of the InstantNGP kernels must agree with the bench line
 prof 900 $O/bench_stats.log --kernel-trace --stats --output-format csv -d $O/bench_stats -- python3 $R/bench.py --full --steps 20 --warmup 5
 # the 3DGS kernels at ONE size (the bench command runs 1 M and 6 M Gaussians through the same kernel names)
+if [ "$MODE" != ngp ]; then
 prof 300 $O/gs_stats.log --kernel-trace --stats --output-format csv -d $O/gs_stats -- python3 $R/tools/bench_gs.py 1000000 20
 prof 300 $O/gs6_stats.log --kernel-trace --stats --output-format csv -d $O/gs6_stats -- python3 $R/tools/bench_gs.py 6000000 5
-if [ "$MODE" = all ]; then
+fi
+if [ "$MODE" != gs ]; then
 prof 600 $O/train_stats.log --kernel-trace --stats --output-format csv -d $O/train_stats -- python3 $R/tools/bench_train.py 2200 20
 # the fused training iteration (nerficg_amd.ngp_trainer): 4 warm-up + 3 x 20 iterations, the next batch marched ahead
 prof 600 $O/fused_stats.log --kernel-trace --stats --output-format csv -d $O/fused_stats -- python3 $R/tools/bench_train_fused.py 2200 20 1 0 0 1
 fi
 for set in "FETCH_SIZE" "WRITE_SIZE" "TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum GRBM_GUI_ACTIVE TA_BUSY_avr" "TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum" "SQ_WAVES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_VALU_MFMA_MOPS_F16 SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES"; do
   tag=$(echo $set | tr ' ' '_' | cut -c1-32)
-  [ "$MODE" = all ] && prof 300 $O/pmc_$tag.log --pmc $set --kernel-trace --output-format csv -d $O/pmc_$tag -- python3 $R/tools/bench_query.py 2
-  prof 300 $O/pmcgs_$tag.log --pmc $set --kernel-trace --output-format csv -d $O/pmcgs_$tag -- python3 $R/tools/bench_gs.py 1000000 2
-  [ "$MODE" = all ] && prof 300 $O/pmctr_$tag.log --pmc $set --kernel-trace --output-format csv -d $O/pmctr_$tag -- python3 $R/tools/bench_train.py 2200 5
-  [ "$MODE" = all ] && prof 300 $O/pmcfu_$tag.log --pmc $set --kernel-trace --output-format csv -d $O/pmcfu_$tag -- python3 $R/tools/bench_train_fused.py 2200 3 0 0 0 1
+  [ "$MODE" != gs ] && prof 300 $O/pmc_$tag.log --pmc $set --kernel-trace --output-format csv -d $O/pmc_$tag -- python3 $R/tools/bench_query.py 2
+  [ "$MODE" != ngp ] && prof 300 $O/pmcgs_$tag.log --pmc $set --kernel-trace --output-format csv -d $O/pmcgs_$tag -- python3 $R/tools/bench_gs.py 1000000 2
+  [ "$MODE" != gs ] && prof 300 $O/pmctr_$tag.log --pmc $set --kernel-trace --output-format csv -d $O/pmctr_$tag -- python3 $R/tools/bench_train.py 2200 5
+  [ "$MODE" != gs ] && prof 300 $O/pmcfu_$tag.log --pmc $set --kernel-trace --output-format csv -d $O/pmcfu_$tag -- python3 $R/tools/bench_train_fused.py 2200 3 0 0 0 1
 done
 find $O -name "*.db" -delete; find $O -name "*_agent_info.csv" -delete; find $O -path "*_stats/*" -name "*kernel_trace.csv" -delete; du -sh $O; ls -la $O | head -50; tail -5 $O/bench_stats.log
