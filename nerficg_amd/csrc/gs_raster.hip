@@ -1698,12 +1698,17 @@ __global__ void __launch_bounds__(256) k_render_bw(GsCam cam, const uint32_t* __
         auto deposit = [&](int jj, int j, float mine) {
             if (q_has && jj < n_mine) {
                 const float y = __builtin_amdgcn_fmed3f(mine * q_scale, -0x1p61f, 0x1p61f);
-                // float -> two's-complement 64-bit, truncating (a bias of half a step of 2^-25 ... 2^-51), in six instructions: the generic
+                // float -> two's-complement 64-bit, truncating (a bias of half a step of 2^-25 ... 2^-51), in seven instructions: the generic
                 // (long long) conversion is thirteen -- a seventh of this loop's VALU instructions with the reduction.  t is an integer-valued float,
-                // hi = floor(t / 2^32) fits an i32, t - hi 2^32 is an exact integer in [0, 2^32) (the low mantissa bits of t): same bits as the cast.
+                // hi = floor(t / 2^32) fits an i32.  The low word is t mod 2^32, taken from t - rint(t / 2^32) 2^32: that lies in [-2^31, 2^31], keeps
+                // only low mantissa bits of t (exact), and has the two's-complement low word of t.  (t - hi 2^32 itself lies in [0, 2^32) but needs
+                // up to 32 significant bits for a NEGATIVE t -- t = -5 gives 2^32 - 5, which f32 rounds to 2^32: the low word lost 8 bits, up to 128
+                // steps per deposit, 2^-18 instead of 2^-25 of the pixel gradient on the conic sums; tests/test_gpu_gs_grad_budget.py.)  A remainder of
+                // exactly +2^31 saturates to 2^31 - 1: one step, at |t| >= 2^31, where t's own last bit is worth 128 steps or more.
                 const float t = __builtin_truncf(y);
-                const float hf = __builtin_floorf(t * 0x1p-32f);
-                const uint32_t lo32 = (uint32_t)__builtin_fmaf(-hf, 0x1p32f, t);
+                const float hs = t * 0x1p-32f;
+                const float hf = __builtin_floorf(hs);
+                const uint32_t lo32 = (uint32_t)(int)__builtin_fmaf(-__builtin_rintf(hs), 0x1p32f, t);
                 atomicAdd(&s_acc[j][q_col], ((unsigned long long)(uint32_t)(int)hf << 32) | lo32);
             }
         };
@@ -1712,8 +1717,9 @@ __global__ void __launch_bounds__(256) k_render_bw(GsCam cam, const uint32_t* __
             if (l16 == 15 && jj < n_mine) {
                 const float y = __builtin_amdgcn_fmed3f(z_sum * ldexpf(1.0f, BW_S_COLOR - gexp), -0x1p61f, 0x1p61f);
                 const float t = __builtin_truncf(y);
-                const float hf = __builtin_floorf(t * 0x1p-32f);
-                const uint32_t lo32 = (uint32_t)__builtin_fmaf(-hf, 0x1p32f, t);
+                const float hs = t * 0x1p-32f;
+                const float hf = __builtin_floorf(hs);
+                const uint32_t lo32 = (uint32_t)(int)__builtin_fmaf(-__builtin_rintf(hs), 0x1p32f, t);
                 atomicAdd(&s_acc[j][NQ - 1], ((unsigned long long)(uint32_t)(int)hf << 32) | lo32);
             }
         };

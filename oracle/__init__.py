@@ -20,7 +20,7 @@ _P = ctypes.c_void_p
 
 
 def build(force: bool = False) -> Path:
-    srcs = sorted(HERE.glob('*.c'))
+    srcs = sorted(HERE.glob('*.c')) + sorted(HERE.glob('*.h'))
     if force or not LIB.exists() or any(s.stat().st_mtime > LIB.stat().st_mtime for s in srcs + [HERE / 'Makefile']):
         subprocess.run(['make', '-C', str(HERE), '-B', 'liboracle.so'], check=True, capture_output=True)
     return LIB
@@ -423,6 +423,27 @@ def _gs_backward(st, dL_dpix):
        ft(a['tan_fovx']), ft(a['tan_fovy']), _p(st.radii), _p(st.points_xy), _p(st.conic_opacity), _p(st.rgb), _p(st.clamped), _p(st.cov3D),
        _p(st.point_list), _p(st.ranges), _p(st.n_contrib), _p(st.final_T), _p(g), _p(out['mean2D']), _p(out['conic']), _p(out['opacity']),
        _p(out['color']), _p(out['mean3D']), _p(out['cov3D']), _p(out['sh']), _p(out['scale']), _p(out['rot']))
+    return out
+
+
+def gs_gaussian_backward(st, mean2D, conic, opacity, color):
+    """Stage (2) of gs_backward alone (gs_oracle_impl.h: gaussian_backward): the per-Gaussian sums of the blending backward -- mean2D (P,3), conic (P,4),
+    opacity (P), color (P,3), as gs_backward returns them -- chained to the leaves.  Returns the same dict as gs_backward; the four inputs pass through.
+    Gaussians are independent: row i of every output depends on row i of the inputs alone."""
+    dtype = st.dtype
+    pre = 'gsf_' if dtype == np.float32 else 'gsd_'
+    ft = ctypes.c_float if dtype == np.float32 else ctypes.c_double
+    P, M = st.P, max(st.M, 1)
+    out = dict(mean2D=np.array(mean2D, dtype).reshape(P, 3), conic=np.array(conic, dtype).reshape(P, 4), opacity=np.array(opacity, dtype).reshape(P),
+               color=np.array(color, dtype).reshape(P, 3), mean3D=np.zeros((P, 3), dtype), cov3D=np.zeros((P, 6), dtype), sh=np.zeros((P, M, 3), dtype),
+               scale=np.zeros((P, 3), dtype), rot=np.zeros((P, 4), dtype))
+    a = st.inputs
+    fn = getattr(lib(), pre + 'gaussian_backward')
+    fn.restype = None
+    fn(_i(P), _i(st.D), _i(st.M), _i(st.W), _i(st.H), _p(a['means3D']), _p(a['shs']), _p(a['colors_precomp']), _p(a['scales']), ft(a['scale_modifier']),
+       _p(a['rotations']), _p(a['cov3D_precomp']), _p(a['viewmatrix']), _p(a['projmatrix']), _p(a['campos']), ft(a['tan_fovx']), ft(a['tan_fovy']),
+       _p(st.radii), _p(st.clamped), _p(st.cov3D), _p(out['mean2D']), _p(out['conic']), _p(out['color']), _p(out['mean3D']), _p(out['cov3D']),
+       _p(out['sh']), _p(out['scale']), _p(out['rot']))
     return out
 
 

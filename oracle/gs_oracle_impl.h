@@ -286,18 +286,13 @@ void FN(render_source_order)(int W, int H, const REAL* bg, const REAL* points_xy
 }
 
 /* ---- backward ---- */
-void FN(backward)(int P, int D, int M, int W, int H, const REAL* bg, const REAL* means3D, const REAL* shs, const REAL* colors_precomp,
-                  const REAL* scales, REAL scale_modifier, const REAL* rotations, const REAL* cov3D_precomp, const REAL* viewmatrix,
-                  const REAL* projmatrix, const REAL* campos, REAL tan_fovx, REAL tan_fovy, const int32_t* radii, const REAL* points_xy,
-                  const REAL* conic_opacity, const REAL* rgb, const uint8_t* clamped, const REAL* cov3D, const int32_t* point_list,
-                  const uint32_t* ranges, const uint32_t* n_contrib, const REAL* final_T, const REAL* dL_dpix,
-                  REAL* dL_dmean2D, REAL* dL_dconic, REAL* dL_dopacity, REAL* dL_dcolor, REAL* dL_dmean3D, REAL* dL_dcov3D, REAL* dL_dsh,
-                  REAL* dL_dscale, REAL* dL_drot) {
+/* stage (1), the blending backward: the per-Gaussian sums dL/d(mean2D, conic, opacity, colour) of one image gradient */
+void FN(blend_backward)(int P, int W, int H, const REAL* bg, const REAL* points_xy, const REAL* conic_opacity, const REAL* rgb, const int32_t* point_list,
+                        const uint32_t* ranges, const uint32_t* n_contrib, const REAL* final_T, const REAL* dL_dpix,
+                        REAL* dL_dmean2D, REAL* dL_dconic, REAL* dL_dopacity, REAL* dL_dcolor) {
     const int gx = (W + TILE - 1) / TILE;
-    const REAL fx = W / ((REAL)2 * tan_fovx), fy = H / ((REAL)2 * tan_fovy);
     memset(dL_dmean2D, 0, sizeof(REAL) * 3 * P); memset(dL_dconic, 0, sizeof(REAL) * 4 * P); memset(dL_dopacity, 0, sizeof(REAL) * P);
-    memset(dL_dcolor, 0, sizeof(REAL) * 3 * P); memset(dL_dmean3D, 0, sizeof(REAL) * 3 * P); memset(dL_dcov3D, 0, sizeof(REAL) * 6 * P);
-    memset(dL_dsh, 0, sizeof(REAL) * 3 * (size_t)M * P); memset(dL_dscale, 0, sizeof(REAL) * 3 * P); memset(dL_drot, 0, sizeof(REAL) * 4 * P);
+    memset(dL_dcolor, 0, sizeof(REAL) * 3 * P);
     /* (1) blending backward: per pixel, back to front */
     const REAL ddelx_dx = (REAL)0.5 * W, ddely_dy = (REAL)0.5 * H;
     /* OpenMP over pixel rows with atomic adds into the per-Gaussian sums (what the reference's CUDA kernel does with atomicAdd).  With ONE
@@ -363,7 +358,18 @@ _Pragma("omp atomic")
                 dL_dopacity[id] += add_; }
             }
         }
-    /* (2) per-Gaussian backward: independent Gaussians */
+}
+
+/* stage (2), the per-Gaussian backward: reads the sums of stage (1) (dL_dmean2D (P,3), dL_dconic (P,4), dL_dcolor (P,3)) and writes the gradients of the
+ * leaves.  Independent Gaussians. */
+void FN(gaussian_backward)(int P, int D, int M, int W, int H, const REAL* means3D, const REAL* shs, const REAL* colors_precomp, const REAL* scales,
+                           REAL scale_modifier, const REAL* rotations, const REAL* cov3D_precomp, const REAL* viewmatrix, const REAL* projmatrix,
+                           const REAL* campos, REAL tan_fovx, REAL tan_fovy, const int32_t* radii, const uint8_t* clamped, const REAL* cov3D,
+                           const REAL* dL_dmean2D, const REAL* dL_dconic, const REAL* dL_dcolor, REAL* dL_dmean3D, REAL* dL_dcov3D, REAL* dL_dsh,
+                           REAL* dL_dscale, REAL* dL_drot) {
+    const REAL fx = W / ((REAL)2 * tan_fovx), fy = H / ((REAL)2 * tan_fovy);
+    memset(dL_dmean3D, 0, sizeof(REAL) * 3 * P); memset(dL_dcov3D, 0, sizeof(REAL) * 6 * P);
+    memset(dL_dsh, 0, sizeof(REAL) * 3 * (size_t)M * P); memset(dL_dscale, 0, sizeof(REAL) * 3 * P); memset(dL_drot, 0, sizeof(REAL) * 4 * P);
 #pragma omp parallel for schedule(static)
     for (int i = 0; i < P; i++) {
         if (!(radii[i] > 0)) continue;
@@ -494,6 +500,19 @@ _Pragma("omp atomic")
             dL_drot[4 * i + 3] = 2 * (-2 * z * dR[0] - r * dR[1] + x * dR[2] + r * dR[3] - 2 * z * dR[4] + y * dR[5] + x * dR[6] + y * dR[7]);
         }
     }
+}
+
+void FN(backward)(int P, int D, int M, int W, int H, const REAL* bg, const REAL* means3D, const REAL* shs, const REAL* colors_precomp,
+                  const REAL* scales, REAL scale_modifier, const REAL* rotations, const REAL* cov3D_precomp, const REAL* viewmatrix,
+                  const REAL* projmatrix, const REAL* campos, REAL tan_fovx, REAL tan_fovy, const int32_t* radii, const REAL* points_xy,
+                  const REAL* conic_opacity, const REAL* rgb, const uint8_t* clamped, const REAL* cov3D, const int32_t* point_list,
+                  const uint32_t* ranges, const uint32_t* n_contrib, const REAL* final_T, const REAL* dL_dpix,
+                  REAL* dL_dmean2D, REAL* dL_dconic, REAL* dL_dopacity, REAL* dL_dcolor, REAL* dL_dmean3D, REAL* dL_dcov3D, REAL* dL_dsh,
+                  REAL* dL_dscale, REAL* dL_drot) {
+    FN(blend_backward)(P, W, H, bg, points_xy, conic_opacity, rgb, point_list, ranges, n_contrib, final_T, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity,
+                       dL_dcolor);
+    FN(gaussian_backward)(P, D, M, W, H, means3D, shs, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp, viewmatrix, projmatrix, campos,
+                          tan_fovx, tan_fovy, radii, clamped, cov3D, dL_dmean2D, dL_dconic, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh, dL_dscale, dL_drot);
 }
 #undef TILE
 #undef SH_C0

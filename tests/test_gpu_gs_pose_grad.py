@@ -82,7 +82,8 @@ def _camera_grads(run):
 def _single(kind):
     """One Gaussian of SH degree 0 at 32 x 32.  'wide': a hand-made splat of sigma ~ 3 pixels around the image centre.  'sub-pixel': the generator's, log-scale mean
     log 0.03, cov2D dominated by the 0.3 low-pass.  The blend backward's conic sums are fixed point (resolution 2^-25 of the tile's largest pixel gradient per
-    addition): an absolute error of order 1e-5 for pixel gradients of order 1 (measured 1.1e-5).  The wide splat's conic gradient is of order 10, so
+    addition): an absolute error of order 1e-5 for pixel gradients of order 1 (measured 1.1e-5 when this test was written, with a conversion that
+    lost 8 bits of a negative sum's low word; tests/test_gpu_gs_grad_budget.py now holds every element to its own budget).  The wide splat's conic gradient is of order 10, so
     that error is 1e-6 of it; the sub-pixel splat's is 0.003 .. 0.03, the error 4e-4 of its largest component and 4e-3 of its smallest -- with a single addend
     per camera entry that IS the entry's relative error, whatever the camera chain does.  The gate against the oracle is therefore asked of the wide splat; the
     sub-pixel one is held against the chain driven by the kernels' own per-Gaussian gradients (test_the_kernel_follows_the_gpu_records)."""
