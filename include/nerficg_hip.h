@@ -44,8 +44,9 @@ enum {
  * 13 = nrc_grid_backward_input / nrc_sh_identity_backward_input (group 3: the encodings' derivatives with respect to their input) are new, every
  * earlier signature is unchanged;
  * 14 = nrc_gs_pose_partials_floats / nrc_gs_backward_pose_band / nrc_gs_camera_block_backward (group 4: gradients to the camera pose) are new, every
- * earlier signature is unchanged. */
-#define NRC_ABI_VERSION 14
+ * earlier signature is unchanged;
+ * 15 = group 16 (nrc_gs_mcmc_*: the relocation, SGLD noise and regularisers of 3DGS-MCMC) is new, every earlier signature is unchanged. */
+#define NRC_ABI_VERSION 15
 /* library identification; also used by the loader's symbol check */
 int nrc_abi_version(void);
 const char* nrc_build_info(void);
@@ -995,6 +996,48 @@ int nrc_map_losses_forward(const float* depth, const float* alpha, const float* 
 int nrc_map_losses_backward(const float* depth, const float* alpha, const float* image, int64_t B, int32_t C, int32_t H, int32_t W, int32_t normalize,
                             float lambda_smooth, float lambda_entropy, int32_t symmetrical, const float* upstream_dev, float* dL_ddepth, float* dL_dalpha,
                             float* dL_dimage, nrc_stream_t stream);
+
+/* =====================================================================================================
+ * Group 16 -- 3DGS-MCMC (Kheradmand et al., "3D Gaussian Splatting as Markov Chain Monte Carlo", NeurIPS 2024): the steps that replace clone / split /
+ *            prune.  The method's source is not part of the reference tree; these comments are the specification.  All on the RAW training parameters,
+ *            f32, contiguous: opacity_logits (P) with o = sigmoid(logit), log_scales (P, 3) with s = exp(log_scale), rotations (P, 4) with
+ *            q = rotation / max(|rotation|, 1e-12), real part first, R = R(q) (the matrix of nrc_gs_densify_split_children), positions (P, 3).
+ *            Every call: NRC_ERR_INVALID before any launch for P < 0 or a null required pointer; P == 0 is a successful no-op.
+ *
+ *   nrc_gs_mcmc_noise: the SGLD noise on the positions, after the optimizer step of every iteration, in place:
+ *              gate = 1 / (1 + exp(-100 ((1 - o) - 0.995)));   v = z * gate * (noise_lr * lr);   x += R diag(s^2) R^T v;   z ~ N(0, I3).
+ *            lr_dev (optional DEVICE f32) replaces lr, device_step (optional DEVICE i32) replaces iteration: a capturable optimizer's own scalars, so that
+ *            a step recorded in a HIP graph does not replay one draw.  z_in (optional, (P, 3)): the caller's draw.  Without it the kernel draws:
+ *            Philox4x32-10, counter = (index lo, index hi, iteration lo, iteration hi), key = (seed lo, seed hi), index = row_offset + local row (the
+ *            Gaussian's GLOBAL row: the draw does not depend on the rank or on how P is cut into launches); the four words w0..w3 become
+ *              ua = ((w0 >> 8) + 1) 2^-24,  ub = (w1 >> 8) 2^-24,  uc = ((w2 >> 8) + 1) 2^-24,  ud = (w3 >> 8) 2^-24,
+ *              z0 = sqrt(-2 ln ua) cos(2 pi ub),  z1 = sqrt(-2 ln ua) sin(2 pi ub),  z2 = sqrt(-2 ln uc) cos(2 pi ud)      (|z| <= 5.77).
+ *            z_out (optional, (P, 3)) receives the draw that was used.  One streaming launch: 44 B read and 12 B written per Gaussian.
+ *
+ *   nrc_gs_mcmc_relocation: one Gaussian that was drawn count times becomes one of N = clamp(count + 1, 1, 50) stacked copies that render like it did;
+ *            rows with count <= 0 are not touched.  In place on opacity_logits and log_scales, evaluated in f64 and rounded once:
+ *              o_new = 1 - (1 - o)^(1/N);   denom = sum_{i=1..N} sum_{k=0..i-1} C(i-1, k) (-1)^k / sqrt(k+1) o_new^(k+1);   s_new = (o / denom) s;
+ *              o_new <- clamp(o_new, 0.005, 1 - 2^-24);   logit_new = log(o_new / (1 - o_new));   log_scale_new = log(s_new).
+ *            (At the centre the copies composite to 1 - (1 - o_new)^N = o; along any line through the centre the integral of the composited opacity,
+ *            sigma_new sqrt(2 pi) denom, equals o sigma sqrt(2 pi).)  moments: HOST array of n_moments <= 12 DEVICE pointers, moment_row_floats: HOST
+ *            array of their floats per row (the convention of nrc_gather_rows): rows with count > 0 are cleared in the same launch (both Adam moments
+ *            of the six groups).  More than 12: NRC_ERR_INVALID.  opacity_out (P), scales_out (P, 3), both optional: the clamped o_new and s_new as
+ *            f32, written for the rows with count > 0 only.
+ *
+ *   nrc_gs_mcmc_regularise: L_o = opacity_reg mean(o), L_s = scale_reg mean(s); the gradients are ADDED to what the backward pass left:
+ *              grad_opacity_logits[i] += opacity_reg / P * o_i (1 - o_i);   grad_log_scales[i][j] += scale_reg / (3 P) * s_ij
+ *            (each the f32 rounding of the f64 sum), losses (DEVICE float[2]) = {L_o, L_s}: one slab of plain stores per workgroup, added in f64 in a
+ *            fixed order by a finishing launch -- no atomics, bit-identical from call to call.  workspace: nrc_gs_mcmc_regularise_ws_bytes(P) bytes,
+ *            8-byte aligned.
+ * ===================================================================================================== */
+int nrc_gs_mcmc_noise(const float* rotations, const float* log_scales, const float* opacity_logits, float* positions, int64_t P, int64_t row_offset,
+                      float noise_lr, float lr, const float* lr_dev, uint64_t seed, uint64_t iteration, const int32_t* device_step, const float* z_in,
+                      float* z_out, nrc_stream_t stream);
+int nrc_gs_mcmc_relocation(float* opacity_logits, float* log_scales, const int32_t* count, int64_t P, float* const* moments, const int32_t* moment_row_floats,
+                           int32_t n_moments, float* opacity_out, float* scales_out, nrc_stream_t stream);
+int64_t nrc_gs_mcmc_regularise_ws_bytes(int64_t P);
+int nrc_gs_mcmc_regularise(const float* opacity_logits, const float* log_scales, int64_t P, double opacity_reg, double scale_reg, float* grad_opacity_logits,
+                           float* grad_log_scales, float* losses, void* workspace, nrc_stream_t stream);
 
 #ifdef __cplusplus
 }

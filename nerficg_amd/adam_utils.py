@@ -14,7 +14,7 @@ import torch
 from . import _lib
 
 __all__ = ['replace_param_group_data', 'prune_param_groups', 'extend_param_groups', 'reset_state', 'sort_param_groups', 'gather_param_groups',
-           'gather_rows', 'compact_mask']
+           'gather_rows', 'scatter_rows', 'compact_mask']
 
 _MOMENTS = ('exp_avg', 'exp_avg_sq')
 Optimizer = torch.optim.Optimizer
@@ -55,6 +55,28 @@ def gather_rows(tensors: list[torch.Tensor], src: torch.Tensor, n_out: int, kind
                                        ctypes.cast(a_zero, ctypes.c_void_p), n, _lib.ptr(src), _lib.ptr(kind), n_out, _lib.stream_of(src)),
                    'gather_rows')
     return outs
+
+
+def scatter_rows(rows: list[torch.Tensor], tensors: list[torch.Tensor], dst: torch.Tensor) -> None:
+    """tensors[t][dst[r]] = rows[t][r] for the DISTINCT rows `dst`, in place, all tensors in one launch (24 per launch): the inverse of gather_rows."""
+    lib = _lib.load()
+    n_in = int(dst.numel())
+    if not tensors or n_in == 0:
+        return
+    _lib.check_input(dst, 'dst', torch.int32)
+    for r, t in zip(rows, tensors):
+        _lib.check_input(r, 'scatter_rows rows', torch.float32)
+        _lib.check_input(t, 'scatter_rows tensor', torch.float32)
+        if r.shape[0] != n_in or r.shape[1:] != t.shape[1:]:
+            raise RuntimeError(f'scatter_rows: rows of shape {tuple(r.shape)} for {n_in} rows of a tensor of shape {tuple(t.shape)}')
+    for b in range(0, len(tensors), 24):
+        chunk_in, chunk_out = rows[b:b + 24], tensors[b:b + 24]
+        n = len(chunk_in)
+        a_in = (ctypes.c_void_p * n)(*[t.data_ptr() for t in chunk_in])
+        a_out = (ctypes.c_void_p * n)(*[t.data_ptr() for t in chunk_out])
+        a_row = (ctypes.c_int32 * n)(*[max(1, math.prod(t.shape[1:])) for t in chunk_out])
+        _lib.check(lib.nrc_scatter_rows(ctypes.cast(a_in, ctypes.c_void_p), ctypes.cast(a_out, ctypes.c_void_p), ctypes.cast(a_row, ctypes.c_void_p), n,
+                                        _lib.ptr(dst), n_in, _lib.stream_of(dst)), 'scatter_rows')
 
 
 def compact_mask(mask: torch.Tensor) -> torch.Tensor:

@@ -41,6 +41,9 @@ PER_FILE_FLAGS = {
     # no FMA contraction: the f32 sequence of the two input-gradient kernels is the one tests/input_grad_ref.py counts rounding by rounding (the
     # grid kernel waits for its gathers, the SH kernel for its rows: a fused multiply-add would buy nothing)
     'ngp_input_grad.hip': ['-ffp-contract=off'],
+    # no FMA contraction: the noise kernel's f32 sequence is the one tests/gs_mcmc_ref.py counts rounding by rounding, and its two load shapes
+    # (16-byte words, single floats) must give a row the same bits; the kernels wait for memory, or run every 100 iterations
+    'gs_mcmc.hip': ['-ffp-contract=off'],
 }
 
 

@@ -13,7 +13,8 @@ import torch
 
 __all__ = ['PerspectiveCamera', 'get_projection_matrix', 'invert_3d_affine', 'make_raster_settings', 'quaternion_to_rotation_matrix',
            'build_covariances', 'extract_upper_triangular_matrix', 'sh_basis', 'convert_sh_features', 'rgb_to_sh0', 'sh0_to_rgb', 'Gaussians',
-           'render_image_training', 'render_image_inference', 'training_loss', 'rest_step_schedule', 'RestStep', 'band_parallel_training_step']
+           'render_image_training', 'render_image_inference', 'training_loss', 'rest_step_schedule', 'RestStep', 'band_parallel_training_step', 'mcmc_noise',
+           'mcmc_regulariser_grads']
 
 
 @dataclass
@@ -209,6 +210,82 @@ def sh0_to_rgb(sh):
     return sh * _SH_C[0] + 0.5
 
 
+def _mcmc_draw(probabilities: torch.Tensor, n: int) -> torch.Tensor:
+    """n indices drawn with replacement (torch.multinomial, as the published 3DGS-MCMC does)."""
+    if probabilities.numel() > 2 ** 24:
+        raise RuntimeError(f'3DGS-MCMC sampling: torch.multinomial takes at most 2^24 categories, {probabilities.numel()} rows given; '
+                           'draw the rows yourself and pass them as sampled=')
+    return torch.multinomial(probabilities, n, replacement=True)
+
+
+def _mcmc_relocation(opacity_logits: torch.Tensor, log_scales: torch.Tensor, counts: torch.Tensor, moments: list[torch.Tensor],
+                     opacity_out: torch.Tensor | None = None, scales_out: torch.Tensor | None = None) -> None:
+    """nrc_gs_mcmc_relocation in place on (P, 1) logits and (P, 3) log-scales for the rows with counts > 0; `moments` (at most 12 tensors of P rows) lose
+    those rows.  opacity_out (P) / scales_out (P, 3): optional, receive the new activated values of those rows."""
+    import ctypes
+    from . import _lib
+    _lib.check_input(opacity_logits, 'opacity logits', torch.float32)
+    _lib.check_input(log_scales, 'log scales', torch.float32)
+    _lib.check_input(counts, 'counts', torch.int32)
+    P = opacity_logits.shape[0]
+    if log_scales.shape[0] != P or counts.numel() != P:
+        raise RuntimeError('mcmc relocation: logits, log-scales and counts must have the same number of rows')
+    for m in moments:
+        _lib.check_input(m, 'Adam moment', torch.float32)
+        if m.shape[0] != P:
+            raise RuntimeError('mcmc relocation: a moment tensor with another number of rows')
+    for t in (opacity_out, scales_out):
+        if t is not None:
+            _lib.check_input(t, 'relocation output', torch.float32)
+    n = len(moments)
+    a_ptr = (ctypes.c_void_p * max(n, 1))(*[m.data_ptr() for m in moments])
+    a_row = (ctypes.c_int32 * max(n, 1))(*[max(1, int(np.prod(m.shape[1:]))) for m in moments])
+    _lib.check(_lib.load().nrc_gs_mcmc_relocation(_lib.ptr(opacity_logits), _lib.ptr(log_scales), _lib.ptr(counts), P, ctypes.cast(a_ptr, ctypes.c_void_p),
+                                                  ctypes.cast(a_row, ctypes.c_void_p), n, _lib.ptr(opacity_out), _lib.ptr(scales_out),
+                                                  _lib.stream_of(opacity_logits)), 'gs_mcmc_relocation')
+
+
+def mcmc_noise(positions: torch.Tensor, rotations: torch.Tensor, log_scales: torch.Tensor, opacity_logits: torch.Tensor, lr: float, noise_lr: float = 5e5,
+               seed: int = 0, iteration: int = 0, z: torch.Tensor | None = None, z_out: torch.Tensor | None = None, row_offset: int = 0,
+               lr_dev: torch.Tensor | None = None, device_step: torch.Tensor | None = None) -> None:
+    """nrc_gs_mcmc_noise in place on `positions` (P, 3): x += R diag(s^2) R^T (z * gate * noise_lr * lr).  row_offset: the global row of local row 0 (the
+    generator's counter is the global row, so a model cut into several launches, or over ranks, draws what one launch draws).  lr_dev (device f32[1]) /
+    device_step (device i32[1]) replace lr / iteration."""
+    from . import _lib
+    for t, name in ((positions, 'positions'), (rotations, 'rotations'), (log_scales, 'log scales'), (opacity_logits, 'opacity logits'), (z, 'z'), (z_out, 'z_out'),
+                    (lr_dev, 'lr_dev')):
+        if t is not None:
+            _lib.check_input(t, name, torch.float32)
+    if device_step is not None:
+        _lib.check_input(device_step, 'device_step', torch.int32)
+    P = positions.shape[0]
+    if rotations.shape[0] != P or log_scales.shape[0] != P or opacity_logits.shape[0] != P or any(t is not None and tuple(t.shape) != (P, 3) for t in (z, z_out)):
+        raise RuntimeError('mcmc_noise: P rows expected in every tensor, (P, 3) for z and z_out')
+    if iteration < 0 or row_offset < 0:
+        raise RuntimeError('mcmc_noise: iteration and row_offset must not be negative')
+    _lib.check(_lib.load().nrc_gs_mcmc_noise(_lib.ptr(rotations), _lib.ptr(log_scales), _lib.ptr(opacity_logits), _lib.ptr(positions), P, int(row_offset),
+                                             float(noise_lr), float(lr), _lib.ptr(lr_dev), int(seed) & (2 ** 64 - 1), int(iteration), _lib.ptr(device_step),
+                                             _lib.ptr(z), _lib.ptr(z_out), _lib.stream_of(positions)), 'gs_mcmc_noise')
+
+
+def mcmc_regulariser_grads(opacity_logits: torch.Tensor, log_scales: torch.Tensor, grad_opacity_logits: torch.Tensor, grad_log_scales: torch.Tensor,
+                           opacity_reg: float = 0.01, scale_reg: float = 0.01) -> torch.Tensor:
+    """nrc_gs_mcmc_regularise: adds d(opacity_reg * mean(o)) / d logit and d(scale_reg * mean(s)) / d log_scale to the two gradient tensors in place and
+    returns the device tensor [L_o, L_s]."""
+    from . import _lib
+    for t, name in ((opacity_logits, 'opacity logits'), (log_scales, 'log scales'), (grad_opacity_logits, 'opacity gradient'), (grad_log_scales, 'scale gradient')):
+        _lib.check_input(t, name, torch.float32)
+    P = opacity_logits.shape[0]
+    if log_scales.shape[0] != P or grad_opacity_logits.numel() != P or grad_log_scales.numel() != 3 * P:
+        raise RuntimeError('mcmc_regulariser_grads: (P, 1) logits and (P, 3) log-scales with gradients of the same shapes expected')
+    lib = _lib.load()
+    losses = torch.zeros(2, dtype=torch.float32, device=opacity_logits.device)
+    ws = torch.empty(max(1, int(lib.nrc_gs_mcmc_regularise_ws_bytes(P)) // 8), dtype=torch.float64, device=opacity_logits.device)
+    _lib.check(lib.nrc_gs_mcmc_regularise(_lib.ptr(opacity_logits), _lib.ptr(log_scales), P, float(opacity_reg), float(scale_reg), _lib.ptr(grad_opacity_logits),
+                                          _lib.ptr(grad_log_scales), _lib.ptr(losses), _lib.ptr(ws), _lib.stream_of(opacity_logits)), 'gs_mcmc_regularise')
+    return losses
+
+
 class Gaussians(torch.nn.Module):
     """Parameter store + activation accessors of GaussianSplatting/Model.py:18-87 (exp scales, normalised quaternions, sigmoid
     opacities, cat[dc, rest] SH features of shape (P, 16, 3)) and the training-time bookkeeping of Model.py:94-284: optimizer setup,
@@ -377,6 +454,110 @@ class Gaussians(torch.nn.Module):
         self.densification_gradient_accum = torch.zeros((n_out, 1), dtype=torch.float32, device=dev)
         self.n_observations = torch.zeros((n_out, 1), dtype=torch.int32, device=dev)
         return {'n_out': n_out, 'n_kept': n_keep, 'n_cloned': n_dup, 'n_split': n_split, 'n_children_kept': 2 * n_child}
+
+    # ---------------------------------------------------------------- 3DGS-MCMC (include/nerficg_hip.h group 16)
+    def _six(self) -> list[torch.Tensor]:
+        return [getattr(self, attr) for attr in self._GROUP_OF.values()]
+
+    def _adam_moments(self) -> list[torch.Tensor]:
+        """Both Adam moments of the six groups (those the optimizer has created so far)."""
+        out = []
+        if self.optimizer is not None:
+            for p in self._six():
+                state = self.optimizer.state.get(p) or {}
+                out += [state[key] for key in ('exp_avg', 'exp_avg_sq') if key in state]
+        return out
+
+    def _drop_grads(self) -> None:
+        for p in self._six():
+            p.grad = None
+
+    @torch.no_grad()
+    def relocate(self, min_opacity: float = 0.005, sampled: torch.Tensor | None = None) -> dict[str, int]:
+        """The relocation round of 3DGS-MCMC: every dead Gaussian (o <= min_opacity) is moved onto a live one, drawn with replacement with probability
+        o / (sum o + 2^-23) (torch.multinomial); a live Gaussian drawn `count` times becomes one of count + 1 stacked copies with the opacity and scale
+        that keep the rendered result (nrc_gs_mcmc_relocation, f64 inside) and loses its Adam moments; the six parameter rows drawn[j] are then copied
+        to dead[j], which keep their own moments (as published).  `sampled`: the drawn rows (n_dead indices of live rows) instead of the draw -- the
+        test hook that `noise=` is for densify_and_prune.  When a row moved, the .grad of the six tensors is dropped: that iteration's optimizer step
+        is skipped, as it is behind densify_and_prune (rest_step_schedule).  Returns {'n_dead', 'n_relocated'}."""
+        from . import adam_utils
+        o = torch.sigmoid(self._opacities.data).reshape(-1)
+        P = o.shape[0]
+        dead_mask = o <= min_opacity
+        dead = torch.nonzero(dead_mask).reshape(-1)
+        n_dead = int(dead.numel())
+        if n_dead == 0 or n_dead == P:      # nothing to move, or nothing to move onto
+            return {'n_dead': n_dead, 'n_relocated': 0}
+        if sampled is None:
+            alive = torch.nonzero(~dead_mask).reshape(-1)
+            weights = o[alive]
+            drawn = alive[_mcmc_draw(weights / (weights.sum() + 2.0 ** -23), n_dead)]
+        else:
+            drawn = sampled.to(device=o.device, dtype=torch.int64).reshape(-1)
+            if drawn.numel() != n_dead or bool(dead_mask[drawn].any()):
+                raise RuntimeError(f'relocate: sampled must hold {n_dead} indices of live rows')
+        counts = torch.bincount(drawn, minlength=P).to(torch.int32)
+        _mcmc_relocation(self._opacities.data, self._scales.data, counts, self._adam_moments())
+        tensors = [p.data for p in self._six()]
+        rows = adam_utils.gather_rows(tensors, drawn.to(torch.int32), n_dead)
+        adam_utils.scatter_rows(rows, tensors, dead.to(torch.int32))
+        self._drop_grads()
+        return {'n_dead': n_dead, 'n_relocated': n_dead}
+
+    @torch.no_grad()
+    def add_new(self, cap_max: int, sampled: torch.Tensor | None = None) -> int:
+        """The growth step of 3DGS-MCMC: n = max(0, min(cap_max, int(1.05 P)) - P) rows are drawn from ALL rows with probability o / (sum o + 2^-23); the
+        drawn rows get the relocation arithmetic in place (moments cleared) and one copy per draw is appended with zero moments.  `sampled`: the n drawn
+        rows instead of the draw.  The six tensors are replaced by fresh Parameters without .grad (that iteration's optimizer step is skipped);
+        densification_gradient_accum / n_observations grow by zero rows.  Returns n."""
+        from . import adam_utils
+        P = self._positions.shape[0]
+        n = max(0, min(int(cap_max), int(1.05 * P)) - P)
+        if n == 0:
+            return 0
+        o = torch.sigmoid(self._opacities.data).reshape(-1)
+        if sampled is None:
+            drawn = _mcmc_draw(o / (o.sum() + 2.0 ** -23), n)
+        else:
+            drawn = sampled.to(device=o.device, dtype=torch.int64).reshape(-1)
+            if drawn.numel() != n:
+                raise RuntimeError(f'add_new: sampled must hold {n} row indices')
+        counts = torch.bincount(drawn, minlength=P).to(torch.int32)
+        _mcmc_relocation(self._opacities.data, self._scales.data, counts, self._adam_moments())
+        src = torch.cat([torch.arange(P, dtype=torch.int32, device=o.device), drawn.to(torch.int32)])
+        kind = torch.cat([torch.zeros(P, dtype=torch.int32, device=o.device), torch.ones(n, dtype=torch.int32, device=o.device)])
+        self._adopt(adam_utils.gather_param_groups(self.optimizer, src, P + n, kind, None, 'extend_param_groups'))
+        self.densification_gradient_accum = torch.cat([self.densification_gradient_accum, self.densification_gradient_accum.new_zeros((n, 1))])
+        self.n_observations = torch.cat([self.n_observations, self.n_observations.new_zeros((n, 1))])
+        return n
+
+    @torch.no_grad()
+    def inject_noise(self, iteration: int | None, noise_lr: float = 5e5, seed: int = 0, z: torch.Tensor | None = None, z_out: torch.Tensor | None = None) -> None:
+        """The SGLD noise of 3DGS-MCMC on the positions, after optimizer.step(): x += R diag(s^2) R^T (z * gate * noise_lr * lr), lr the learning rate of
+        the `positions` group, gate = sigmoid(100 ((1 - o) - 0.995)) (one streaming launch: nrc_gs_mcmc_noise).  `z`: the caller's (P, 3) standard normal
+        draw; by default the kernel draws (Philox4x32-10 keyed by seed, counter = (row, iteration): the same draw on every rank of a view-parallel run).
+        z_out: (P, 3), receives the draw that was used.  iteration=None with a capturable optimizer: generator and learning rate are keyed by the
+        optimizer's own device scalars (the step counter of the `positions` group), so a step recorded in a HIP graph draws anew on every replay."""
+        gi, group = next((i, g) for i, g in enumerate(self.optimizer.param_groups) if g.get('name') == 'positions')
+        lr_dev = device_step = None
+        if iteration is None:
+            slot = getattr(self.optimizer, '_lr_dev', {}).get(gi)
+            if not getattr(self.optimizer, 'capturable', False) or slot is None or not torch.is_tensor(group.get('step')):
+                raise RuntimeError('inject_noise: iteration=None needs a capturable optimizer that has taken a step (its device step counter keys the generator)')
+            lr_dev, device_step, iteration = slot[0], group['step'], 0
+        mcmc_noise(self._positions.data, self._rotations.data, self._scales.data, self._opacities.data, float(group['lr']), noise_lr=noise_lr, seed=seed,
+                   iteration=iteration, z=z, z_out=z_out, lr_dev=lr_dev, device_step=device_step)
+
+    @torch.no_grad()
+    def add_mcmc_regulariser_grads(self, opacity_reg: float = 0.01, scale_reg: float = 0.01) -> tuple[torch.Tensor, torch.Tensor]:
+        """The two L1 regularisers of 3DGS-MCMC, L_o = opacity_reg * mean(o) and L_s = scale_reg * mean(s): their gradients are added in place to the .grad
+        the backward pass left on the opacity and scale tensors (created as zeros where there is none), the two loss values come back as device scalars
+        (bit-reproducible: nrc_gs_mcmc_regularise)."""
+        for p in (self._opacities, self._scales):
+            if p.grad is None:
+                p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        losses = mcmc_regulariser_grads(self._opacities.data, self._scales.data, self._opacities.grad, self._scales.grad, opacity_reg, scale_reg)
+        return losses[0], losses[1]
 
     # ---------------------------------------------------------------- export (Model.py:248-318)
     @torch.no_grad()
