@@ -45,8 +45,9 @@ enum {
  * earlier signature is unchanged;
  * 14 = nrc_gs_pose_partials_floats / nrc_gs_backward_pose_band / nrc_gs_camera_block_backward (group 4: gradients to the camera pose) are new, every
  * earlier signature is unchanged;
- * 15 = group 16 (nrc_gs_mcmc_*: the relocation, SGLD noise and regularisers of 3DGS-MCMC) is new, every earlier signature is unchanged. */
-#define NRC_ABI_VERSION 15
+ * 15 = group 16 (nrc_gs_mcmc_*: the relocation, SGLD noise and regularisers of 3DGS-MCMC) is new, every earlier signature is unchanged;
+ * 16 = group 17 (nrc_nerf_*: the vanilla NeRF block's inference forward as one kernel) is new, every earlier signature is unchanged. */
+#define NRC_ABI_VERSION 16
 /* library identification; also used by the loader's symbol check */
 int nrc_abi_version(void);
 const char* nrc_build_info(void);
@@ -1038,6 +1039,40 @@ int nrc_gs_mcmc_relocation(float* opacity_logits, float* log_scales, const int32
 int64_t nrc_gs_mcmc_regularise_ws_bytes(int64_t P);
 int nrc_gs_mcmc_regularise(const float* opacity_logits, const float* log_scales, int64_t P, double opacity_reg, double scale_reg, float* grad_opacity_logits,
                            float* grad_log_scales, float* losses, void* workspace, nrc_stream_t stream);
+
+/* =====================================================================================================
+ * Group 17 -- the vanilla NeRF block, INFERENCE forward, as one kernel (csrc/nerf_net.hip).  Replaces src/Methods/NeRF/Model.py:59-83
+ *            (NeRFBlock.forward) and utils.py:12-36 (FrequencyEncoding.forward) under no_grad: frequency encodings, n_layers x (Linear W + ReLU) with
+ *            the encoded position re-entering behind every layer of the skip set, density head (Linear(W, 1) + ReLU), feature layer (Linear(W, W)),
+ *            colour head (Linear(W + n_dir, W/2) + ReLU, (n_color_layers - 1) x (Linear(W/2, W/2) + ReLU), Linear(W/2, 3) + Sigmoid).
+ *            cfg = (width, n_layers, n_color_layers, n_frequencies_position, n_frequencies_direction, append_input, skip_mask); bit k of skip_mask:
+ *            the input of layer k (0-based) is [hidden, encoded position], i.e. k is in the module's input_skips, 1 <= k <= n_layers - 1.
+ *            Supported: width 128 or 256, n_layers 1..8, n_color_layers 1..3, n_frequencies_position 0..10 with encoded width 1..64,
+ *            n_frequencies_direction 0..4 with encoded width 1..32, any such skip_mask.  Everything else: nrc_nerf_supported = 0, the other calls
+ *            NRC_ERR_UNSUPPORTED.  Arithmetic contract (fp16 operands, f32 accumulation from the f32 bias, convert -> ReLU -> saturate at 65504,
+ *            sigma / rgb straight from the accumulator, accurate sincosf with |error| <= 2^-22): top of csrc/nerf_net.hip, DESIGN.md.
+ *
+ *   nrc_nerf_tile_rows: rows per workgroup (the sizes at which a launch gains a workgroup).
+ *   nrc_nerf_packed_bytes: size of the packed blob (fp16 weight fragments in the order the forward kernel reads them, then f32 biases).
+ *   nrc_nerf_pack_weights: params = HOST array of n_params = 2 x linears DEVICE f32 pointers, (weight, bias) of initial_layers[0..], density_layer,
+ *            feature_layer, the colour head's linears in order; copied into the launch's arguments, one kernel, no host sync, capturable.
+ *            blob: DEVICE, 16-byte aligned.
+ *   nrc_nerf_block_forward: positions (M, 3) f32; directions (ceil(M / dir_group), 3) f32 -- row i reads direction row i / dir_group (1 = per sample,
+ *            S = per ray of S consecutive samples); sigma (M) f32, rgb (M, 3) f32.  tap = 0: production.  tap = t > 0 (a separate instantiation):
+ *            additionally writes the fp16 operand of stage t of [enc_pos, enc_dir, H_1 .. H_L, F, C_1 .. C_n] (1-based) to tap_out (M, width of the
+ *            stage), unpadded, row-major.  M == 0: NRC_OK without a launch.  M < 0, dir_group < 1, a tap out of range, a null pointer: NRC_ERR_INVALID.
+ * ===================================================================================================== */
+int nrc_nerf_supported(int32_t width, int32_t n_layers, int32_t n_color_layers, int32_t n_frequencies_position, int32_t n_frequencies_direction,
+                       int32_t append_input, int32_t skip_mask);
+int nrc_nerf_tile_rows(void);
+int64_t nrc_nerf_packed_bytes(int32_t width, int32_t n_layers, int32_t n_color_layers, int32_t n_frequencies_position, int32_t n_frequencies_direction,
+                              int32_t append_input, int32_t skip_mask);
+int nrc_nerf_pack_weights(const float* const* params, int32_t n_params, int32_t width, int32_t n_layers, int32_t n_color_layers,
+                          int32_t n_frequencies_position, int32_t n_frequencies_direction, int32_t append_input, int32_t skip_mask, void* blob,
+                          nrc_stream_t stream);
+int nrc_nerf_block_forward(const float* positions, const float* directions, int64_t dir_group, int64_t M, const void* blob, int32_t width,
+                           int32_t n_layers, int32_t n_color_layers, int32_t n_frequencies_position, int32_t n_frequencies_direction,
+                           int32_t append_input, int32_t skip_mask, float* sigma, float* rgb, int32_t tap, void* tap_out, nrc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -44,6 +44,8 @@ PER_FILE_FLAGS = {
     # no FMA contraction: the noise kernel's f32 sequence is the one tests/gs_mcmc_ref.py counts rounding by rounding, and its two load shapes
     # (16-byte words, single floats) must give a row the same bits; the kernels wait for memory, or run every 100 iterations
     'gs_mcmc.hip': ['-ffp-contract=off'],
+    # no SLP vectoriser, for the reason given for ngp_net.hip: the accumulator -> operand conversions sit between MFMAs (the packed fp16 max / min are written out)
+    'nerf_net.hip': ['-fno-slp-vectorize'],
 }
 
 

@@ -1,6 +1,7 @@
 """nerficg_amd.nerf -- host-side mirror of the reference's vanilla NeRF hot path (config 1: nerf_lego.yaml, pure PyTorch, runs
 on CPU or on the GPU through torch): FrequencyEncoding, NeRFBlock, stratified + PDF sampling, sample integration and the
-hierarchical (coarse -> fine) ray renderer.
+hierarchical (coarse -> fine) ray renderer.  `fused_forward` / `render_rays(fused=True)` run the block's INFERENCE forward as one HIP kernel
+(csrc/nerf_net.hip, header group 17: fp16 MFMA operands, f32 accumulation); training and everything else stay on torch.
 
 Reference: src/Methods/NeRF/utils.py:12-136, src/Methods/NeRF/Model.py:10-83, src/Methods/NeRF/Renderer.py:20-95.
 Pinned against golden vectors generated from the reference (tests/test_host_golden.py).  `integrate_samples` is also the
@@ -10,7 +11,8 @@ from __future__ import annotations
 
 import torch
 
-__all__ = ['FrequencyEncoding', 'NeRFBlock', 'generate_samples', 'generate_samples_from_pdf', 'integrate_samples', 'render_rays']
+__all__ = ['FrequencyEncoding', 'NeRFBlock', 'generate_samples', 'generate_samples_from_pdf', 'integrate_samples', 'render_rays', 'fused_forward',
+           'fused_config', 'fused_tap_names']
 
 
 class FrequencyEncoding(torch.nn.Module):
@@ -67,6 +69,94 @@ class NeRFBlock(torch.nn.Module):
         return self.density_activation(sigma), self.color_layers(view_dependent)
 
 
+def _block_linears(block: NeRFBlock) -> list:
+    """The block's linears in the order of the packed parameter list (include/nerficg_hip.h group 17)."""
+    color = list(block.color_layers)
+    return ([seq[0] for seq in block.initial_layers] + [block.density_layer, block.feature_layer, color[0]] + [m[0] for m in color[2:-2]] + [color[-2]])
+
+
+def fused_config(block: NeRFBlock):
+    """(width, n_layers, n_color_layers, n_frequencies_position, n_frequencies_direction, append_input, skip_mask) of a block the fused kernel can
+    run (nrc_nerf_supported), None for any other: widths other than 128 / 256, encodings wider than 64 / 32, differing append flags, non-f32 parameters."""
+    from . import _lib
+    n_layers, width = len(block.initial_layers), block.feature_layer.in_features
+    skips = {int(k) for k in block.input_skips if 1 <= int(k) <= n_layers}   # the module itself ignores every other entry
+    if n_layers in skips or bool(block.encoding_position.append_input) != bool(block.encoding_direction.append_input):
+        return None
+    cfg = (width, n_layers, len(block.color_layers) - 3, block.encoding_position.frequency_factors.numel(),
+           block.encoding_direction.frequency_factors.numel(), int(bool(block.encoding_position.append_input)), sum(1 << k for k in skips))
+    if not _lib.load().nrc_nerf_supported(*cfg):
+        return None
+    n_pos, n_dir, half = block.encoding_position.get_n_outputs(3), block.encoding_direction.get_n_outputs(3), width // 2
+    shapes = ([(width, n_pos)] + [(width, width + (n_pos if k in skips else 0)) for k in range(1, n_layers)] + [(1, width), (width, width), (half, width + n_dir)]
+              + [(half, half)] * (cfg[2] - 1) + [(3, half)])
+    linears = _block_linears(block)
+    if len(linears) != len(shapes):
+        return None
+    for lin, shape in zip(linears, shapes):
+        if (not isinstance(lin, torch.nn.Linear) or tuple(lin.weight.shape) != shape or lin.bias is None or lin.weight.dtype != torch.float32
+                or lin.bias.dtype != torch.float32 or not lin.weight.is_contiguous()):
+            return None
+    return cfg
+
+
+def fused_tap_names(cfg) -> list[tuple[str, int]]:
+    """(name, width) of the stages `fused_forward(tap=...)` can return, in the kernel's order; tap = 1 + index."""
+    width, n_layers, n_color, k_pos, k_dir, append = cfg[:6]
+    return ([('enc_pos', 6 * k_pos + 3 * append), ('enc_dir', 6 * k_dir + 3 * append)] + [(f'H_{l}', width) for l in range(1, n_layers + 1)] + [('F', width)]
+            + [(f'C_{q}', width // 2) for q in range(1, n_color + 1)])
+
+
+def _packed_blob(block: NeRFBlock, cfg, device) -> torch.Tensor:
+    """The block's parameters as the kernel's blob, cached on the block; repacked (one launch, no sync) when any parameter's storage or version changed."""
+    import ctypes
+    from . import _lib
+    params = [t for lin in _block_linears(block) for t in (lin.weight, lin.bias)]
+    key = (cfg, str(device)) + tuple((t.data_ptr(), t._version) for t in params)
+    cache = block.__dict__.setdefault('_fused_cache', {'key': None, 'blob': None, 'packs': 0})
+    if cache['key'] != key:
+        lib = _lib.load()
+        n_bytes = lib.nrc_nerf_packed_bytes(*cfg)
+        if cache['blob'] is None or cache['blob'].numel() != n_bytes or cache['blob'].device != device:
+            cache['blob'] = torch.empty(n_bytes, dtype=torch.uint8, device=device)
+        ptrs = (ctypes.c_void_p * len(params))(*[t.data_ptr() for t in params])
+        _lib.check(lib.nrc_nerf_pack_weights(ctypes.cast(ptrs, ctypes.c_void_p), len(params), *cfg, _lib.ptr(cache['blob']), _lib.stream_of(cache['blob'])),
+                   'nerf_pack_weights')
+        cache['key'] = key
+        cache['packs'] += 1
+    return cache['blob']
+
+
+def fused_forward(block: NeRFBlock, positions: torch.Tensor, directions: torch.Tensor, dir_group: int = 1, tap: int | None = None):
+    """`NeRFBlock.forward` without noise as one kernel -> (sigma (M, 1), rgb (M, 3)), f32.  `directions` holds one row per `dir_group` consecutive
+    samples (1: per sample; S: per ray of S samples).  With `tap` = t >= 1 a third value is returned: the fp16 operand of stage t of
+    `fused_tap_names` (None on the torch path).  Falls back to the torch module -- same values as `block(positions, expanded directions)` -- for CPU
+    tensors, an unsupported block, or when autograd is recording and an input or a parameter requires grad."""
+    m = positions.shape[0]
+    eligible = (positions.is_cuda and directions.is_cuda and positions.dtype == torch.float32 and directions.dtype == torch.float32
+                and all(p.is_cuda and p.device == positions.device for p in block.parameters())
+                and not (torch.is_grad_enabled() and (positions.requires_grad or directions.requires_grad or any(p.requires_grad for p in block.parameters()))))
+    cfg = fused_config(block) if eligible else None
+    if cfg is None:
+        expanded = directions if dir_group == 1 else directions[:, None, :].expand(-1, dir_group, -1).reshape(-1, 3)[:m]
+        out = block(positions, expanded)
+        return out if tap is None else (*out, None)
+    from . import _lib
+    positions, directions = positions.detach().contiguous(), directions.detach().contiguous()
+    if directions.shape[0] * dir_group < m:
+        raise ValueError(f'{directions.shape[0]} direction rows x dir_group {dir_group} do not cover {m} samples')
+    with torch.cuda.device(positions.device):
+        blob = _packed_blob(block, cfg, positions.device)
+        sigma = torch.empty(m, 1, dtype=torch.float32, device=positions.device)
+        rgb = torch.empty(m, 3, dtype=torch.float32, device=positions.device)
+        tapped = None
+        if tap:
+            tapped = torch.empty(m, fused_tap_names(cfg)[tap - 1][1], dtype=torch.float16, device=positions.device)
+        _lib.check(_lib.load().nrc_nerf_block_forward(_lib.ptr(positions), _lib.ptr(directions), int(dir_group), m, _lib.ptr(blob), *cfg, _lib.ptr(sigma),
+                                                      _lib.ptr(rgb), int(tap or 0), _lib.ptr(tapped), _lib.stream_of(positions)), 'nerf_block_forward')
+    return (sigma, rgb) if tap is None else (sigma, rgb, tapped)
+
+
 def generate_samples(n_rays: int, n_samples: int, near_plane: float, far_plane: float, randomize_samples: bool, dtype=torch.float32,
                      device=None) -> torch.Tensor:
     """Depths of the coarse pass (utils.py:57-75): `n_samples` evenly spaced values in [near, far] for every ray; with `randomize_samples` each
@@ -120,8 +210,14 @@ def integrate_samples(depth_samples, ray_directions, densities, colors, backgrou
 
 def render_rays(coarse_nerf: NeRFBlock | None, nerf: NeRFBlock, origin, direction, view_direction, near_plane: float, far_plane: float,
                 background_color, ray_batch_size: int = 8192, n_samples_coarse_nerf: int = 64, n_samples_nerf: int = 192,
-                randomize_samples: bool = False, random_noise_density: float = 0.0) -> dict[str, torch.Tensor]:
-    """NeRFRayRenderingComponent.forward (Renderer.py:29-95): chunked coarse pass -> PDF samples -> sorted union -> fine pass."""
+                randomize_samples: bool = False, random_noise_density: float = 0.0, fused: bool = False) -> dict[str, torch.Tensor]:
+    """NeRFRayRenderingComponent.forward (Renderer.py:29-95): chunked coarse pass -> PDF samples -> sorted union -> fine pass.  `fused`: the two network
+    calls go through `fused_forward` (one direction row per ray); with density noise, and wherever `fused_forward` falls back, the torch path runs."""
+    def query(block, pos, vd):
+        if fused and not random_noise_density > 0.0:
+            return fused_forward(block, pos.reshape(-1, 3), vd, dir_group=pos.shape[1])
+        return block(pos.reshape(-1, 3), vd[:, None, :].expand_as(pos).reshape(-1, 3), random_noise_density)
+
     use_coarse = coarse_nerf is not None and n_samples_coarse_nerf > 0
     keys = ['rgb', 'alpha', 'depth'] + (['rgb_coarse', 'alpha_coarse', 'depth_coarse'] if use_coarse else [])
     chunks: dict[str, list] = {k: [] for k in keys}
@@ -132,7 +228,7 @@ def render_rays(coarse_nerf: NeRFBlock | None, nerf: NeRFBlock, origin, directio
         if use_coarse:
             t_c = generate_samples(n, n_samples_coarse_nerf, near_plane, far_plane, randomize_samples, o.dtype, o.device)
             pos = o[:, None, :] + d[:, None, :] * t_c[:, :, None]
-            dens, col = coarse_nerf(pos.reshape(-1, 3), vd[:, None, :].expand_as(pos).reshape(-1, 3), random_noise_density)
+            dens, col = query(coarse_nerf, pos, vd)
             rgb_c, depth_c, alpha_c, w_c = integrate_samples(t_c, d, dens.reshape(n, -1), col.reshape(n, -1, 3), bg)
             t_f = generate_samples_from_pdf(t_c, w_c, n_samples_nerf, randomize_samples)
             t, _ = torch.sort(torch.cat((t_c, t_f), dim=-1), dim=-1)
@@ -140,7 +236,7 @@ def render_rays(coarse_nerf: NeRFBlock | None, nerf: NeRFBlock, origin, directio
         else:
             t = generate_samples(n, n_samples_nerf, near_plane, far_plane, randomize_samples, o.dtype, o.device)
         pos = o[:, None, :] + d[:, None, :] * t[:, :, None]
-        dens, col = nerf(pos.reshape(-1, 3), vd[:, None, :].expand_as(pos).reshape(-1, 3), random_noise_density)
+        dens, col = query(nerf, pos, vd)
         rgb, depth, alpha, _ = integrate_samples(t, d, dens.reshape(n, -1), col.reshape(n, -1, 3), bg)
         chunks['rgb'].append(rgb); chunks['depth'].append(depth); chunks['alpha'].append(alpha)
     return {k: torch.cat(v, dim=0) for k, v in chunks.items()}

@@ -51,6 +51,9 @@ if tstats:
 fstats = sorted(glob.glob(str(RAW / 'fused_stats' / '*' / '*kernel_stats.csv')), key=os.path.getmtime)
 if fstats:
     shutil.copy(fstats[-1], OUT / f'{ROUND}_fused_train_kernel_stats.csv')
+nstats = sorted(glob.glob(str(RAW / 'nerf_stats' / '*' / '*kernel_stats.csv')), key=os.path.getmtime)   # tools/bench_nerf_fused.py: fused NeRF block and the torch module
+if nstats:
+    shutil.copy(nstats[-1], OUT / f'{ROUND}_nerf_kernel_stats.csv')
 # one accumulator per collection run: pmc_* = tools/bench_query.py (InstantNGP image pipeline), pmcgs_* = tools/bench_gs.py (3DGS frame),
 # pmctr_* = tools/bench_train.py (InstantNGP training iteration).  A kernel that appears in several of them (k_grid_encode runs in the image
 # pipeline with 8 Mi-slot launches and in training with 264 K samples) is reported from the run that is about it.
@@ -69,7 +72,7 @@ for k in names:
     for n, vals in src[k].items():
         acc[k][n] = vals
 keep = ('k_grid_encode', 'k_ngp_mlp', 'k_render', 'k_composite_image', 'k_preprocess', 'k_span_', 'k_item_', 'k_depth_keys', 'k_radix_', 'k_scan_tiles', 'k_march_wave',
-        'k_grid_bwd', 'k_nwie_', 'k_composite_train', 'k_gb_', 'k_train_', 'k_amp_', 'k_adam')
+        'k_grid_bwd', 'k_nwie_', 'k_composite_train', 'k_gb_', 'k_train_', 'k_amp_', 'k_adam', 'k_nerf_')
 lines = [f'# rocprofv3 --pmc summary (MI355X, {ROUND})', '',
          'Collected by `tools/collect_profiles.sh` (one `--pmc` group per run, `--kernel-trace` only), averaged per kernel over all launches of',
          '`tools/bench_query.py` (InstantNGP 800x800 image pipeline), `tools/bench_gs.py` (3DGS, 1 M Gaussians, 1297x840) and `tools/bench_train.py`',
