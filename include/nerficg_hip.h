@@ -46,8 +46,9 @@ enum {
  * 14 = nrc_gs_pose_partials_floats / nrc_gs_backward_pose_band / nrc_gs_camera_block_backward (group 4: gradients to the camera pose) are new, every
  * earlier signature is unchanged;
  * 15 = group 16 (nrc_gs_mcmc_*: the relocation, SGLD noise and regularisers of 3DGS-MCMC) is new, every earlier signature is unchanged;
- * 16 = group 17 (nrc_nerf_*: the vanilla NeRF block's inference forward as one kernel) is new, every earlier signature is unchanged. */
-#define NRC_ABI_VERSION 16
+ * 16 = group 17 (nrc_nerf_*: the vanilla NeRF block's inference forward as one kernel) is new, every earlier signature is unchanged;
+ * 17 = group 18 (the vanilla NeRF block's training forward and backward) is new, every earlier signature is unchanged. */
+#define NRC_ABI_VERSION 17
 /* library identification; also used by the loader's symbol check */
 int nrc_abi_version(void);
 const char* nrc_build_info(void);
@@ -1073,6 +1074,61 @@ int nrc_nerf_pack_weights(const float* const* params, int32_t n_params, int32_t 
 int nrc_nerf_block_forward(const float* positions, const float* directions, int64_t dir_group, int64_t M, const void* blob, int32_t width,
                            int32_t n_layers, int32_t n_color_layers, int32_t n_frequencies_position, int32_t n_frequencies_direction,
                            int32_t append_input, int32_t skip_mask, float* sigma, float* rgb, int32_t tap, void* tap_out, nrc_stream_t stream);
+
+/* =====================================================================================================
+ * Group 18 -- the vanilla NeRF block, TRAINING: a forward that keeps what the backward needs, and the backward through the whole block
+ *            (csrc/nerf_net.hip: k_nerf_forward<W, 2>; csrc/nerf_grad.hip).  Replaces autograd through NeRFBlock.forward (Model.py:59-83) for the block's
+ *            PARAMETERS; positions and directions receive no gradient.  cfg as in group 17.  Supported: everything group 17 supports with
+ *            n_color_layers = 1 (nrc_nerf_train_supported; a deeper colour head: NRC_ERR_UNSUPPORTED, the caller trains on torch).
+ *            Arithmetic contract (fp16 MFMA operands, f32 accumulation, one power-of-two scale, fixed summation order): top of csrc/nerf_grad.hip.
+ *
+ *   nrc_nerf_train_workspace_bytes: one caller-allocated DEVICE buffer (16-byte aligned) shared by the forward and the backward of ONE batch of M rows;
+ *            its layout is private.  With Mp = M rounded up to 128 rows and W = width it holds 256 bytes of header, the saved fp16 operands
+ *            (Mp x 2 x (64 + 32 + (n_layers + 1) W + W / 2) bytes), the fp16 pre-activation gradients (Mp x 2 x (32 + (n_layers + 1) W + W / 2) bytes) --
+ *            9 984 bytes per row for the 8 x 256 block -- and ceil(Mp / nrc_nerf_wgrad_chunk_rows()) f32 partial sums of about the parameter count
+ *            each (2.4 MB per chunk for the 8 x 256 block).
+ *   nrc_nerf_wgrad_chunk_rows: rows per partial sum of the weight gradient (the sizes at which the reduction gains a term).
+ *   nrc_nerf_grad_params_floats: floats in grad_params = the block's parameter count.
+ *   nrc_nerf_packed_transposed_bytes / nrc_nerf_pack_weights_transposed: the fp16 weights in the fragment order of the data gradient (W^T as the A operand),
+ *            the SAME fp16 values as nrc_nerf_pack_weights stores (round-to-nearest-even, clamped at +-65504); params as there.  One kernel, no host
+ *            sync, capturable.
+ *   nrc_nerf_block_forward_train: nrc_nerf_block_forward with tap = 0, plus the workspace: sigma and rgb are bit-identical to that call on the same inputs
+ *            and blob, and every saved stage operand (nrc_nerf_saved_stage) is bit-identical to what tap = stage + 1 returns.
+ *   nrc_nerf_block_backward: d_sigma (M) f32, d_rgb (M, 3) f32: the upstream gradients; sigma, rgb: what the forward wrote; workspace: as the forward of the
+ *            same M rows left it; blob_transposed: nrc_nerf_pack_weights_transposed of the same parameters.  grad_scale: 0 = automatic
+ *            (2^(12 - floor(log2 max |head gradient|)), computed on the device), or a positive power of two in [2^-126, 2^126] (anything else:
+ *            NRC_ERR_INVALID).  grad_params (nrc_nerf_grad_params_floats f32): per linear in the order of params -- weight (out, in) row-major, then
+ *            bias -- UNSCALED gradients; every element is overwritten, nothing needs clearing.  stats (4 int32, DEVICE): [0] the exponent of the scale
+ *            used, [1] gradient elements whose magnitude reached the fp16 overflow threshold before the conversion (they were saturated at +-65504),
+ *            [2..3] 0.  No host synchronisation; five launches on `stream` in one linear order (capturable); two calls on the same inputs give the same bits.
+ *   nrc_nerf_saved_stage / nrc_nerf_grad_stage (tests): one stage of the workspace as (M, width) row-major fp16.  Saved stages: 0 enc_pos, 1 enc_dir,
+ *            2 .. n_layers + 1 H_1 .. H_L, n_layers + 2 F, n_layers + 3 C_1.  Gradient stages, in backward order: 0 rgb head (3 wide), 1 C_1 (W / 2),
+ *            2 F, 3 sigma head (1 wide), 4 .. n_layers + 3 H_L .. H_1.
+ *   M == 0: NRC_OK without a launch (nothing is written).  M < 0, dir_group < 1, a stage out of range, a null or misaligned pointer: NRC_ERR_INVALID.
+ * ===================================================================================================== */
+int nrc_nerf_train_supported(int32_t width, int32_t n_layers, int32_t n_color_layers, int32_t n_frequencies_position, int32_t n_frequencies_direction,
+                             int32_t append_input, int32_t skip_mask);
+int64_t nrc_nerf_train_workspace_bytes(int32_t width, int32_t n_layers, int32_t n_color_layers, int32_t n_frequencies_position,
+                                       int32_t n_frequencies_direction, int32_t append_input, int32_t skip_mask, int64_t M);
+int nrc_nerf_wgrad_chunk_rows(void);
+int64_t nrc_nerf_grad_params_floats(int32_t width, int32_t n_layers, int32_t n_color_layers, int32_t n_frequencies_position, int32_t n_frequencies_direction,
+                                    int32_t append_input, int32_t skip_mask);
+int64_t nrc_nerf_packed_transposed_bytes(int32_t width, int32_t n_layers, int32_t n_color_layers, int32_t n_frequencies_position,
+                                         int32_t n_frequencies_direction, int32_t append_input, int32_t skip_mask);
+int nrc_nerf_pack_weights_transposed(const float* const* params, int32_t n_params, int32_t width, int32_t n_layers, int32_t n_color_layers,
+                                     int32_t n_frequencies_position, int32_t n_frequencies_direction, int32_t append_input, int32_t skip_mask, void* blob,
+                                     nrc_stream_t stream);
+int nrc_nerf_block_forward_train(const float* positions, const float* directions, int64_t dir_group, int64_t M, const void* blob, int32_t width,
+                                 int32_t n_layers, int32_t n_color_layers, int32_t n_frequencies_position, int32_t n_frequencies_direction,
+                                 int32_t append_input, int32_t skip_mask, float* sigma, float* rgb, void* workspace, nrc_stream_t stream);
+int nrc_nerf_block_backward(const float* d_sigma, const float* d_rgb, const float* sigma, const float* rgb, int64_t M, const void* blob_transposed,
+                            int32_t width, int32_t n_layers, int32_t n_color_layers, int32_t n_frequencies_position, int32_t n_frequencies_direction,
+                            int32_t append_input, int32_t skip_mask, void* workspace, float grad_scale, float* grad_params, int32_t* stats,
+                            nrc_stream_t stream);
+int nrc_nerf_saved_stage(const void* workspace, int32_t width, int32_t n_layers, int32_t n_color_layers, int32_t n_frequencies_position,
+                         int32_t n_frequencies_direction, int32_t append_input, int32_t skip_mask, int64_t M, int32_t stage, void* out, nrc_stream_t stream);
+int nrc_nerf_grad_stage(const void* workspace, int32_t width, int32_t n_layers, int32_t n_color_layers, int32_t n_frequencies_position,
+                        int32_t n_frequencies_direction, int32_t append_input, int32_t skip_mask, int64_t M, int32_t stage, void* out, nrc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -46,6 +46,7 @@ PER_FILE_FLAGS = {
     'gs_mcmc.hip': ['-ffp-contract=off'],
     # no SLP vectoriser, for the reason given for ngp_net.hip: the accumulator -> operand conversions sit between MFMAs (the packed fp16 max / min are written out)
     'nerf_net.hip': ['-fno-slp-vectorize'],
+    'nerf_grad.hip': ['-fno-slp-vectorize'],   # the backward of the same block: masks and conversions between MFMAs
 }
 
 

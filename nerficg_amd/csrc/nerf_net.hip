@@ -25,50 +25,9 @@
 // part as [k-step][m-tile][lane] x 16 bytes, i.e. exactly the A fragments in the order they are consumed, so staging is a linear 16-byte copy and a
 // fragment read is one conflict-free ds_read_b128 per MFMA.  Slabs of <= 32 KB are double-buffered: while slab i feeds the MFMAs, slab i + 1 (or the
 // first slab of the NEXT part) travels L2 -> registers -> the other buffer; one barrier per slab.
-#include "ngp_net.h"
-
-#define NRC_NERF_TILE_ROWS 128
-#define NRC_NERF_MAX_PARTS 24
-#define NRC_NERF_MAX_LINEARS 14
-#define NRC_NERF_MAX_BIAS 2816   // floats: 8 x 256 + 32 (density) + 256 (feature) + 3 x 128 (colour) + 32 (rgb) + slack, padded to 32 per tile
-#define NRC_NERF_SLAB 2048   // uint4 per LDS buffer (32 KB)
-#define NRC_NERF_SLAB_TILES (NRC_NERF_SLAB / 64)   // (k-step, m-tile) fragments per slab
-#define NRC_NERF_PF (NRC_NERF_SLAB / 256)          // 16-byte loads per thread and slab
+#include "nerf_net.h"
 
 namespace {
-
-struct NerfCfg { int32_t width, n_layers, n_color_layers, n_freq_pos, n_freq_dir, append_input, skip_mask; };
-
-struct NerfPart {
-    uint32_t off;       // first uint4 of the part in the blob
-    uint32_t first;     // uint4 in its first slab
-    int16_t nmt, nks;   // m-tiles (32 output neurons each), k-steps (16 inputs each)
-    int16_t src;        // index of the weight in the parameter list
-    int16_t natural;    // 1: k in NATURAL order (encodings), 0: ACC order (converted accumulators)
-    int32_t rows, ld, col_off, kvalid;
-};
-struct NerfLinear { uint32_t off; int32_t rows, nmt, src; };   // bias block: off in floats behind bias_base, nmt x 2 x 16 floats in accumulator order
-struct NerfLayout {
-    int32_t n_parts, n_linears;
-    uint32_t w_total;      // uint4 in the weight region
-    uint32_t b_total;      // floats in the bias region (behind the weights)
-    NerfPart part[NRC_NERF_MAX_PARTS + 1];   // [n_parts]: off = w_total, first = 0
-    NerfLinear lin[NRC_NERF_MAX_LINEARS];
-};
-
-inline int enc_width(int n_freq, int append) { return 3 * 2 * n_freq + (append ? 3 : 0); }
-
-bool cfg_supported(const NerfCfg& c) {
-    if (c.width != 128 && c.width != 256) return false;
-    if (c.n_layers < 1 || c.n_layers > 8 || c.n_color_layers < 1 || c.n_color_layers > 3) return false;
-    if (c.n_freq_pos < 0 || c.n_freq_pos > 10 || c.n_freq_dir < 0 || c.n_freq_dir > 4) return false;
-    if (c.append_input != 0 && c.append_input != 1) return false;
-    const int np = enc_width(c.n_freq_pos, c.append_input), nd = enc_width(c.n_freq_dir, c.append_input);
-    if (np < 1 || np > 64 || nd < 1 || nd > 32) return false;
-    // bit k: the encoded position re-enters in front of layer k (0-based), 1 <= k <= n_layers - 1; the module is ill-formed for k = n_layers
-    if (c.skip_mask < 0 || (c.skip_mask & ~((1 << c.n_layers) - 2)) != 0) return false;
-    return true;
-}
 
 // Parameter list order: [initial_layers[0..L-1], density_layer, feature_layer, colour linears 0..n_color_layers-1, rgb linear] x (weight, bias).
 void make_layout(const NerfCfg& c, NerfLayout& L) {
@@ -76,9 +35,7 @@ void make_layout(const NerfCfg& c, NerfLayout& L) {
     int n = 0, nl = 0;
     uint32_t off = 0, boff = 0;
     auto part = [&](int nmt, int nks, int src, int natural, int rows, int ld, int col_off, int kvalid) {
-        const int sk = nks < NRC_NERF_SLAB_TILES / nmt ? nks : NRC_NERF_SLAB_TILES / nmt;
-        L.part[n++] = NerfPart{off, (uint32_t)(sk * nmt * 64), (int16_t)nmt, (int16_t)nks, (int16_t)src, (int16_t)natural, rows, ld, col_off, kvalid};
-        off += (uint32_t)(nmt * nks * 64);
+        L.part[n++] = make_part(off, nmt, nks, src, natural, rows, ld, col_off, kvalid);
     };
     auto linear = [&](int rows, int nmt, int src) { L.lin[nl++] = NerfLinear{boff, rows, nmt, src}; boff += (uint32_t)(nmt * 32); };
     int lin = 0;
@@ -95,19 +52,7 @@ void make_layout(const NerfCfg& c, NerfLayout& L) {
     part(NM / 2, 2, 2 * lin, 1, W / 2, W + nd, W, nd); linear(W / 2, NM / 2, 2 * lin + 1); lin++;   // ... and encoded direction BEHIND them
     for (int q = 1; q < c.n_color_layers; q++, lin++) { part(NM / 2, W / 32, 2 * lin, 0, W / 2, W / 2, 0, W / 2); linear(W / 2, NM / 2, 2 * lin + 1); }
     part(1, W / 32, 2 * lin, 0, 3, W / 2, 0, W / 2); linear(3, 1, 2 * lin + 1); lin++;
-    L.n_parts = n; L.n_linears = nl; L.w_total = off; L.b_total = boff;   // boff <= NRC_NERF_MAX_BIAS for every supported shape (a multiple of 32)
-    L.part[n] = NerfPart{off, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int k = n + 1; k <= NRC_NERF_MAX_PARTS; k++) L.part[k] = L.part[n];
-    for (int k = nl; k < NRC_NERF_MAX_LINEARS; k++) L.lin[k] = NerfLinear{0, 0, 0, 0};
-}
-
-struct NerfParams { const float* p[2 * NRC_NERF_MAX_LINEARS]; };
-
-__device__ __forceinline__ _Float16 to_h_sat(float v) {
-    const _Float16 lim = (_Float16)65504.f;
-    _Float16 h = (_Float16)v;
-    h = h > lim ? lim : h;
-    return h < -lim ? -lim : h;
+    close_layout(L, n, nl, off, boff);   // boff <= NRC_NERF_MAX_BIAS for every supported shape (a multiple of 32)
 }
 
 __global__ void __launch_bounds__(256) k_nerf_pack(NerfParams P, NerfLayout L, uint4* __restrict__ blob) {
@@ -139,55 +84,6 @@ __global__ void __launch_bounds__(256) k_nerf_pack(NerfParams P, NerfLayout L, u
 }
 
 // ---- forward ---------------------------------------------------------------------------------------------------------------------------
-struct Stream {               // the weight stream of one workgroup: which part comes next, which LDS buffer holds its first slab
-    const uint4* blob;
-    uint4* lds;
-    int p, cur;
-};
-
-// acc += W_part . B.  NKS k-steps of B, NMT m-tiles; the part's first slab is in buffer st.cur on entry, the next part's first slab on exit.
-template <int NMT, int NKS>
-__device__ __forceinline__ void gemm_part(f16v (&acc)[NMT], const h8* B, const NerfLayout& L, Stream& st, int tid, int lane) {
-    constexpr int SK = NKS < NRC_NERF_SLAB_TILES / NMT ? NKS : NRC_NERF_SLAB_TILES / NMT, NS = NKS / SK, SLAB = SK * NMT * 64;
-    static_assert(NKS % SK == 0 && SLAB <= NRC_NERF_SLAB, "slab shape");
-    const uint32_t off = L.part[st.p].off, next_off = L.part[st.p + 1].off, next_cnt = L.part[st.p + 1].first;
-#pragma unroll
-    for (int i = 0; i < NS; i++) {
-        const uint4* src = (i + 1 < NS) ? st.blob + off + (i + 1) * SLAB : st.blob + next_off;
-        const uint32_t cnt = (i + 1 < NS) ? (uint32_t)SLAB : next_cnt;
-        uint4 pf[NRC_NERF_PF];
-#pragma unroll
-        for (int q = 0; q < NRC_NERF_PF; q++) {
-            const uint32_t e = (uint32_t)tid + 256u * q;
-            pf[q] = make_uint4(0u, 0u, 0u, 0u);
-            if (e < cnt) pf[q] = src[e];
-        }
-        // the slab's SK x NMT fragments in the order of use, DEPTH reads ahead of the MFMA that consumes them: with one wave per SIMD nothing else
-        // hides the LDS latency (two reads in flight, the compiler's own schedule, left the matrix pipe idle three clocks out of four)
-        const uint4* buf = st.lds + st.cur * NRC_NERF_SLAB + lane;
-        constexpr int NT = SK * NMT, WANT = NMT < 8 ? 4 : 8, DEPTH = NT < WANT ? NT : WANT;   // (eight at W = 128 would cost that width its second wave per SIMD)
-        uint4 ring[DEPTH];
-#pragma unroll
-        for (int t = 0; t < DEPTH; t++) ring[t] = buf[t * 64];
-        __builtin_amdgcn_sched_barrier(0);   // (the scheduler otherwise sinks every read back to its use)
-#pragma unroll
-        for (int t = 0; t < NT; t++) {
-            acc[t % NMT] = NRC_MFMA(*reinterpret_cast<const h8*>(&ring[t % DEPTH]), B[i * SK + t / NMT], acc[t % NMT]);
-            if (t + DEPTH < NT) ring[t % DEPTH] = buf[(t + DEPTH) * 64];
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        uint4* nb = st.lds + (st.cur ^ 1) * NRC_NERF_SLAB;
-#pragma unroll
-        for (int q = 0; q < NRC_NERF_PF; q++) {
-            const uint32_t e = (uint32_t)tid + 256u * q;
-            if (e < cnt) nb[e] = pf[q];
-        }
-        __syncthreads();
-        st.cur ^= 1;
-    }
-    st.p++;
-}
-
 template <int NMT>
 __device__ __forceinline__ void load_bias(f16v (&acc)[NMT], const float* bias, int hh) {
 #pragma unroll
@@ -199,22 +95,6 @@ __device__ __forceinline__ void load_bias(f16v (&acc)[NMT], const float* bias, i
             acc[mt][4 * q] = v.x; acc[mt][4 * q + 1] = v.y; acc[mt][4 * q + 2] = v.z; acc[mt][4 * q + 3] = v.w;
         }
     }
-}
-
-// accumulator -> next operand: fp16 (RNE), then ReLU (optional), then saturation, the last two packed
-template <bool RELU>
-__device__ __forceinline__ h8 to_operand(const f16v& acc, int g) {
-    h8 f;
-#pragma unroll
-    for (int j = 0; j < 8; j++) f[j] = (_Float16)acc[8 * g + j];
-    const _Float16 m = (_Float16)65504.f, lo = RELU ? (_Float16)0.f : -m;
-    const h8 vlo = {lo, lo, lo, lo, lo, lo, lo, lo}, vhi = {m, m, m, m, m, m, m, m};
-    return __builtin_elementwise_min(__builtin_elementwise_max(f, vlo), vhi);
-}
-template <int NMT, bool RELU>
-__device__ __forceinline__ void to_operands(const f16v (&acc)[NMT], h8* H) {
-#pragma unroll
-    for (int mt = 0; mt < NMT; mt++) { H[2 * mt] = to_operand<RELU>(acc[mt], 0); H[2 * mt + 1] = to_operand<RELU>(acc[mt], 1); }
 }
 
 // sin and cos of an f32 argument, |error| <= 2^-22 for |a| <= 4096 (the contract at the top of the file; tests/nerf_mlp_ref.py restates the sequence)
@@ -281,7 +161,16 @@ __device__ __forceinline__ void tap_acc(const h8* H, int width, _Float16* out, i
         for (int j = 0; j < 8; j++) out[i * width + 16 * s + 8 * (j >> 2) + 4 * hh + (j & 3)] = H[s][j];
 }
 
-template <int W, bool TAP>
+// training (TAP == 2): every stage's operand as the fragments the lanes hold, padded rows included, into the workspace behind tap_out (NerfWs)
+template <int N>
+__device__ __forceinline__ void save_stage(const h8* F, uint4* ws, const NerfWs& S, int t, int64_t tile32, int lane) {
+    uint4* dst = ws + S.stage_base(S.saved_ks(t)) + tile32 * N * 64 + lane;
+#pragma unroll
+    for (int s = 0; s < N; s++) dst[s * 64] = *reinterpret_cast<const uint4*>(&F[s]);
+}
+
+// TAP: 0 = inference, 1 = one stage to tap_out (tests), 2 = training: every stage into the workspace
+template <int W, int TAP>
 __global__ void __launch_bounds__(256) k_nerf_forward(const float* __restrict__ positions, const float* __restrict__ directions, int64_t dir_group, int64_t M,
                                                       const uint4* __restrict__ blob, NerfCfg c, NerfLayout L, float* __restrict__ sigma,
                                                       float* __restrict__ rgb, int tap, _Float16* __restrict__ tap_out) {
@@ -310,7 +199,11 @@ __global__ void __launch_bounds__(256) k_nerf_forward(const float* __restrict__ 
         encode_freq<2>(dp[0], dp[1], dp[2], c.n_freq_dir, c.append_input, hh, ED);
     }
     const int n_pos = 6 * c.n_freq_pos + (c.append_input ? 3 : 0), n_dir = 6 * c.n_freq_dir + (c.append_input ? 3 : 0);
-    if constexpr (TAP) {
+    [[maybe_unused]] NerfWs S{(int64_t)gridDim.x * (NRC_NERF_TILE_ROWS / 32), NK, c.n_layers};
+    [[maybe_unused]] uint4* ws = reinterpret_cast<uint4*>(tap_out);
+    [[maybe_unused]] const int64_t tile32 = (int64_t)blockIdx.x * (NRC_NERF_TILE_ROWS / 32) + (tid >> 6);
+    if constexpr (TAP == 2) { save_stage<4>(EP, ws, S, 0, tile32, lane); save_stage<2>(ED, ws, S, 1, tile32, lane); }
+    if constexpr (TAP == 1) {
         if (valid && tap == 1) tap_natural<4>(EP, n_pos, tap_out, i, hh);
         if (valid && tap == 2) tap_natural<2>(ED, n_dir, tap_out, i, hh);
     }
@@ -322,13 +215,15 @@ __global__ void __launch_bounds__(256) k_nerf_forward(const float* __restrict__ 
     load_bias<NM>(acc, bias + L.lin[li++].off, hh);
     gemm_part<NM, 4>(acc, EP, L, st, tid, lane);
     to_operands<NM, true>(acc, H);
-    if constexpr (TAP) if (valid && tap == 3) tap_acc<NK>(H, W, tap_out, i, hh);
+    if constexpr (TAP == 1) if (valid && tap == 3) tap_acc<NK>(H, W, tap_out, i, hh);
+    if constexpr (TAP == 2) save_stage<NK>(H, ws, S, 2, tile32, lane);
     for (int l = 1; l < c.n_layers; l++) {
         load_bias<NM>(acc, bias + L.lin[li++].off, hh);
         gemm_part<NM, NK>(acc, H, L, st, tid, lane);
         if ((c.skip_mask >> l) & 1) gemm_part<NM, 4>(acc, EP, L, st, tid, lane);
         to_operands<NM, true>(acc, H);
-        if constexpr (TAP) if (valid && tap == 3 + l) tap_acc<NK>(H, W, tap_out, i, hh);
+        if constexpr (TAP == 1) if (valid && tap == 3 + l) tap_acc<NK>(H, W, tap_out, i, hh);
+        if constexpr (TAP == 2) save_stage<NK>(H, ws, S, 2 + l, tile32, lane);
     }
     {   // density head: row 0 of a one-tile part
         f16v a1[1];
@@ -340,7 +235,8 @@ __global__ void __launch_bounds__(256) k_nerf_forward(const float* __restrict__ 
     gemm_part<NM, NK>(acc, H, L, st, tid, lane);
     to_operands<NM, false>(acc, H);
     int t = 3 + c.n_layers;
-    if constexpr (TAP) if (valid && tap == t) tap_acc<NK>(H, W, tap_out, i, hh);
+    if constexpr (TAP == 1) if (valid && tap == t) tap_acc<NK>(H, W, tap_out, i, hh);
+    if constexpr (TAP == 2) save_stage<NK>(H, ws, S, c.n_layers + 2, tile32, lane);
     // colour head: [features, encoded direction] -> W/2, then (n_color_layers - 1) x W/2 -> W/2, then 3
     f16v ac[NM / 2];
     h8 C[NK / 2];
@@ -349,13 +245,14 @@ __global__ void __launch_bounds__(256) k_nerf_forward(const float* __restrict__ 
     gemm_part<NM / 2, 2>(ac, ED, L, st, tid, lane);
     to_operands<NM / 2, true>(ac, C);
     t++;
-    if constexpr (TAP) if (valid && tap == t) tap_acc<NK / 2>(C, W / 2, tap_out, i, hh);
+    if constexpr (TAP == 1) if (valid && tap == t) tap_acc<NK / 2>(C, W / 2, tap_out, i, hh);
+    if constexpr (TAP == 2) save_stage<NK / 2>(C, ws, S, c.n_layers + 3, tile32, lane);
     for (int q = 1; q < c.n_color_layers; q++) {
         load_bias<NM / 2>(ac, bias + L.lin[li++].off, hh);
         gemm_part<NM / 2, NK / 2>(ac, C, L, st, tid, lane);
         to_operands<NM / 2, true>(ac, C);
         t++;
-        if constexpr (TAP) if (valid && tap == t) tap_acc<NK / 2>(C, W / 2, tap_out, i, hh);
+        if constexpr (TAP == 1) if (valid && tap == t) tap_acc<NK / 2>(C, W / 2, tap_out, i, hh);
     }
     {
         f16v a1[1];
@@ -429,14 +326,44 @@ int nrc_nerf_block_forward(const float* positions, const float* directions, int6
     hipStream_t s = (hipStream_t)stream;
     _Float16* to = (_Float16*)tap_out;
     if (width == 256) {
-        if (tap) hipLaunchKernelGGL((k_nerf_forward<256, true>), grid, block, 0, s, positions, directions, dir_group, M, (const uint4*)blob, c, L, sigma, rgb, (int)tap, to);
-        else hipLaunchKernelGGL((k_nerf_forward<256, false>), grid, block, 0, s, positions, directions, dir_group, M, (const uint4*)blob, c, L, sigma, rgb, 0, to);
+        if (tap) hipLaunchKernelGGL((k_nerf_forward<256, 1>), grid, block, 0, s, positions, directions, dir_group, M, (const uint4*)blob, c, L, sigma, rgb, (int)tap, to);
+        else hipLaunchKernelGGL((k_nerf_forward<256, 0>), grid, block, 0, s, positions, directions, dir_group, M, (const uint4*)blob, c, L, sigma, rgb, 0, to);
     } else {
-        if (tap) hipLaunchKernelGGL((k_nerf_forward<128, true>), grid, block, 0, s, positions, directions, dir_group, M, (const uint4*)blob, c, L, sigma, rgb, (int)tap, to);
-        else hipLaunchKernelGGL((k_nerf_forward<128, false>), grid, block, 0, s, positions, directions, dir_group, M, (const uint4*)blob, c, L, sigma, rgb, 0, to);
+        if (tap) hipLaunchKernelGGL((k_nerf_forward<128, 1>), grid, block, 0, s, positions, directions, dir_group, M, (const uint4*)blob, c, L, sigma, rgb, (int)tap, to);
+        else hipLaunchKernelGGL((k_nerf_forward<128, 0>), grid, block, 0, s, positions, directions, dir_group, M, (const uint4*)blob, c, L, sigma, rgb, 0, to);
     }
     NRC_LAUNCH_CHECK();
     NRC_STAGE((hipStream_t)stream, "k_nerf_forward");
+    return NRC_OK;
+}
+
+int nrc_nerf_train_supported(int32_t width, int32_t n_layers, int32_t n_color_layers, int32_t n_frequencies_position, int32_t n_frequencies_direction,
+                             int32_t append_input, int32_t skip_mask) {
+    return train_cfg_supported(NerfCfg{width, n_layers, n_color_layers, n_frequencies_position, n_frequencies_direction, append_input, skip_mask}) ? 1 : 0;
+}
+
+int nrc_nerf_block_forward_train(const float* positions, const float* directions, int64_t dir_group, int64_t M, const void* blob, int32_t width,
+                                 int32_t n_layers, int32_t n_color_layers, int32_t n_frequencies_position, int32_t n_frequencies_direction,
+                                 int32_t append_input, int32_t skip_mask, float* sigma, float* rgb, void* workspace, nrc_stream_t stream) {
+    NRC_ENTER();
+    const NerfCfg c{width, n_layers, n_color_layers, n_frequencies_position, n_frequencies_direction, append_input, skip_mask};
+    if (!train_cfg_supported(c)) return NRC_ERR_UNSUPPORTED;
+    if (M < 0 || dir_group < 1) return NRC_ERR_INVALID;
+    if (M == 0) return NRC_OK;
+    if (!positions || !directions || !blob || !sigma || !rgb || !workspace || (reinterpret_cast<uintptr_t>(blob) & 15u) ||
+        (reinterpret_cast<uintptr_t>(workspace) & 15u)) return NRC_ERR_INVALID;
+    const int64_t blocks = nrc_cdiv(M, NRC_NERF_TILE_ROWS);
+    if (blocks > 0x7fffffff) return NRC_ERR_INVALID;
+    NerfLayout L;
+    make_layout(c, L);
+    NRC_STAGE((hipStream_t)stream, nullptr);
+    const dim3 grid((unsigned)blocks), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    _Float16* ws = (_Float16*)workspace;
+    if (width == 256) hipLaunchKernelGGL((k_nerf_forward<256, 2>), grid, block, 0, s, positions, directions, dir_group, M, (const uint4*)blob, c, L, sigma, rgb, 0, ws);
+    else hipLaunchKernelGGL((k_nerf_forward<128, 2>), grid, block, 0, s, positions, directions, dir_group, M, (const uint4*)blob, c, L, sigma, rgb, 0, ws);
+    NRC_LAUNCH_CHECK();
+    NRC_STAGE((hipStream_t)stream, "k_nerf_forward_train");
     return NRC_OK;
 }
 

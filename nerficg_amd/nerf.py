@@ -1,7 +1,9 @@
 """nerficg_amd.nerf -- host-side mirror of the reference's vanilla NeRF hot path (config 1: nerf_lego.yaml, pure PyTorch, runs
 on CPU or on the GPU through torch): FrequencyEncoding, NeRFBlock, stratified + PDF sampling, sample integration and the
 hierarchical (coarse -> fine) ray renderer.  `fused_forward` / `render_rays(fused=True)` run the block's INFERENCE forward as one HIP kernel
-(csrc/nerf_net.hip, header group 17: fp16 MFMA operands, f32 accumulation); training and everything else stay on torch.
+(csrc/nerf_net.hip, header group 17: fp16 MFMA operands, f32 accumulation).  `fused_apply` / `render_rays(fused_train=True)` are the opt-in TRAINING
+path: a forward that keeps every stage's fp16 operand and a backward through the whole block (csrc/nerf_grad.hip, header group 18) behind an autograd
+function that returns gradients for the block's parameters; sampling, sorting and compositing stay torch autograd.  Everything else stays on torch.
 
 Reference: src/Methods/NeRF/utils.py:12-136, src/Methods/NeRF/Model.py:10-83, src/Methods/NeRF/Renderer.py:20-95.
 Pinned against golden vectors generated from the reference (tests/test_host_golden.py).  `integrate_samples` is also the
@@ -12,7 +14,7 @@ from __future__ import annotations
 import torch
 
 __all__ = ['FrequencyEncoding', 'NeRFBlock', 'generate_samples', 'generate_samples_from_pdf', 'integrate_samples', 'render_rays', 'fused_forward',
-           'fused_config', 'fused_tap_names']
+           'fused_config', 'fused_tap_names', 'fused_apply', 'fused_grad_stats']
 
 
 class FrequencyEncoding(torch.nn.Module):
@@ -157,6 +159,114 @@ def fused_forward(block: NeRFBlock, positions: torch.Tensor, directions: torch.T
     return (sigma, rgb) if tap is None else (sigma, rgb, tapped)
 
 
+def _train_blobs(block: NeRFBlock, cfg, device):
+    """(forward blob, transposed blob of the data gradient): the same fp16 values, the second cached under the key of the first."""
+    import ctypes
+    from . import _lib
+    blob = _packed_blob(block, cfg, device)
+    cache = block._fused_cache
+    if cache.get('key_t') != cache['key']:
+        lib = _lib.load()
+        n_bytes = lib.nrc_nerf_packed_transposed_bytes(*cfg)
+        if cache.get('blob_t') is None or cache['blob_t'].numel() != n_bytes or cache['blob_t'].device != device:
+            cache['blob_t'] = torch.empty(n_bytes, dtype=torch.uint8, device=device)
+        params = [t for lin in _block_linears(block) for t in (lin.weight, lin.bias)]
+        ptrs = (ctypes.c_void_p * len(params))(*[t.data_ptr() for t in params])
+        _lib.check(lib.nrc_nerf_pack_weights_transposed(ctypes.cast(ptrs, ctypes.c_void_p), len(params), *cfg, _lib.ptr(cache['blob_t']),
+                                                        _lib.stream_of(cache['blob_t'])), 'nerf_pack_weights_transposed')
+        cache['key_t'] = cache['key']
+        cache['packs_t'] = cache.get('packs_t', 0) + 1
+    return blob, cache['blob_t']
+
+
+class _FusedBlock(torch.autograd.Function):
+    """Training forward + backward of one block (header group 18).  Gradients for the parameters only."""
+
+    @staticmethod
+    def forward(ctx, block, cfg, positions, directions, dir_group, grad_scale, *params):
+        from . import _lib
+        lib, m, device = _lib.load(), positions.shape[0], positions.device
+        with torch.cuda.device(device):
+            blob, blob_t = _train_blobs(block, cfg, device)
+            cache = block._fused_cache
+            n_bytes = lib.nrc_nerf_train_workspace_bytes(*cfg, m)
+            pool = cache.setdefault('workspaces', [])        # one per forward whose backward is still to come; grown on demand
+            ws = pool.pop() if pool else None
+            if ws is None or ws.numel() < n_bytes or ws.device != device:
+                ws = torch.empty(n_bytes, dtype=torch.uint8, device=device)
+            sigma = torch.empty(m, 1, dtype=torch.float32, device=device)
+            rgb = torch.empty(m, 3, dtype=torch.float32, device=device)
+            _lib.check(lib.nrc_nerf_block_forward_train(_lib.ptr(positions), _lib.ptr(directions), int(dir_group), m, _lib.ptr(blob), *cfg, _lib.ptr(sigma),
+                                                        _lib.ptr(rgb), _lib.ptr(ws), _lib.stream_of(positions)), 'nerf_block_forward_train')
+        ctx.block, ctx.cfg, ctx.m, ctx.grad_scale, ctx.ws, ctx.blob_t = block, cfg, m, grad_scale, ws, blob_t
+        ctx.save_for_backward(sigma, rgb)
+        return sigma, rgb
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_sigma, d_rgb):
+        from . import _lib
+        lib = _lib.load()
+        sigma, rgb = ctx.saved_tensors
+        block, cfg = ctx.block, ctx.cfg
+        d_sigma, d_rgb = d_sigma.contiguous().float(), d_rgb.contiguous().float()
+        with torch.cuda.device(sigma.device):
+            grad = torch.empty(lib.nrc_nerf_grad_params_floats(*cfg), dtype=torch.float32, device=sigma.device)
+            stats = torch.empty(4, dtype=torch.int32, device=sigma.device)
+            _lib.check(lib.nrc_nerf_block_backward(_lib.ptr(d_sigma), _lib.ptr(d_rgb), _lib.ptr(sigma), _lib.ptr(rgb), ctx.m, _lib.ptr(ctx.blob_t), *cfg,
+                                                   _lib.ptr(ctx.ws), float(ctx.grad_scale or 0.0), _lib.ptr(grad), _lib.ptr(stats), _lib.stream_of(sigma)),
+                       'nerf_block_backward')
+        cache = block._fused_cache
+        cache['stats'], cache['last_workspace'] = stats, ctx.ws
+        cache.setdefault('workspaces', []).append(ctx.ws)
+        ctx.ws = None
+        out, at = [], 0
+        for k, lin in enumerate(_block_linears(block)):
+            for j, t in enumerate((lin.weight, lin.bias)):
+                n = t.numel()
+                out.append(grad[at:at + n].view(t.shape) if ctx.needs_input_grad[6 + 2 * k + j] else None)
+                at += n
+        return (None,) * 6 + tuple(out)
+
+
+def fused_apply(block: NeRFBlock, positions: torch.Tensor, directions: torch.Tensor, dir_group: int = 1, grad_scale: float | None = None):
+    """`NeRFBlock.forward` without noise for TRAINING -> (sigma (M, 1), rgb (M, 3)), f32, differentiable with respect to the block's parameters: the
+    forward keeps every stage's fp16 operand, the backward runs the whole block on the matrix units (csrc/nerf_grad.hip) and autograd accumulates
+    its result into `.grad` as usual.  `grad_scale`: a positive power of two for the fp16 gradients, None = chosen on the device per call.  Second-order
+    gradients are not supported, positions and directions receive none.  Under `torch.no_grad()`, or when no parameter requires grad, this is
+    `fused_forward`.  For CPU tensors, a block `nrc_nerf_train_supported` refuses, non-f32 parameters, an empty batch, or positions / directions that
+    require grad it returns `block(positions, expanded directions)` with torch's bits and torch's autograd."""
+    params = [t for lin in _block_linears(block) for t in (lin.weight, lin.bias)]
+    if not torch.is_grad_enabled() or not any(p.requires_grad for p in block.parameters()):
+        return fused_forward(block, positions, directions, dir_group)
+    m = positions.shape[0]
+    eligible = (m > 0 and positions.is_cuda and directions.is_cuda and positions.dtype == torch.float32 and directions.dtype == torch.float32
+                and all(p.is_cuda and p.device == positions.device for p in block.parameters())
+                and not (positions.requires_grad or directions.requires_grad))
+    cfg = fused_config(block) if eligible else None
+    if cfg is not None:
+        from . import _lib
+        if not _lib.load().nrc_nerf_train_supported(*cfg):
+            cfg = None
+    if cfg is None:
+        expanded = directions if dir_group == 1 else directions[:, None, :].expand(-1, dir_group, -1).reshape(-1, 3)[:m]
+        return block(positions, expanded)
+    if grad_scale is not None:
+        import math
+        if not (grad_scale > 0.0 and math.frexp(grad_scale)[0] == 0.5 and 2.0 ** -126 <= grad_scale <= 2.0 ** 126):
+            raise ValueError(f'grad_scale {grad_scale} is not a positive power of two in [2^-126, 2^126]')
+    positions, directions = positions.contiguous(), directions.contiguous()
+    if directions.shape[0] * dir_group < m:
+        raise ValueError(f'{directions.shape[0]} direction rows x dir_group {dir_group} do not cover {m} samples')
+    return _FusedBlock.apply(block, cfg, positions, directions, int(dir_group), grad_scale, *params)
+
+
+def fused_grad_stats(block: NeRFBlock):
+    """The statistics of the block's last fused backward, an int32 tensor ON THE DEVICE (reading it is the caller's synchronisation): [0] the exponent of
+    the gradient scale that was used, [1] gradient elements that overflowed fp16 and were saturated at +-65504, [2..3] 0.  None before the first."""
+    return block.__dict__.get('_fused_cache', {}).get('stats')
+
+
 def generate_samples(n_rays: int, n_samples: int, near_plane: float, far_plane: float, randomize_samples: bool, dtype=torch.float32,
                      device=None) -> torch.Tensor:
     """Depths of the coarse pass (utils.py:57-75): `n_samples` evenly spaced values in [near, far] for every ray; with `randomize_samples` each
@@ -210,10 +320,14 @@ def integrate_samples(depth_samples, ray_directions, densities, colors, backgrou
 
 def render_rays(coarse_nerf: NeRFBlock | None, nerf: NeRFBlock, origin, direction, view_direction, near_plane: float, far_plane: float,
                 background_color, ray_batch_size: int = 8192, n_samples_coarse_nerf: int = 64, n_samples_nerf: int = 192,
-                randomize_samples: bool = False, random_noise_density: float = 0.0, fused: bool = False) -> dict[str, torch.Tensor]:
+                randomize_samples: bool = False, random_noise_density: float = 0.0, fused: bool = False, fused_train: bool = False) -> dict[str, torch.Tensor]:
     """NeRFRayRenderingComponent.forward (Renderer.py:29-95): chunked coarse pass -> PDF samples -> sorted union -> fine pass.  `fused`: the two network
-    calls go through `fused_forward` (one direction row per ray); with density noise, and wherever `fused_forward` falls back, the torch path runs."""
+    calls go through `fused_forward` (one direction row per ray); with density noise, and wherever `fused_forward` falls back, the torch path runs.
+    `fused_train`: they go through `fused_apply` instead -- the training path, differentiable with respect to the blocks' parameters; with density
+    noise the torch path runs."""
     def query(block, pos, vd):
+        if fused_train and not random_noise_density > 0.0:
+            return fused_apply(block, pos.reshape(-1, 3), vd, dir_group=pos.shape[1])
         if fused and not random_noise_density > 0.0:
             return fused_forward(block, pos.reshape(-1, 3), vd, dir_group=pos.shape[1])
         return block(pos.reshape(-1, 3), vd[:, None, :].expand_as(pos).reshape(-1, 3), random_noise_density)

@@ -20,9 +20,11 @@ prof() {
 # MODE=ngp: the reverse -- everything but the 3DGS-only runs, for a change confined to the InstantNGP sources (tools/make_profile_summary.py ROUND ngp_net.hip).
 # MODE=nerf: a change confined to csrc/nerf_net.hip -- the bench command (all durations; no bench leg runs the NeRF block) and the fused NeRF block's own
 # trace and counter runs (tools/bench_nerf_fused.py); tools/make_profile_summary.py ROUND nerf_net.hip carries every other kernel's counters over.
+# MODE=nerf_train: the trace and counter runs of the block's training path alone (tools/bench_nerf_train.py; no bench command) -- a call of its own after
+# MODE=nerf when csrc/nerf_grad.hip or the shared csrc/nerf_net.h changed; then tools/make_profile_summary.py ROUND nerf_net.hip nerf_net.h nerf_grad.hip.
 MODE=${1:-all}
 # the full bench command (bench.py --full --steps 20 --warmup 5, every leg): the per-kernel averages of the InstantNGP kernels must agree with the bench line
-prof 900 $O/bench_stats.log --kernel-trace --stats --output-format csv -d $O/bench_stats -- python3 $R/bench.py --full --steps 20 --warmup 5
+[ "$MODE" != nerf_train ] && prof 900 $O/bench_stats.log --kernel-trace --stats --output-format csv -d $O/bench_stats -- python3 $R/bench.py --full --steps 20 --warmup 5
 # the 3DGS kernels at ONE size (the bench command runs 1 M and 6 M Gaussians through the same kernel names)
 if [ "$MODE" = nerf ] || [ "$MODE" = all ]; then
 prof 300 $O/nerf_stats.log --kernel-trace --stats --output-format csv -d $O/nerf_stats -- python3 $R/tools/bench_nerf_fused.py 5
@@ -31,8 +33,16 @@ for set in "GRBM_GUI_ACTIVE SQ_WAVES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_VA
   prof 300 $O/pmcnf_$tag.log --pmc $set --kernel-trace --kernel-include-regex k_nerf --output-format csv -d $O/pmcnf_$tag -- python3 $R/tools/bench_nerf_fused.py 5
 done
 fi
-if [ "$MODE" = nerf ]; then
-find $O -name "*.db" -delete; find $O -name "*_agent_info.csv" -delete; find $O -path "*_stats/*" -name "*kernel_trace.csv" -delete; du -sh $O; tail -5 $O/bench_stats.log
+if [ "$MODE" = nerf_train ] || [ "$MODE" = all ]; then
+# the training path of the same block (tools/bench_nerf_train.py): one trace, then the same counter groups, each a run of its own
+prof 400 $O/nerf_train_stats.log --kernel-trace --stats --output-format csv -d $O/nerf_train_stats -- python3 $R/tools/bench_nerf_train.py 3
+for set in "GRBM_GUI_ACTIVE SQ_WAVES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VALU_MFMA_MOPS_F16 SQ_VALU_MFMA_BUSY_CYCLES" "TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum GRBM_GUI_ACTIVE" "SQ_WAVE_CYCLES SQ_WAIT_INST_LDS SQ_INST_CYCLES_VMEM SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_VALU"; do
+  tag=$(echo $set | tr ' ' '_' | cut -c1-32)
+  prof 400 $O/pmcnt_$tag.log --pmc $set --kernel-trace --kernel-include-regex "k_nerf_(forward|dgrad|wgrad|wreduce)" --output-format csv -d $O/pmcnt_$tag -- python3 $R/tools/bench_nerf_train.py 3
+done
+fi
+if [ "$MODE" = nerf ] || [ "$MODE" = nerf_train ]; then
+find $O -name "*.db" -delete; find $O -name "*_agent_info.csv" -delete; find $O -path "*_stats/*" -name "*kernel_trace.csv" -delete; du -sh $O; [ -f $O/bench_stats.log ] && tail -5 $O/bench_stats.log
 exit 0
 fi
 if [ "$MODE" != ngp ]; then
