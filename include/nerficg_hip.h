@@ -47,8 +47,10 @@ enum {
  * earlier signature is unchanged;
  * 15 = group 16 (nrc_gs_mcmc_*: the relocation, SGLD noise and regularisers of 3DGS-MCMC) is new, every earlier signature is unchanged;
  * 16 = group 17 (nrc_nerf_*: the vanilla NeRF block's inference forward as one kernel) is new, every earlier signature is unchanged;
- * 17 = group 18 (the vanilla NeRF block's training forward and backward) is new, every earlier signature is unchanged. */
-#define NRC_ABI_VERSION 17
+ * 17 = group 18 (the vanilla NeRF block's training forward and backward) is new, every earlier signature is unchanged;
+ * 18 = group 19 (nrc_nerf_rays_* / nrc_nerf_sample_* / nrc_nerf_integrate_*: NeRF sampling, compositing and resampling) is new, every earlier signature is
+ * unchanged. */
+#define NRC_ABI_VERSION 18
 /* library identification; also used by the loader's symbol check */
 int nrc_abi_version(void);
 const char* nrc_build_info(void);
@@ -1129,6 +1131,46 @@ int nrc_nerf_saved_stage(const void* workspace, int32_t width, int32_t n_layers,
                          int32_t n_frequencies_direction, int32_t append_input, int32_t skip_mask, int64_t M, int32_t stage, void* out, nrc_stream_t stream);
 int nrc_nerf_grad_stage(const void* workspace, int32_t width, int32_t n_layers, int32_t n_color_layers, int32_t n_frequencies_position,
                         int32_t n_frequencies_direction, int32_t append_input, int32_t skip_mask, int64_t M, int32_t stage, void* out, nrc_stream_t stream);
+
+/* =====================================================================================================
+ * Group 19 -- what surrounds the vanilla NeRF block (csrc/nerf_rays.hip): stratified sampling, compositing with its backward, and the fine pass's
+ *            resampling with the sorted union of both depth sets.  Replaces src/Methods/NeRF/utils.py:57-75 (generate_samples), :78-109
+ *            (generate_samples_from_pdf), :112-136 (integrate_samples) and, in src/Methods/NeRF/Renderer.py:54, :70 and :75, the position broadcast o + d t and
+ *            sort(cat(t_coarse, t_fine)).  Dense: N rays x S samples, S the same for every ray, f32, row-major.  One wave per ray,
+ *            nrc_nerf_rays_per_group() rays per workgroup.  One launch per call, no host synchronisation, no atomics, every reduction in a fixed order
+ *            (two calls give the same bits; a ray's outputs do not depend on the other rays); capturable.  The arithmetic contract, operation by
+ *            operation: top of csrc/nerf_rays.hip; restated in tests/nerf_rays_ref.py.
+ *            Every call: NRC_ERR_UNSUPPORTED outside the supported sample counts, then NRC_ERR_INVALID before any launch for N < 0, a null required
+ *            pointer or a pointer that is not 4-byte aligned; N == 0: NRC_OK without a launch.
+ *
+ *   nrc_nerf_rays_supported(S_coarse, S_fine): S_fine == 0 asks for sampling / compositing with S = S_coarse: 1 <= S <= 1024.  S_fine != 0 asks for
+ *            resampling: 3 <= S_coarse <= 1024, 1 <= S_fine <= 1024, S_coarse + S_fine <= 2048.
+ *   nrc_nerf_sample_coarse: origins, directions (N, 3); t_row (S): the caller's evenly spaced depths; u (N, S) or NULL.  t (N, S): t_row for every ray
+ *            without u, otherwise lower + (upper - lower) u with the strata meeting at the mid points of t_row and the outer ones ending at t_row[0] /
+ *            t_row[S-1].  positions (N S, 3) = o + d t, one multiplication and one addition per component.
+ *   nrc_nerf_integrate_forward: t (N, S), directions (N, 3), sigma (N S), rgb_samples (N S, 3), background (3) or NULL, final_delta.  Segment length =
+ *            (t[i+1] - t[i], the last one final_delta) |d|; a = 1 - expf(-sigma len); w = a T; the leftover transmittance goes to the background.
+ *            rgb (N, 3), depth (N) = sum w t / alpha where the leftover is < 1, else 0; alpha (N) = 1 - leftover; weights (N, S).  No early-out.
+ *   nrc_nerf_integrate_backward: upstream d_rgb (N, 3), d_alpha (N), d_weights (N, S), each may be NULL (= zero); the forward's inputs again.
+ *            d_sigma (N S), d_rgb_samples (N S, 3).  The transmittance is recomputed; one reverse scan, no division by 1 - a.  No gradient to t, to the
+ *            directions or through depth.
+ *   nrc_nerf_sample_fine: t_coarse, weights (N, S_coarse); u with a row stride in ELEMENTS: 0 = one row of S_fine values shared by all rays, >= S_fine =
+ *            one row per ray (anything between: NRC_ERR_INVALID); origins, directions (N, 3).  t (N, S_coarse + S_fine): the ascending sort of the multiset
+ *            t_coarse u t_fine (FINITE inputs required); positions (N (S_coarse + S_fine), 3).  Optional, for tests (NULL = not written): cdf
+ *            (N, S_coarse - 1) and t_fine (N, S_fine), unsorted, in the order of u.
+ *   Stage-timer names: k_nerf_sample_coarse, k_nerf_integrate_fw, k_nerf_integrate_bw, k_nerf_sample_fine.
+ * ===================================================================================================== */
+int nrc_nerf_rays_per_group(void);
+int nrc_nerf_rays_supported(int32_t S_coarse, int32_t S_fine);
+int nrc_nerf_sample_coarse(const float* origins, const float* directions, const float* t_row, const float* u, int64_t N, int32_t S, float* t,
+                           float* positions, nrc_stream_t stream);
+int nrc_nerf_integrate_forward(const float* t, const float* directions, const float* sigma, const float* rgb_samples, const float* background,
+                               float final_delta, int64_t N, int32_t S, float* rgb, float* depth, float* alpha, float* weights, nrc_stream_t stream);
+int nrc_nerf_integrate_backward(const float* d_rgb, const float* d_alpha, const float* d_weights, const float* t, const float* directions, const float* sigma,
+                                const float* rgb_samples, const float* background, float final_delta, int64_t N, int32_t S, float* d_sigma,
+                                float* d_rgb_samples, nrc_stream_t stream);
+int nrc_nerf_sample_fine(const float* t_coarse, const float* weights, const float* u, int64_t u_stride, const float* origins, const float* directions,
+                         int64_t N, int32_t S_coarse, int32_t S_fine, float* t, float* positions, float* cdf, float* t_fine, nrc_stream_t stream);
 
 #ifdef __cplusplus
 }

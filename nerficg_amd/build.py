@@ -47,6 +47,9 @@ PER_FILE_FLAGS = {
     # no SLP vectoriser, for the reason given for ngp_net.hip: the accumulator -> operand conversions sit between MFMAs (the packed fp16 max / min are written out)
     'nerf_net.hip': ['-fno-slp-vectorize'],
     'nerf_grad.hip': ['-fno-slp-vectorize'],   # the backward of the same block: masks and conversions between MFMAs
+    # no FMA contraction: sampling and resampling are compared bit for bit with the numpy restatement of their f32 sequence (tests/nerf_rays_ref.py), and the
+    # compositing budgets count that sequence rounding by rounding; the kernels stream a few dozen bytes per sample, a fused multiply-add would buy nothing
+    'nerf_rays.hip': ['-ffp-contract=off'],
 }
 
 

@@ -3,7 +3,9 @@ on CPU or on the GPU through torch): FrequencyEncoding, NeRFBlock, stratified + 
 hierarchical (coarse -> fine) ray renderer.  `fused_forward` / `render_rays(fused=True)` run the block's INFERENCE forward as one HIP kernel
 (csrc/nerf_net.hip, header group 17: fp16 MFMA operands, f32 accumulation).  `fused_apply` / `render_rays(fused_train=True)` are the opt-in TRAINING
 path: a forward that keeps every stage's fp16 operand and a backward through the whole block (csrc/nerf_grad.hip, header group 18) behind an autograd
-function that returns gradients for the block's parameters; sampling, sorting and compositing stay torch autograd.  Everything else stays on torch.
+function that returns gradients for the block's parameters; sampling, sorting and compositing stay torch autograd.  `sample_coarse`, `composite`,
+`sample_fine` / `render_rays(device_rays=True)` are the opt-in device path for what surrounds the block: stratified sampling, compositing with its
+backward and the fine pass's resampling + sorted union as one HIP kernel each (csrc/nerf_rays.hip, header group 19).  Everything else stays on torch.
 
 Reference: src/Methods/NeRF/utils.py:12-136, src/Methods/NeRF/Model.py:10-83, src/Methods/NeRF/Renderer.py:20-95.
 Pinned against golden vectors generated from the reference (tests/test_host_golden.py).  `integrate_samples` is also the
@@ -14,7 +16,7 @@ from __future__ import annotations
 import torch
 
 __all__ = ['FrequencyEncoding', 'NeRFBlock', 'generate_samples', 'generate_samples_from_pdf', 'integrate_samples', 'render_rays', 'fused_forward',
-           'fused_config', 'fused_tap_names', 'fused_apply', 'fused_grad_stats']
+           'fused_config', 'fused_tap_names', 'fused_apply', 'fused_grad_stats', 'sample_coarse', 'sample_fine', 'composite']
 
 
 class FrequencyEncoding(torch.nn.Module):
@@ -274,22 +276,30 @@ def generate_samples(n_rays: int, n_samples: int, near_plane: float, far_plane: 
     t = torch.linspace(near_plane, far_plane, n_samples, dtype=dtype, device=device).expand(n_rays, n_samples)
     if not randomize_samples:
         return t
+    return _stratified(t, torch.rand(t.shape, dtype=dtype, device=device))
+
+
+def _stratified(t: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
     cuts = (t[:, 1:] + t[:, :-1]) * 0.5
     lower, upper = torch.cat((t[:, :1], cuts), dim=1), torch.cat((cuts, t[:, -1:]), dim=1)
-    return torch.lerp(lower, upper, torch.rand(t.shape, dtype=dtype, device=device))
+    return torch.lerp(lower, upper, u)
 
 
 def generate_samples_from_pdf(bins: torch.Tensor, values: torch.Tensor, n_samples: int, randomize_samples: bool) -> torch.Tensor:
     """Depths of the fine pass (utils.py:78-109): inverse-transform sampling of the piecewise-constant density whose K-2 inner masses
     (`values` without its ends, + 1e-5) sit between the K-1 mid points of `bins`; u is uniform (random or evenly spaced)."""
-    knots = (bins[:, 1:] + bins[:, :-1]) * 0.5
-    mass = values[:, 1:-1] + 1e-5
-    cdf = torch.nn.functional.pad(torch.cumsum(mass / mass.sum(dim=1, keepdim=True), dim=1), (1, 0))  # cdf[:, 0] = 0
-    rows = cdf.shape[0]
+    rows = bins.shape[0]
     if randomize_samples:
         u = torch.rand(rows, n_samples, device=bins.device)
     else:
         u = torch.linspace(0.0, 1.0, steps=n_samples, device=bins.device).expand(rows, n_samples).contiguous()
+    return _samples_from_pdf(bins, values, u)
+
+
+def _samples_from_pdf(bins: torch.Tensor, values: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
+    knots = (bins[:, 1:] + bins[:, :-1]) * 0.5
+    mass = values[:, 1:-1] + 1e-5
+    cdf = torch.nn.functional.pad(torch.cumsum(mass / mass.sum(dim=1, keepdim=True), dim=1), (1, 0))  # cdf[:, 0] = 0
     right = torch.searchsorted(cdf, u, right=True)
     left, right = (right - 1).clamp(min=0), right.clamp(max=cdf.shape[1] - 1)
     c0, c1, k0, k1 = cdf.gather(1, left), cdf.gather(1, right), knots.gather(1, left), knots.gather(1, right)
@@ -318,13 +328,147 @@ def integrate_samples(depth_samples, ray_directions, densities, colors, backgrou
     return rgb, depth, alpha, weights
 
 
+def _rays_eligible(n_coarse: int, n_fine: int, *tensors) -> bool:
+    """The device path of group 19 takes these tensors: all on one GPU, f32, none requiring grad while autograd records, a supported sample count."""
+    first = tensors[0]
+    if not all(t.is_cuda and t.device == first.device and t.dtype == torch.float32 for t in tensors):
+        return False
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        return False
+    from . import _lib
+    return first.shape[0] > 0 and bool(_lib.load().nrc_nerf_rays_supported(int(n_coarse), int(n_fine)))
+
+
+def sample_coarse(origins: torch.Tensor, directions: torch.Tensor, n_samples: int, near_plane: float, far_plane: float, randomize_samples: bool,
+                  u: torch.Tensor | None = None):
+    """Depths of the coarse pass and their positions -> (t (N, S), positions (N S, 3)): `generate_samples` and `o + d t` as one kernel
+    (csrc/nerf_rays.hip, header group 19).  With `randomize_samples` the offsets are `u` (N, S), drawn with `torch.rand` exactly as
+    `generate_samples` draws them when not given.  Falls back to the torch expressions of `render_rays` -- torch's bits -- for CPU tensors, non-f32
+    input, an unsupported S, or origins / directions that require grad."""
+    n = origins.shape[0]
+    if not _rays_eligible(n_samples, 0, origins, directions) or (u is not None and not _rays_eligible(n_samples, 0, u)):
+        if u is None:
+            t = generate_samples(n, n_samples, near_plane, far_plane, randomize_samples, origins.dtype, origins.device)
+        else:
+            t = _stratified(torch.linspace(near_plane, far_plane, n_samples, dtype=origins.dtype, device=origins.device).expand(n, n_samples), u)
+        return t, (origins[:, None, :] + directions[:, None, :] * t[:, :, None]).reshape(-1, 3)
+    from . import _lib
+    t_row = torch.linspace(near_plane, far_plane, n_samples, dtype=torch.float32, device=origins.device)
+    if randomize_samples and u is None:
+        u = torch.rand((n, n_samples), dtype=torch.float32, device=origins.device)
+    origins, directions, u = origins.detach().contiguous(), directions.detach().contiguous(), None if u is None else u.detach().contiguous()
+    with torch.cuda.device(origins.device):
+        t = torch.empty(n, n_samples, dtype=torch.float32, device=origins.device)
+        positions = torch.empty(n * n_samples, 3, dtype=torch.float32, device=origins.device)
+        _lib.check(_lib.load().nrc_nerf_sample_coarse(_lib.ptr(origins), _lib.ptr(directions), _lib.ptr(t_row), _lib.ptr(u), n, int(n_samples), _lib.ptr(t),
+                                                      _lib.ptr(positions), _lib.stream_of(origins)), 'nerf_sample_coarse')
+    return t, positions
+
+
+def sample_fine(t_coarse: torch.Tensor, weights: torch.Tensor, n_samples: int, randomize_samples: bool, origins: torch.Tensor, directions: torch.Tensor,
+                u: torch.Tensor | None = None):
+    """Depths of the fine pass merged with the coarse ones, and their positions -> (t (N, Sc + Sf) ascending, positions (N (Sc + Sf), 3)):
+    `generate_samples_from_pdf`, `sort(cat(t_coarse, t_fine))` and `o + d t` as one kernel (header group 19).  `u`: (N, Sf) per-ray draws or (Sf,) one row
+    for all rays; when not given it is drawn (`torch.rand`) or laid out (`torch.linspace(0, 1, Sf)`) exactly as `generate_samples_from_pdf` does.  The
+    weights carry no gradient (the reference detaches the fine depths).  Finite inputs are required.  Falls back to the torch expressions of `render_rays`
+    for CPU tensors, non-f32 input, unsupported sample counts, or depths / origins / directions that require grad."""
+    n, n_coarse = t_coarse.shape
+    weights = weights.detach()
+    if not _rays_eligible(n_coarse, n_samples, t_coarse, weights, origins, directions) or (u is not None and not _rays_eligible(n_coarse, n_samples, u)):
+        if u is None:
+            t_f = generate_samples_from_pdf(t_coarse, weights, n_samples, randomize_samples)
+        else:
+            t_f = _samples_from_pdf(t_coarse, weights, u.expand(n, n_samples).contiguous())
+        t, _ = torch.sort(torch.cat((t_coarse, t_f), dim=-1), dim=-1)
+        return t, (origins[:, None, :] + directions[:, None, :] * t[:, :, None]).reshape(-1, 3)
+    from . import _lib
+    device = t_coarse.device
+    if u is None:
+        u = (torch.rand(n, n_samples, device=device) if randomize_samples else torch.linspace(0.0, 1.0, steps=n_samples, device=device))
+    if u.shape not in ((n, n_samples), (n_samples,)):
+        raise ValueError(f'u has shape {tuple(u.shape)}, expected ({n}, {n_samples}) or ({n_samples},)')
+    u = u.detach().contiguous()
+    t_coarse, origins, directions = t_coarse.detach().contiguous(), origins.detach().contiguous(), directions.detach().contiguous()
+    weights = weights.contiguous()
+    total = n_coarse + n_samples
+    with torch.cuda.device(device):
+        t = torch.empty(n, total, dtype=torch.float32, device=device)
+        positions = torch.empty(n * total, 3, dtype=torch.float32, device=device)
+        _lib.check(_lib.load().nrc_nerf_sample_fine(_lib.ptr(t_coarse), _lib.ptr(weights), _lib.ptr(u), n_samples if u.dim() == 2 else 0, _lib.ptr(origins),
+                                                    _lib.ptr(directions), n, int(n_coarse), int(n_samples), _lib.ptr(t), _lib.ptr(positions), None, None,
+                                                    _lib.stream_of(t_coarse)), 'nerf_sample_fine')
+    return t, positions
+
+
+class _Composite(torch.autograd.Function):
+    """Compositing forward + backward (header group 19).  Gradients for sigma and rgb only; depth is not differentiable."""
+
+    @staticmethod
+    def forward(ctx, t, directions, sigma, rgb, background, final_delta):
+        from . import _lib
+        n, s = t.shape
+        with torch.cuda.device(t.device):
+            out = torch.empty(n, 3, dtype=torch.float32, device=t.device)
+            depth = torch.empty(n, 1, dtype=torch.float32, device=t.device)
+            alpha = torch.empty(n, 1, dtype=torch.float32, device=t.device)
+            weights = torch.empty(n, s, dtype=torch.float32, device=t.device)
+            _lib.check(_lib.load().nrc_nerf_integrate_forward(_lib.ptr(t), _lib.ptr(directions), _lib.ptr(sigma), _lib.ptr(rgb), _lib.ptr(background),
+                                                              float(final_delta), n, s, _lib.ptr(out), _lib.ptr(depth), _lib.ptr(alpha), _lib.ptr(weights),
+                                                              _lib.stream_of(t)), 'nerf_integrate_forward')
+        ctx.final_delta = float(final_delta)
+        ctx.save_for_backward(t, directions, sigma, rgb, background)
+        ctx.mark_non_differentiable(depth)
+        ctx.set_materialize_grads(False)
+        return out, depth, alpha, weights
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_rgb, d_depth, d_alpha, d_weights):
+        from . import _lib
+        t, directions, sigma, rgb, background = ctx.saved_tensors
+        n, s = t.shape
+        d_rgb, d_alpha, d_weights = (None if g is None else g.contiguous().float() for g in (d_rgb, d_alpha, d_weights))
+        with torch.cuda.device(t.device):
+            d_sigma = torch.empty_like(sigma)
+            d_samples = torch.empty_like(rgb)
+            _lib.check(_lib.load().nrc_nerf_integrate_backward(_lib.ptr(d_rgb), _lib.ptr(d_alpha), _lib.ptr(d_weights), _lib.ptr(t), _lib.ptr(directions),
+                                                               _lib.ptr(sigma), _lib.ptr(rgb), _lib.ptr(background), ctx.final_delta, n, s, _lib.ptr(d_sigma),
+                                                               _lib.ptr(d_samples), _lib.stream_of(t)), 'nerf_integrate_backward')
+        return None, None, d_sigma, d_samples, None, None
+
+
+def composite(t: torch.Tensor, directions: torch.Tensor, sigma: torch.Tensor, rgb: torch.Tensor, background: torch.Tensor | None,
+              final_delta: float = 1.0e10):
+    """`integrate_samples` as one kernel, with a backward kernel behind autograd (csrc/nerf_rays.hip, header group 19) -> rgb (N, 3), depth (N, 1),
+    alpha (N, 1), weights (N, S).  t (N, S), directions (N, 3), sigma (N, S), rgb (N, S, 3), background (3,) or None.  sigma and rgb receive gradients
+    (first order only); depth is marked non-differentiable, as the reference's own comment on its depth expression asks.  Falls back to
+    `integrate_samples` -- torch's bits and torch's autograd -- for CPU tensors, non-f32 input, an unsupported S, or when t, the directions or the
+    background require grad."""
+    tensors = (t, directions, sigma, rgb) + (() if background is None else (background,))
+    first = t
+    eligible = (t.dim() == 2 and t.shape[0] > 0 and all(x.is_cuda and x.device == first.device and x.dtype == torch.float32 for x in tensors)
+                and tuple(sigma.shape) == tuple(t.shape) and tuple(rgb.shape) == (*t.shape, 3) and tuple(directions.shape) == (t.shape[0], 3)
+                and (background is None or background.numel() == 3)
+                and not (torch.is_grad_enabled() and (t.requires_grad or directions.requires_grad or (background is not None and background.requires_grad))))
+    if eligible:
+        from . import _lib
+        eligible = bool(_lib.load().nrc_nerf_rays_supported(int(t.shape[1]), 0))
+    if not eligible:
+        return integrate_samples(t, directions, sigma, rgb, background, final_delta)
+    return _Composite.apply(t.detach().contiguous(), directions.detach().contiguous(), sigma.contiguous(), rgb.contiguous(),
+                            None if background is None else background.detach().contiguous(), final_delta)
+
+
 def render_rays(coarse_nerf: NeRFBlock | None, nerf: NeRFBlock, origin, direction, view_direction, near_plane: float, far_plane: float,
                 background_color, ray_batch_size: int = 8192, n_samples_coarse_nerf: int = 64, n_samples_nerf: int = 192,
-                randomize_samples: bool = False, random_noise_density: float = 0.0, fused: bool = False, fused_train: bool = False) -> dict[str, torch.Tensor]:
+                randomize_samples: bool = False, random_noise_density: float = 0.0, fused: bool = False, fused_train: bool = False,
+                device_rays: bool = False) -> dict[str, torch.Tensor]:
     """NeRFRayRenderingComponent.forward (Renderer.py:29-95): chunked coarse pass -> PDF samples -> sorted union -> fine pass.  `fused`: the two network
     calls go through `fused_forward` (one direction row per ray); with density noise, and wherever `fused_forward` falls back, the torch path runs.
     `fused_train`: they go through `fused_apply` instead -- the training path, differentiable with respect to the blocks' parameters; with density
-    noise the torch path runs."""
+    noise the torch path runs.  `device_rays`: sampling, compositing and the fine pass's resampling + sort go through `sample_coarse`, `composite` and
+    `sample_fine` (one kernel each; the random numbers are drawn in the torch path's shapes and order, so a seed gives the same offsets); composes with
+    `fused` / `fused_train` and with the torch block; each of the three falls back to the torch expressions below on its own conditions."""
     def query(block, pos, vd):
         if fused_train and not random_noise_density > 0.0:
             return fused_apply(block, pos.reshape(-1, 3), vd, dir_group=pos.shape[1])
@@ -339,6 +483,19 @@ def render_rays(coarse_nerf: NeRFBlock | None, nerf: NeRFBlock, origin, directio
     for a in range(0, origin.shape[0], ray_batch_size):
         o, d, vd = origin[a:a + ray_batch_size], direction[a:a + ray_batch_size], view_direction[a:a + ray_batch_size]
         n = o.shape[0]
+        if device_rays:
+            if use_coarse:
+                t_c, pos = sample_coarse(o, d, n_samples_coarse_nerf, near_plane, far_plane, randomize_samples)
+                dens, col = query(coarse_nerf, pos.view(n, -1, 3), vd)
+                rgb_c, depth_c, alpha_c, w_c = composite(t_c, d, dens.reshape(n, -1), col.reshape(n, -1, 3), bg)
+                t, pos = sample_fine(t_c, w_c, n_samples_nerf, randomize_samples, o, d)
+                chunks['rgb_coarse'].append(rgb_c); chunks['depth_coarse'].append(depth_c); chunks['alpha_coarse'].append(alpha_c)
+            else:
+                t, pos = sample_coarse(o, d, n_samples_nerf, near_plane, far_plane, randomize_samples)
+            dens, col = query(nerf, pos.view(n, -1, 3), vd)
+            rgb, depth, alpha, _ = composite(t, d, dens.reshape(n, -1), col.reshape(n, -1, 3), bg)
+            chunks['rgb'].append(rgb); chunks['depth'].append(depth); chunks['alpha'].append(alpha)
+            continue
         if use_coarse:
             t_c = generate_samples(n, n_samples_coarse_nerf, near_plane, far_plane, randomize_samples, o.dtype, o.device)
             pos = o[:, None, :] + d[:, None, :] * t_c[:, :, None]

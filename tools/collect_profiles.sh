@@ -22,6 +22,8 @@ prof() {
 # trace and counter runs (tools/bench_nerf_fused.py); tools/make_profile_summary.py ROUND nerf_net.hip carries every other kernel's counters over.
 # MODE=nerf_train: the trace and counter runs of the block's training path alone (tools/bench_nerf_train.py; no bench command) -- a call of its own after
 # MODE=nerf when csrc/nerf_grad.hip or the shared csrc/nerf_net.h changed; then tools/make_profile_summary.py ROUND nerf_net.hip nerf_net.h nerf_grad.hip.
+# MODE=nerf_rays: a change confined to csrc/nerf_rays.hip -- the bench command (all durations; no bench leg runs the ray stages) and one trace of
+# tools/bench_nerf_rays.py; then tools/make_profile_summary.py ROUND nerf_rays.hip (every other kernel's counters carried over).
 MODE=${1:-all}
 # the full bench command (bench.py --full --steps 20 --warmup 5, every leg): the per-kernel averages of the InstantNGP kernels must agree with the bench line
 [ "$MODE" != nerf_train ] && prof 900 $O/bench_stats.log --kernel-trace --stats --output-format csv -d $O/bench_stats -- python3 $R/bench.py --full --steps 20 --warmup 5
@@ -41,7 +43,10 @@ for set in "GRBM_GUI_ACTIVE SQ_WAVES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_VA
   prof 400 $O/pmcnt_$tag.log --pmc $set --kernel-trace --kernel-include-regex "k_nerf_(forward|dgrad|wgrad|wreduce)" --output-format csv -d $O/pmcnt_$tag -- python3 $R/tools/bench_nerf_train.py 3
 done
 fi
-if [ "$MODE" = nerf ] || [ "$MODE" = nerf_train ]; then
+if [ "$MODE" = nerf_rays ]; then
+prof 300 $O/nerf_rays_stats.log --kernel-trace --stats --output-format csv -d $O/nerf_rays_stats -- python3 $R/tools/bench_nerf_rays.py 7
+fi
+if [ "$MODE" = nerf ] || [ "$MODE" = nerf_train ] || [ "$MODE" = nerf_rays ]; then
 find $O -name "*.db" -delete; find $O -name "*_agent_info.csv" -delete; find $O -path "*_stats/*" -name "*kernel_trace.csv" -delete; du -sh $O; [ -f $O/bench_stats.log ] && tail -5 $O/bench_stats.log
 exit 0
 fi
