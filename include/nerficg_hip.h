@@ -49,8 +49,9 @@ enum {
  * 16 = group 17 (nrc_nerf_*: the vanilla NeRF block's inference forward as one kernel) is new, every earlier signature is unchanged;
  * 17 = group 18 (the vanilla NeRF block's training forward and backward) is new, every earlier signature is unchanged;
  * 18 = group 19 (nrc_nerf_rays_* / nrc_nerf_sample_* / nrc_nerf_integrate_*: NeRF sampling, compositing and resampling) is new, every earlier signature is
- * unchanged. */
-#define NRC_ABI_VERSION 18
+ * unchanged;
+ * 19 = group 20 (the vanilla NeRF path's gradients to sample positions, viewing directions and rays) is new, every earlier signature is unchanged. */
+#define NRC_ABI_VERSION 19
 /* library identification; also used by the loader's symbol check */
 int nrc_abi_version(void);
 const char* nrc_build_info(void);
@@ -1080,7 +1081,7 @@ int nrc_nerf_block_forward(const float* positions, const float* directions, int6
 /* =====================================================================================================
  * Group 18 -- the vanilla NeRF block, TRAINING: a forward that keeps what the backward needs, and the backward through the whole block
  *            (csrc/nerf_net.hip: k_nerf_forward<W, 2>; csrc/nerf_grad.hip).  Replaces autograd through NeRFBlock.forward (Model.py:59-83) for the block's
- *            PARAMETERS; positions and directions receive no gradient.  cfg as in group 17.  Supported: everything group 17 supports with
+ *            PARAMETERS; positions and directions receive theirs from group 20.  cfg as in group 17.  Supported: everything group 17 supports with
  *            n_color_layers = 1 (nrc_nerf_train_supported; a deeper colour head: NRC_ERR_UNSUPPORTED, the caller trains on torch).
  *            Arithmetic contract (fp16 MFMA operands, f32 accumulation, one power-of-two scale, fixed summation order): top of csrc/nerf_grad.hip.
  *
@@ -1153,7 +1154,7 @@ int nrc_nerf_grad_stage(const void* workspace, int32_t width, int32_t n_layers, 
  *            rgb (N, 3), depth (N) = sum w t / alpha where the leftover is < 1, else 0; alpha (N) = 1 - leftover; weights (N, S).  No early-out.
  *   nrc_nerf_integrate_backward: upstream d_rgb (N, 3), d_alpha (N), d_weights (N, S), each may be NULL (= zero); the forward's inputs again.
  *            d_sigma (N S), d_rgb_samples (N S, 3).  The transmittance is recomputed; one reverse scan, no division by 1 - a.  No gradient to t, to the
- *            directions or through depth.
+ *            directions (group 20: nrc_nerf_integrate_backward_dirs) or through depth.
  *   nrc_nerf_sample_fine: t_coarse, weights (N, S_coarse); u with a row stride in ELEMENTS: 0 = one row of S_fine values shared by all rays, >= S_fine =
  *            one row per ray (anything between: NRC_ERR_INVALID); origins, directions (N, 3).  t (N, S_coarse + S_fine): the ascending sort of the multiset
  *            t_coarse u t_fine (FINITE inputs required); positions (N (S_coarse + S_fine), 3).  Optional, for tests (NULL = not written): cdf
@@ -1171,6 +1172,50 @@ int nrc_nerf_integrate_backward(const float* d_rgb, const float* d_alpha, const 
                                 float* d_rgb_samples, nrc_stream_t stream);
 int nrc_nerf_sample_fine(const float* t_coarse, const float* weights, const float* u, int64_t u_stride, const float* origins, const float* directions,
                          int64_t N, int32_t S_coarse, int32_t S_fine, float* t, float* positions, float* cdf, float* t_fine, nrc_stream_t stream);
+
+/* =====================================================================================================
+ * Group 20 -- the vanilla NeRF path's gradients to its INPUTS: sample positions and viewing directions through the block (csrc/nerf_input_grad.hip),
+ *            ray origins and directions through o + d t and through the segment lengths of the compositor (csrc/nerf_rays.hip).  Opt-in
+ *            (nerf.fused_apply / sample_coarse / sample_fine / composite / render_rays with input_grad=True); no call of groups 17 - 19 changes.
+ *            cfg as in group 17; supported: whatever nrc_nerf_train_supported accepts.  The arithmetic contract (fp16 operands and one f32 accumulator for
+ *            the encoded-input gradients, the f32 encoding backward with the forward's own sin / cos, the summation orders): top of
+ *            csrc/nerf_input_grad.hip and csrc/nerf_rays.hip; restated in tests/nerf_input_grad_ref.py.
+ *
+ *   nrc_nerf_packed_input_bytes / nrc_nerf_pack_weights_input: a third weight stream, the SAME fp16 values as the two other blobs (round-to-nearest-even,
+ *            clamped at +-65504), transposed with the encoded features as the m-tile rows in natural order: all of W_0, W_k[:, W : W + n_pos] for every
+ *            skip bit k (ascending), W_colour[:, W : W + n_dir].  params as nrc_nerf_pack_weights.  One kernel, no host sync, capturable.
+ *   nrc_nerf_block_input_grad: to be called after nrc_nerf_block_backward of the same M rows, with the workspace as that call left it, the same positions,
+ *            directions and dir_group as the forward and the same grad_scale as the backward (0 = the automatic scale, read from the workspace header on
+ *            the device).  d_positions (M, 3) f32, d_directions (ceil(M / dir_group), 3) f32: UNSCALED gradients, every element overwritten.  A group's
+ *            d_directions is the sum of its rows' direction gradients in a fixed order (the last group may be partial); with dir_group > 1 the per-row
+ *            values pass through the workspace's weight-gradient partial sums, which the backward has consumed (nothing else of the workspace is
+ *            written: nrc_nerf_grad_stage / nrc_nerf_saved_stage read the same values afterwards), and a second small launch reduces them.  A row's
+ *            d_positions and, with dir_group = 1, its d_directions depend on that row and the weights only; two calls give the same bits; no
+ *            floating-point atomics; no host synchronisation; capturable.  Optional, for tests (NULL = not written): d_enc_pos (M, n_pos) and d_enc_dir
+ *            (M, n_dir) f32, the gradients with respect to the encoded inputs, still scaled by the gradient scale.
+ *            M == 0: NRC_OK without a launch.  M < 0, dir_group < 1, a grad_scale nrc_nerf_block_backward refuses, a null required pointer, a blob or
+ *            workspace that is not 16-byte aligned, any other pointer that is not 4-byte aligned: NRC_ERR_INVALID before any launch.
+ *   nrc_nerf_positions_backward: the backward of positions = o + d t.  d_positions (N S, 3), t (N, S) -> d_origins (N, 3) = sum_s g_s, d_directions (N, 3) =
+ *            sum_s t_s g_s.  One wave per ray, fixed order, no atomics.  Validation as in group 19.
+ *   nrc_nerf_integrate_backward_dirs: nrc_nerf_integrate_backward plus d_directions (N, 3), the gradient through the segment lengths (t[i+1] - t[i]) |d|:
+ *            (d / |d|) sum_i q_i sigma_i Delta_i with q_i the factor whose product with len_i is d_sigma_i and the last Delta = final_delta; 0 where
+ *            |d| = 0; finite for finite inputs with final_delta = 1e10.  d_sigma and d_rgb_samples are bit-identical to nrc_nerf_integrate_backward.  t
+ *            receives no gradient and depth stays non-differentiable.  Validation as in group 19; d_directions is required.
+ *   Stage-timer names: k_nerf_pack_i, k_nerf_input_grad, k_nerf_dir_reduce, k_nerf_positions_bw, k_nerf_integrate_bw_dirs.
+ * ===================================================================================================== */
+int64_t nrc_nerf_packed_input_bytes(int32_t width, int32_t n_layers, int32_t n_color_layers, int32_t n_frequencies_position, int32_t n_frequencies_direction,
+                                    int32_t append_input, int32_t skip_mask);
+int nrc_nerf_pack_weights_input(const float* const* params, int32_t n_params, int32_t width, int32_t n_layers, int32_t n_color_layers,
+                                int32_t n_frequencies_position, int32_t n_frequencies_direction, int32_t append_input, int32_t skip_mask, void* blob,
+                                nrc_stream_t stream);
+int nrc_nerf_block_input_grad(const float* positions, const float* directions, int64_t dir_group, int64_t M, const void* blob_input, int32_t width,
+                              int32_t n_layers, int32_t n_color_layers, int32_t n_frequencies_position, int32_t n_frequencies_direction, int32_t append_input,
+                              int32_t skip_mask, void* workspace, float grad_scale, float* d_positions, float* d_directions, float* d_enc_pos, float* d_enc_dir,
+                              nrc_stream_t stream);
+int nrc_nerf_positions_backward(const float* d_positions, const float* t, int64_t N, int32_t S, float* d_origins, float* d_directions, nrc_stream_t stream);
+int nrc_nerf_integrate_backward_dirs(const float* d_rgb, const float* d_alpha, const float* d_weights, const float* t, const float* directions,
+                                     const float* sigma, const float* rgb_samples, const float* background, float final_delta, int64_t N, int32_t S,
+                                     float* d_sigma, float* d_rgb_samples, float* d_directions, nrc_stream_t stream);
 
 #ifdef __cplusplus
 }

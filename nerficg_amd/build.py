@@ -50,6 +50,9 @@ PER_FILE_FLAGS = {
     # no FMA contraction: sampling and resampling are compared bit for bit with the numpy restatement of their f32 sequence (tests/nerf_rays_ref.py), and the
     # compositing budgets count that sequence rounding by rounding; the kernels stream a few dozen bytes per sample, a fused multiply-add would buy nothing
     'nerf_rays.hip': ['-ffp-contract=off'],
+    # the input gradient of the same block: the same matrix pipeline (no SLP vectoriser, as for nerf_net.hip); its f32 encoding backward is written in
+    # explicit single-rounding operations, so the contraction setting has nothing to decide
+    'nerf_input_grad.hip': ['-fno-slp-vectorize'],
 }
 
 

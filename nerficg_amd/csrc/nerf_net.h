@@ -76,6 +76,23 @@ __device__ __forceinline__ _Float16 to_h_sat(float v) {
     return h < -lim ? -lim : h;
 }
 
+// shared by the forward's encoding and its derivative (nerf_input_grad.hip): sin and cos of an f32 argument, |error| <= 2^-22 for |a| <= 4096 (the contract at the top of nerf_net.hip; tests/nerf_mlp_ref.py restates the sequence)
+__device__ __forceinline__ void nerf_sincos(float a, float& sn, float& cs) {
+    const float n = rintf(__fmul_rn(a, 0.636619772f));
+    float r = fmaf(-n, 1.5703125f, a);
+    r = fmaf(-n, 4.837512969970703125e-4f, r);
+    r = fmaf(-n, 7.54978995489188216e-8f, r);
+    const float z = __fmul_rn(r, r);
+    const float ps = fmaf(fmaf(-1.9515295891e-4f, z, 8.3321608736e-3f), z, -1.6666654611e-1f);
+    const float s = fmaf(__fmul_rn(ps, z), r, r);
+    const float pc = fmaf(fmaf(2.443315711809948e-5f, z, -1.388731625493765e-3f), z, 4.166664568298827e-2f);
+    const float c = fmaf(pc, __fmul_rn(z, z), fmaf(-0.5f, z, 1.0f));
+    const int q = (int)n & 3;
+    const float s1 = (q & 1) ? c : s, c1 = (q & 1) ? s : c;
+    sn = (q & 2) ? -s1 : s1;
+    cs = ((q + 1) & 2) ? -c1 : c1;
+}
+
 struct Stream {               // the weight stream of one workgroup: which part comes next, which LDS buffer holds its first slab
     const uint4* blob;
     uint4* lds;

@@ -8,7 +8,7 @@
 //   * the next operand is  sat(relu(fp16(z))) : conversion FIRST (RNE, may give inf), THEN ReLU, THEN saturation to +-65504 -- the last two as
 //     packed fp16 max / min.  The feature layer has no ReLU: sat(fp16(z)).  Since rounding is monotone and keeps 0 this equals fp16(clamp(relu(z))).
 //   * sigma = relu(z) and rgb = 1 / (1 + expf(-z)) leave the f32 accumulator directly (accurate expf and division: no fast-math in this build).
-//   * encodings: the argument a = x * 2^k is exact in f32 (a multiplication by a power of two).  sin / cos: nerf_sincos below -- n = rint(a 2/pi),
+//   * encodings: the argument a = x * 2^k is exact in f32 (a multiplication by a power of two).  sin / cos: nerf_sincos (nerf_net.h) -- n = rint(a 2/pi),
 //     r = a - n pi/2 in three fused multiply-adds with pi/2 = C1 + C2 + C3 (C1 8 bits, C2 11 bits: n C1 and n C2 are exact for |n| < 2^12, the first
 //     step is exact, the other two round once each at <= 2^-25), then the degree-7 / degree-8 minimax polynomials of Cephes sinf / cosf on
 //     [-pi/4, pi/4] and the quadrant by n & 3.  |f32 value - f64 function| <= NRC_NERF_E_ENC = 2^-22 (2.4e-7) for |x| <= 8, k <= 9 (|a| <= 4096):
@@ -95,23 +95,6 @@ __device__ __forceinline__ void load_bias(f16v (&acc)[NMT], const float* bias, i
             acc[mt][4 * q] = v.x; acc[mt][4 * q + 1] = v.y; acc[mt][4 * q + 2] = v.z; acc[mt][4 * q + 3] = v.w;
         }
     }
-}
-
-// sin and cos of an f32 argument, |error| <= 2^-22 for |a| <= 4096 (the contract at the top of the file; tests/nerf_mlp_ref.py restates the sequence)
-__device__ __forceinline__ void nerf_sincos(float a, float& sn, float& cs) {
-    const float n = rintf(__fmul_rn(a, 0.636619772f));
-    float r = fmaf(-n, 1.5703125f, a);
-    r = fmaf(-n, 4.837512969970703125e-4f, r);
-    r = fmaf(-n, 7.54978995489188216e-8f, r);
-    const float z = __fmul_rn(r, r);
-    const float ps = fmaf(fmaf(-1.9515295891e-4f, z, 8.3321608736e-3f), z, -1.6666654611e-1f);
-    const float s = fmaf(__fmul_rn(ps, z), r, r);
-    const float pc = fmaf(fmaf(2.443315711809948e-5f, z, -1.388731625493765e-3f), z, 4.166664568298827e-2f);
-    const float c = fmaf(pc, __fmul_rn(z, z), fmaf(-0.5f, z, 1.0f));
-    const int q = (int)n & 3;
-    const float s1 = (q & 1) ? c : s, c1 = (q & 1) ? s : c;
-    sn = (q & 2) ? -s1 : s1;
-    cs = ((q + 1) & 2) ? -c1 : c1;
 }
 
 // frequency encoding of (x0, x1, x2) as NKS NATURAL-order fragments: element j of lane half hh of k-step s = feature 16 s + 8 hh + j of

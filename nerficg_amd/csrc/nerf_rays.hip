@@ -22,6 +22,13 @@
 //                   d_sigma_i = len_i ((gw_i (T_i m_i) - sum_{j>i} gw_j w_j) - T_end B);  d_rgb_samples_ic = w_i g_c.  T is recomputed as in the forward.  The
 //                   suffix sum: lane chunk totals in ascending i, exclusive reverse Hillis-Steele scan over the lanes, then descending inside the chunk.
 //                   Nothing divides by 1 - a: finite on saturated rays and with final_delta = 1e10.
+//   backward_dirs   the same kernel with one more output, the gradient through |d| in len_i (group 20).  q_i = (gw_i (T_i m_i) - sum_{j>i} gw_j w_j) - T_end B is the
+//                   factor whose product with len_i is d_sigma_i;  p_i = q_i (sigma_i Delta_i), Delta_i = t[i+1] - t[i], the last one final_delta;  P = sum_i p_i:
+//                   lane-strided partial sums in ascending i, then the 6-step xor butterfly;  d_directions_c = (d_c / norm) P, 0 where norm = 0.  d_sigma and
+//                   d_rgb_samples: the operations above, unchanged.  Where m_last = 0 (sigma_last final_delta large) q_last is 0 exactly; where sigma_last = 0 the
+//                   product sigma Delta is: finite with final_delta = 1e10.  t receives no gradient, depth stays non-differentiable.
+//   positions_bw    the backward of position = o + d t (group 20): d_o_c = sum_s g_sc, d_d_c = sum_s t_s g_sc (one rounded product each), both as lane-strided
+//                   partial sums in ascending s starting at 0, then the 6-step xor butterfly.
 //   sample_fine     knot_k = (b[k+1] + b[k]) 0.5, k < Sc-1;  mass_j = w[j+1] + 1e-5f, j < Sc-2;  total = the lanes' chunk sums (ascending j, Cm = ceil((Sc-2)/64)
 //                   masses per lane) through a 6-step xor butterfly;  pdf_j = mass_j / total;  cdf[0] = 0, cdf[1+j] = P_l + r_j with r_j the running sum of
 //                   lane l's chunk (ascending) and P_0 = 0, P_{l+1} = P_l + (lane l's chunk total), accumulated lane after lane: the chunk's last value IS
@@ -147,10 +154,12 @@ __global__ void __launch_bounds__(64 * RPG) k_nerf_integrate_fw(const float* __r
     }
 }
 
+template <bool DIRS>
 __global__ void __launch_bounds__(64 * RPG) k_nerf_integrate_bw(const float* __restrict__ d_rgb, const float* __restrict__ d_alpha, const float* __restrict__ d_weights,
                                                                 const float* __restrict__ t, const float* __restrict__ directions, const float* __restrict__ sigma,
                                                                 const float* __restrict__ rgb_in, const float* __restrict__ background, float final_delta,
-                                                                int64_t N, int S, float* __restrict__ d_sigma, float* __restrict__ d_rgb_samples) {
+                                                                int64_t N, int S, float* __restrict__ d_sigma, float* __restrict__ d_rgb_samples,
+                                                                float* __restrict__ d_directions) {
     extern __shared__ float smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t ray = (int64_t)blockIdx.x * RPG + wave;
@@ -189,13 +198,41 @@ __global__ void __launch_bounds__(64 * RPG) k_nerf_integrate_bw(const float* __r
     }
     __syncthreads();
     const float TB = T_end * B;
-    if (valid)
+    if (valid) {
+        float P = 0.f;
         for (int i = lane; i < S; i += 64) {
             const float* c = rgb_in + 3 * (r * S + i);
             const float gw = ((g0 * c[0] + g1 * c[1]) + g2 * c[2]) + (d_weights ? d_weights[r * S + i] : 0.f);
             const float len = segment_len(tr, i, S, final_delta, norm);
-            d_sigma[r * S + i] = len * ((gw * (T[i] * (1.f - a_s[i])) - g[i]) - TB);
+            const float q = (gw * (T[i] * (1.f - a_s[i])) - g[i]) - TB;
+            d_sigma[r * S + i] = len * q;
+            if constexpr (DIRS) P += q * (sigma[r * S + i] * (i + 1 < S ? tr[i + 1] - tr[i] : final_delta));
         }
+        if constexpr (DIRS) {
+            P = nrc_group_sum<64>(P);
+            if (lane < 3) d_directions[3 * r + lane] = norm > 0.f ? (directions[3 * r + lane] / norm) * P : 0.f;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(64 * RPG) k_nerf_positions_bw(const float* __restrict__ d_positions, const float* __restrict__ t, int64_t N, int S,
+                                                                float* __restrict__ d_origins, float* __restrict__ d_directions) {
+    const int lane = threadIdx.x & 63;
+    const int64_t ray = (int64_t)blockIdx.x * RPG + (threadIdx.x >> 6);
+    if (ray >= N) return;
+    float o0 = 0.f, o1 = 0.f, o2 = 0.f, e0 = 0.f, e1 = 0.f, e2 = 0.f;
+    for (int i = lane; i < S; i += 64) {
+        const float* g = d_positions + 3 * (ray * S + i);
+        const float ti = t[ray * S + i];
+        o0 += g[0]; o1 += g[1]; o2 += g[2];
+        e0 += ti * g[0]; e1 += ti * g[1]; e2 += ti * g[2];
+    }
+    o0 = nrc_group_sum<64>(o0); o1 = nrc_group_sum<64>(o1); o2 = nrc_group_sum<64>(o2);
+    e0 = nrc_group_sum<64>(e0); e1 = nrc_group_sum<64>(e1); e2 = nrc_group_sum<64>(e2);
+    if (lane == 0) {
+        d_origins[3 * ray] = o0; d_origins[3 * ray + 1] = o1; d_origins[3 * ray + 2] = o2;
+        d_directions[3 * ray] = e0; d_directions[3 * ray + 1] = e1; d_directions[3 * ray + 2] = e2;
+    }
 }
 
 __global__ void __launch_bounds__(64 * RPG) k_nerf_sample_fine(const float* __restrict__ t_coarse, const float* __restrict__ weights, const float* __restrict__ u,
@@ -346,8 +383,8 @@ int nrc_nerf_integrate_backward(const float* d_rgb, const float* d_alpha, const 
     if (blocks > 0x7fffffff) return NRC_ERR_INVALID;
     hipStream_t s = (hipStream_t)stream;
     NRC_STAGE(s, nullptr);
-    hipLaunchKernelGGL(k_nerf_integrate_bw, dim3((unsigned)blocks), dim3(64 * RPG), (size_t)RPG * 3 * S * sizeof(float), s, d_rgb, d_alpha, d_weights, t,
-                       directions, sigma, rgb_samples, background, final_delta, N, (int)S, d_sigma, d_rgb_samples);
+    hipLaunchKernelGGL(k_nerf_integrate_bw<false>, dim3((unsigned)blocks), dim3(64 * RPG), (size_t)RPG * 3 * S * sizeof(float), s, d_rgb, d_alpha, d_weights, t,
+                       directions, sigma, rgb_samples, background, final_delta, N, (int)S, d_sigma, d_rgb_samples, (float*)nullptr);
     NRC_LAUNCH_CHECK();
     NRC_STAGE(s, "k_nerf_integrate_bw");
     return NRC_OK;
@@ -372,6 +409,44 @@ int nrc_nerf_sample_fine(const float* t_coarse, const float* weights, const floa
                        (int)S_fine, P, t, positions, cdf, t_fine);
     NRC_LAUNCH_CHECK();
     NRC_STAGE(s, "k_nerf_sample_fine");
+    return NRC_OK;
+}
+
+int nrc_nerf_integrate_backward_dirs(const float* d_rgb, const float* d_alpha, const float* d_weights, const float* t, const float* directions,
+                                     const float* sigma, const float* rgb_samples, const float* background, float final_delta, int64_t N, int32_t S,
+                                     float* d_sigma, float* d_rgb_samples, float* d_directions, nrc_stream_t stream) {
+    NRC_ENTER();
+    if (!s_ok(S)) return NRC_ERR_UNSUPPORTED;
+    if (N < 0) return NRC_ERR_INVALID;
+    if (N == 0) return NRC_OK;
+    if (!t || !directions || !sigma || !rgb_samples || !d_sigma || !d_rgb_samples || !d_directions || misaligned(d_rgb) || misaligned(d_alpha) ||
+        misaligned(d_weights) || misaligned(t) || misaligned(directions) || misaligned(sigma) || misaligned(rgb_samples) || misaligned(background) ||
+        misaligned(d_sigma) || misaligned(d_rgb_samples) || misaligned(d_directions)) return NRC_ERR_INVALID;
+    const int64_t blocks = nrc_cdiv(N, RPG);
+    if (blocks > 0x7fffffff) return NRC_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    NRC_STAGE(s, nullptr);
+    hipLaunchKernelGGL(k_nerf_integrate_bw<true>, dim3((unsigned)blocks), dim3(64 * RPG), (size_t)RPG * 3 * S * sizeof(float), s, d_rgb, d_alpha, d_weights, t,
+                       directions, sigma, rgb_samples, background, final_delta, N, (int)S, d_sigma, d_rgb_samples, d_directions);
+    NRC_LAUNCH_CHECK();
+    NRC_STAGE(s, "k_nerf_integrate_bw_dirs");
+    return NRC_OK;
+}
+
+int nrc_nerf_positions_backward(const float* d_positions, const float* t, int64_t N, int32_t S, float* d_origins, float* d_directions, nrc_stream_t stream) {
+    NRC_ENTER();
+    if (!s_ok(S)) return NRC_ERR_UNSUPPORTED;
+    if (N < 0) return NRC_ERR_INVALID;
+    if (N == 0) return NRC_OK;
+    if (!d_positions || !t || !d_origins || !d_directions || misaligned(d_positions) || misaligned(t) || misaligned(d_origins) || misaligned(d_directions))
+        return NRC_ERR_INVALID;
+    const int64_t blocks = nrc_cdiv(N, RPG);
+    if (blocks > 0x7fffffff) return NRC_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    NRC_STAGE(s, nullptr);
+    hipLaunchKernelGGL(k_nerf_positions_bw, dim3((unsigned)blocks), dim3(64 * RPG), 0, s, d_positions, t, N, (int)S, d_origins, d_directions);
+    NRC_LAUNCH_CHECK();
+    NRC_STAGE(s, "k_nerf_positions_bw");
     return NRC_OK;
 }
 

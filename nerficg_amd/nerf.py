@@ -5,7 +5,10 @@ hierarchical (coarse -> fine) ray renderer.  `fused_forward` / `render_rays(fuse
 path: a forward that keeps every stage's fp16 operand and a backward through the whole block (csrc/nerf_grad.hip, header group 18) behind an autograd
 function that returns gradients for the block's parameters; sampling, sorting and compositing stay torch autograd.  `sample_coarse`, `composite`,
 `sample_fine` / `render_rays(device_rays=True)` are the opt-in device path for what surrounds the block: stratified sampling, compositing with its
-backward and the fine pass's resampling + sorted union as one HIP kernel each (csrc/nerf_rays.hip, header group 19).  Everything else stays on torch.
+backward and the fine pass's resampling + sorted union as one HIP kernel each (csrc/nerf_rays.hip, header group 19).  `input_grad=True` on any of them (and on
+`render_rays`) is the opt-in for gradients to the INPUTS on that device path -- sample positions and viewing directions through the block
+(csrc/nerf_input_grad.hip), ray origins and directions through `o + d t` and the compositor's segment lengths (header group 20): pose refinement and
+tracking against a frozen model without leaving the fused path.  Everything else stays on torch.
 
 Reference: src/Methods/NeRF/utils.py:12-136, src/Methods/NeRF/Model.py:10-83, src/Methods/NeRF/Renderer.py:20-95.
 Pinned against golden vectors generated from the reference (tests/test_host_golden.py).  `integrate_samples` is also the
@@ -181,8 +184,29 @@ def _train_blobs(block: NeRFBlock, cfg, device):
     return blob, cache['blob_t']
 
 
+def _input_blob(block: NeRFBlock, cfg, device):
+    """The weight stream of the input gradient (header group 20): the same fp16 values again, cached under the key of the forward blob."""
+    import ctypes
+    from . import _lib
+    _packed_blob(block, cfg, device)
+    cache = block._fused_cache
+    if cache.get('key_i') != cache['key']:
+        lib = _lib.load()
+        n_bytes = lib.nrc_nerf_packed_input_bytes(*cfg)
+        if cache.get('blob_i') is None or cache['blob_i'].numel() != n_bytes or cache['blob_i'].device != device:
+            cache['blob_i'] = torch.empty(n_bytes, dtype=torch.uint8, device=device)
+        params = [t for lin in _block_linears(block) for t in (lin.weight, lin.bias)]
+        ptrs = (ctypes.c_void_p * len(params))(*[t.data_ptr() for t in params])
+        _lib.check(lib.nrc_nerf_pack_weights_input(ctypes.cast(ptrs, ctypes.c_void_p), len(params), *cfg, _lib.ptr(cache['blob_i']),
+                                                   _lib.stream_of(cache['blob_i'])), 'nerf_pack_weights_input')
+        cache['key_i'] = cache['key']
+        cache['packs_i'] = cache.get('packs_i', 0) + 1
+    return cache['blob_i']
+
+
 class _FusedBlock(torch.autograd.Function):
-    """Training forward + backward of one block (header group 18).  Gradients for the parameters only."""
+    """Training forward + backward of one block (header group 18).  Gradients for the parameters and -- when the positions or the directions require grad,
+    which `fused_apply` lets through only with `input_grad=True` -- for those two (header group 20)."""
 
     @staticmethod
     def forward(ctx, block, cfg, positions, directions, dir_group, grad_scale, *params):
@@ -200,8 +224,12 @@ class _FusedBlock(torch.autograd.Function):
             rgb = torch.empty(m, 3, dtype=torch.float32, device=device)
             _lib.check(lib.nrc_nerf_block_forward_train(_lib.ptr(positions), _lib.ptr(directions), int(dir_group), m, _lib.ptr(blob), *cfg, _lib.ptr(sigma),
                                                         _lib.ptr(rgb), _lib.ptr(ws), _lib.stream_of(positions)), 'nerf_block_forward_train')
-        ctx.block, ctx.cfg, ctx.m, ctx.grad_scale, ctx.ws, ctx.blob_t = block, cfg, m, grad_scale, ws, blob_t
-        ctx.save_for_backward(sigma, rgb)
+            ctx.blob_i = _input_blob(block, cfg, device) if (ctx.needs_input_grad[2] or ctx.needs_input_grad[3]) else None
+        ctx.block, ctx.cfg, ctx.m, ctx.grad_scale, ctx.ws, ctx.blob_t, ctx.dir_group = block, cfg, m, grad_scale, ws, blob_t, int(dir_group)
+        if ctx.blob_i is None:
+            ctx.save_for_backward(sigma, rgb)
+        else:
+            ctx.save_for_backward(sigma, rgb, positions, directions)
         return sigma, rgb
 
     @staticmethod
@@ -209,8 +237,9 @@ class _FusedBlock(torch.autograd.Function):
     def backward(ctx, d_sigma, d_rgb):
         from . import _lib
         lib = _lib.load()
-        sigma, rgb = ctx.saved_tensors
+        sigma, rgb = ctx.saved_tensors[:2]
         block, cfg = ctx.block, ctx.cfg
+        d_positions = d_directions = None
         d_sigma, d_rgb = d_sigma.contiguous().float(), d_rgb.contiguous().float()
         with torch.cuda.device(sigma.device):
             grad = torch.empty(lib.nrc_nerf_grad_params_floats(*cfg), dtype=torch.float32, device=sigma.device)
@@ -218,6 +247,12 @@ class _FusedBlock(torch.autograd.Function):
             _lib.check(lib.nrc_nerf_block_backward(_lib.ptr(d_sigma), _lib.ptr(d_rgb), _lib.ptr(sigma), _lib.ptr(rgb), ctx.m, _lib.ptr(ctx.blob_t), *cfg,
                                                    _lib.ptr(ctx.ws), float(ctx.grad_scale or 0.0), _lib.ptr(grad), _lib.ptr(stats), _lib.stream_of(sigma)),
                        'nerf_block_backward')
+            if ctx.blob_i is not None:      # before the workspace returns to its pool: the gradient stages are still in it
+                positions, directions = ctx.saved_tensors[2:]
+                d_positions, d_directions = torch.empty_like(positions), torch.empty_like(directions)
+                _lib.check(lib.nrc_nerf_block_input_grad(_lib.ptr(positions), _lib.ptr(directions), ctx.dir_group, ctx.m, _lib.ptr(ctx.blob_i), *cfg,
+                                                         _lib.ptr(ctx.ws), float(ctx.grad_scale or 0.0), _lib.ptr(d_positions), _lib.ptr(d_directions), None,
+                                                         None, _lib.stream_of(sigma)), 'nerf_block_input_grad')
         cache = block._fused_cache
         cache['stats'], cache['last_workspace'] = stats, ctx.ws
         cache.setdefault('workspaces', []).append(ctx.ws)
@@ -228,23 +263,31 @@ class _FusedBlock(torch.autograd.Function):
                 n = t.numel()
                 out.append(grad[at:at + n].view(t.shape) if ctx.needs_input_grad[6 + 2 * k + j] else None)
                 at += n
-        return (None,) * 6 + tuple(out)
+        return (None, None, d_positions if ctx.needs_input_grad[2] else None, d_directions if ctx.needs_input_grad[3] else None, None, None) + tuple(out)
 
 
-def fused_apply(block: NeRFBlock, positions: torch.Tensor, directions: torch.Tensor, dir_group: int = 1, grad_scale: float | None = None):
+def fused_apply(block: NeRFBlock, positions: torch.Tensor, directions: torch.Tensor, dir_group: int = 1, grad_scale: float | None = None,
+                input_grad: bool = False):
     """`NeRFBlock.forward` without noise for TRAINING -> (sigma (M, 1), rgb (M, 3)), f32, differentiable with respect to the block's parameters: the
     forward keeps every stage's fp16 operand, the backward runs the whole block on the matrix units (csrc/nerf_grad.hip) and autograd accumulates
     its result into `.grad` as usual.  `grad_scale`: a positive power of two for the fp16 gradients, None = chosen on the device per call.  Second-order
     gradients are not supported, positions and directions receive none.  Under `torch.no_grad()`, or when no parameter requires grad, this is
     `fused_forward`.  For CPU tensors, a block `nrc_nerf_train_supported` refuses, non-f32 parameters, an empty batch, or positions / directions that
-    require grad it returns `block(positions, expanded directions)` with torch's bits and torch's autograd."""
+    require grad it returns `block(positions, expanded directions)` with torch's bits and torch's autograd.
+
+    `input_grad=True`: positions or directions that require grad no longer disqualify the call -- the backward also runs the input-gradient kernel
+    (csrc/nerf_input_grad.hip, header group 20) and returns their gradients, `directions.grad` summed over the `dir_group` rows that share a row; the
+    parameter gradients keep their bits.  The device path then also runs when no parameter requires grad but an input does (tracking against a frozen
+    model).  `directions` must then hold exactly ceil(M / dir_group) rows."""
     params = [t for lin in _block_linears(block) for t in (lin.weight, lin.bias)]
-    if not torch.is_grad_enabled() or not any(p.requires_grad for p in block.parameters()):
+    inputs_want = bool(input_grad) and (positions.requires_grad or directions.requires_grad)
+    if not torch.is_grad_enabled() or not (any(p.requires_grad for p in block.parameters()) or inputs_want):
         return fused_forward(block, positions, directions, dir_group)
     m = positions.shape[0]
     eligible = (m > 0 and positions.is_cuda and directions.is_cuda and positions.dtype == torch.float32 and directions.dtype == torch.float32
                 and all(p.is_cuda and p.device == positions.device for p in block.parameters())
-                and not (positions.requires_grad or directions.requires_grad))
+                and (bool(input_grad) or not (positions.requires_grad or directions.requires_grad))
+                and not (inputs_want and directions.shape[0] != -(-m // int(dir_group))))
     cfg = fused_config(block) if eligible else None
     if cfg is not None:
         from . import _lib
@@ -328,25 +371,62 @@ def integrate_samples(depth_samples, ray_directions, densities, colors, backgrou
     return rgb, depth, alpha, weights
 
 
-def _rays_eligible(n_coarse: int, n_fine: int, *tensors) -> bool:
-    """The device path of group 19 takes these tensors: all on one GPU, f32, none requiring grad while autograd records, a supported sample count."""
+def _rays_eligible(n_coarse: int, n_fine: int, *tensors, grad_ok=()) -> bool:
+    """The device path of group 19 takes these tensors: all on one GPU, f32, none requiring grad while autograd records (but for those in `grad_ok`, which
+    the caller differentiates itself: group 20), a supported sample count."""
     first = tensors[0]
     if not all(t.is_cuda and t.device == first.device and t.dtype == torch.float32 for t in tensors):
         return False
-    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+    if torch.is_grad_enabled() and any(t.requires_grad and not any(t is g for g in grad_ok) for t in tensors):
         return False
     from . import _lib
     return first.shape[0] > 0 and bool(_lib.load().nrc_nerf_rays_supported(int(n_coarse), int(n_fine)))
 
 
+class _RayPositions(torch.autograd.Function):
+    """positions = o + d t behind a sampling kernel that has already produced them (header group 20): the backward is nrc_nerf_positions_backward.  t is a
+    constant here (the reference detaches the fine depths; the coarse ones do not depend on the ray)."""
+
+    @staticmethod
+    def forward(ctx, origins, directions, t, positions):
+        ctx.save_for_backward(t)
+        ctx.set_materialize_grads(False)
+        return positions.view_as(positions)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_positions):
+        if d_positions is None:
+            return None, None, None, None
+        from . import _lib
+        (t,) = ctx.saved_tensors
+        n, s = t.shape
+        d_positions = d_positions.contiguous().float()
+        with torch.cuda.device(t.device):
+            d_origins = torch.empty(n, 3, dtype=torch.float32, device=t.device)
+            d_directions = torch.empty(n, 3, dtype=torch.float32, device=t.device)
+            _lib.check(_lib.load().nrc_nerf_positions_backward(_lib.ptr(d_positions), _lib.ptr(t), n, s, _lib.ptr(d_origins), _lib.ptr(d_directions),
+                                                               _lib.stream_of(t)), 'nerf_positions_backward')
+        return (d_origins if ctx.needs_input_grad[0] else None, d_directions if ctx.needs_input_grad[1] else None, None, None)
+
+
+def _attach_rays(origins, directions, t, positions, input_grad):
+    """the sampled positions, differentiable with respect to the rays when the caller asked for it and one of them requires grad"""
+    if input_grad and torch.is_grad_enabled() and (origins.requires_grad or directions.requires_grad):
+        return _RayPositions.apply(origins, directions, t, positions)
+    return positions
+
+
 def sample_coarse(origins: torch.Tensor, directions: torch.Tensor, n_samples: int, near_plane: float, far_plane: float, randomize_samples: bool,
-                  u: torch.Tensor | None = None):
+                  u: torch.Tensor | None = None, input_grad: bool = False):
     """Depths of the coarse pass and their positions -> (t (N, S), positions (N S, 3)): `generate_samples` and `o + d t` as one kernel
     (csrc/nerf_rays.hip, header group 19).  With `randomize_samples` the offsets are `u` (N, S), drawn with `torch.rand` exactly as
     `generate_samples` draws them when not given.  Falls back to the torch expressions of `render_rays` -- torch's bits -- for CPU tensors, non-f32
-    input, an unsupported S, or origins / directions that require grad."""
+    input, an unsupported S, or origins / directions that require grad.  `input_grad=True`: origins and directions that require grad keep the device
+    forward and receive `nrc_nerf_positions_backward`'s outputs (header group 20); t carries no gradient."""
     n = origins.shape[0]
-    if not _rays_eligible(n_samples, 0, origins, directions) or (u is not None and not _rays_eligible(n_samples, 0, u)):
+    rays_in = (origins, directions)
+    if not _rays_eligible(n_samples, 0, origins, directions, grad_ok=rays_in if input_grad else ()) or (u is not None and not _rays_eligible(n_samples, 0, u)):
         if u is None:
             t = generate_samples(n, n_samples, near_plane, far_plane, randomize_samples, origins.dtype, origins.device)
         else:
@@ -362,19 +442,23 @@ def sample_coarse(origins: torch.Tensor, directions: torch.Tensor, n_samples: in
         positions = torch.empty(n * n_samples, 3, dtype=torch.float32, device=origins.device)
         _lib.check(_lib.load().nrc_nerf_sample_coarse(_lib.ptr(origins), _lib.ptr(directions), _lib.ptr(t_row), _lib.ptr(u), n, int(n_samples), _lib.ptr(t),
                                                       _lib.ptr(positions), _lib.stream_of(origins)), 'nerf_sample_coarse')
-    return t, positions
+    return t, _attach_rays(*rays_in, t, positions, input_grad)
 
 
 def sample_fine(t_coarse: torch.Tensor, weights: torch.Tensor, n_samples: int, randomize_samples: bool, origins: torch.Tensor, directions: torch.Tensor,
-                u: torch.Tensor | None = None):
+                u: torch.Tensor | None = None, input_grad: bool = False):
     """Depths of the fine pass merged with the coarse ones, and their positions -> (t (N, Sc + Sf) ascending, positions (N (Sc + Sf), 3)):
     `generate_samples_from_pdf`, `sort(cat(t_coarse, t_fine))` and `o + d t` as one kernel (header group 19).  `u`: (N, Sf) per-ray draws or (Sf,) one row
     for all rays; when not given it is drawn (`torch.rand`) or laid out (`torch.linspace(0, 1, Sf)`) exactly as `generate_samples_from_pdf` does.  The
     weights carry no gradient (the reference detaches the fine depths).  Finite inputs are required.  Falls back to the torch expressions of `render_rays`
-    for CPU tensors, non-f32 input, unsupported sample counts, or depths / origins / directions that require grad."""
+    for CPU tensors, non-f32 input, unsupported sample counts, or depths / origins / directions that require grad.  `input_grad=True`: origins and
+    directions that require grad keep the device forward and receive `nrc_nerf_positions_backward`'s outputs (header group 20); t carries no gradient, and
+    depths that require grad still fall back."""
     n, n_coarse = t_coarse.shape
     weights = weights.detach()
-    if not _rays_eligible(n_coarse, n_samples, t_coarse, weights, origins, directions) or (u is not None and not _rays_eligible(n_coarse, n_samples, u)):
+    rays_in = (origins, directions)
+    if (not _rays_eligible(n_coarse, n_samples, t_coarse, weights, origins, directions, grad_ok=rays_in if input_grad else ())
+            or (u is not None and not _rays_eligible(n_coarse, n_samples, u))):
         if u is None:
             t_f = generate_samples_from_pdf(t_coarse, weights, n_samples, randomize_samples)
         else:
@@ -397,11 +481,12 @@ def sample_fine(t_coarse: torch.Tensor, weights: torch.Tensor, n_samples: int, r
         _lib.check(_lib.load().nrc_nerf_sample_fine(_lib.ptr(t_coarse), _lib.ptr(weights), _lib.ptr(u), n_samples if u.dim() == 2 else 0, _lib.ptr(origins),
                                                     _lib.ptr(directions), n, int(n_coarse), int(n_samples), _lib.ptr(t), _lib.ptr(positions), None, None,
                                                     _lib.stream_of(t_coarse)), 'nerf_sample_fine')
-    return t, positions
+    return t, _attach_rays(*rays_in, t, positions, input_grad)
 
 
 class _Composite(torch.autograd.Function):
-    """Compositing forward + backward (header group 19).  Gradients for sigma and rgb only; depth is not differentiable."""
+    """Compositing forward + backward (header group 19).  Gradients for sigma and rgb; for the directions (through the segment lengths, header group 20)
+    when they require grad, which `composite` lets through only with `input_grad=True`; depth is not differentiable."""
 
     @staticmethod
     def forward(ctx, t, directions, sigma, rgb, background, final_delta):
@@ -431,6 +516,13 @@ class _Composite(torch.autograd.Function):
         with torch.cuda.device(t.device):
             d_sigma = torch.empty_like(sigma)
             d_samples = torch.empty_like(rgb)
+            if ctx.needs_input_grad[1]:
+                d_directions = torch.empty_like(directions)
+                _lib.check(_lib.load().nrc_nerf_integrate_backward_dirs(_lib.ptr(d_rgb), _lib.ptr(d_alpha), _lib.ptr(d_weights), _lib.ptr(t),
+                                                                        _lib.ptr(directions), _lib.ptr(sigma), _lib.ptr(rgb), _lib.ptr(background),
+                                                                        ctx.final_delta, n, s, _lib.ptr(d_sigma), _lib.ptr(d_samples), _lib.ptr(d_directions),
+                                                                        _lib.stream_of(t)), 'nerf_integrate_backward_dirs')
+                return None, d_directions, d_sigma, d_samples, None, None
             _lib.check(_lib.load().nrc_nerf_integrate_backward(_lib.ptr(d_rgb), _lib.ptr(d_alpha), _lib.ptr(d_weights), _lib.ptr(t), _lib.ptr(directions),
                                                                _lib.ptr(sigma), _lib.ptr(rgb), _lib.ptr(background), ctx.final_delta, n, s, _lib.ptr(d_sigma),
                                                                _lib.ptr(d_samples), _lib.stream_of(t)), 'nerf_integrate_backward')
@@ -438,40 +530,43 @@ class _Composite(torch.autograd.Function):
 
 
 def composite(t: torch.Tensor, directions: torch.Tensor, sigma: torch.Tensor, rgb: torch.Tensor, background: torch.Tensor | None,
-              final_delta: float = 1.0e10):
+              final_delta: float = 1.0e10, input_grad: bool = False):
     """`integrate_samples` as one kernel, with a backward kernel behind autograd (csrc/nerf_rays.hip, header group 19) -> rgb (N, 3), depth (N, 1),
     alpha (N, 1), weights (N, S).  t (N, S), directions (N, 3), sigma (N, S), rgb (N, S, 3), background (3,) or None.  sigma and rgb receive gradients
     (first order only); depth is marked non-differentiable, as the reference's own comment on its depth expression asks.  Falls back to
     `integrate_samples` -- torch's bits and torch's autograd -- for CPU tensors, non-f32 input, an unsupported S, or when t, the directions or the
-    background require grad."""
+    background require grad.  `input_grad=True`: directions that require grad keep the device path and receive the gradient through the segment lengths
+    (t[i+1] - t[i]) |d| (`nrc_nerf_integrate_backward_dirs`, header group 20); a t that requires grad still falls back."""
     tensors = (t, directions, sigma, rgb) + (() if background is None else (background,))
     first = t
     eligible = (t.dim() == 2 and t.shape[0] > 0 and all(x.is_cuda and x.device == first.device and x.dtype == torch.float32 for x in tensors)
                 and tuple(sigma.shape) == tuple(t.shape) and tuple(rgb.shape) == (*t.shape, 3) and tuple(directions.shape) == (t.shape[0], 3)
                 and (background is None or background.numel() == 3)
-                and not (torch.is_grad_enabled() and (t.requires_grad or directions.requires_grad or (background is not None and background.requires_grad))))
+                and not (torch.is_grad_enabled() and (t.requires_grad or (directions.requires_grad and not input_grad) or (background is not None and background.requires_grad))))
     if eligible:
         from . import _lib
         eligible = bool(_lib.load().nrc_nerf_rays_supported(int(t.shape[1]), 0))
     if not eligible:
         return integrate_samples(t, directions, sigma, rgb, background, final_delta)
-    return _Composite.apply(t.detach().contiguous(), directions.detach().contiguous(), sigma.contiguous(), rgb.contiguous(),
+    return _Composite.apply(t.detach().contiguous(), directions.contiguous() if input_grad else directions.detach().contiguous(), sigma.contiguous(), rgb.contiguous(),
                             None if background is None else background.detach().contiguous(), final_delta)
 
 
 def render_rays(coarse_nerf: NeRFBlock | None, nerf: NeRFBlock, origin, direction, view_direction, near_plane: float, far_plane: float,
                 background_color, ray_batch_size: int = 8192, n_samples_coarse_nerf: int = 64, n_samples_nerf: int = 192,
                 randomize_samples: bool = False, random_noise_density: float = 0.0, fused: bool = False, fused_train: bool = False,
-                device_rays: bool = False) -> dict[str, torch.Tensor]:
+                device_rays: bool = False, input_grad: bool = False) -> dict[str, torch.Tensor]:
     """NeRFRayRenderingComponent.forward (Renderer.py:29-95): chunked coarse pass -> PDF samples -> sorted union -> fine pass.  `fused`: the two network
     calls go through `fused_forward` (one direction row per ray); with density noise, and wherever `fused_forward` falls back, the torch path runs.
     `fused_train`: they go through `fused_apply` instead -- the training path, differentiable with respect to the blocks' parameters; with density
     noise the torch path runs.  `device_rays`: sampling, compositing and the fine pass's resampling + sort go through `sample_coarse`, `composite` and
     `sample_fine` (one kernel each; the random numbers are drawn in the torch path's shapes and order, so a seed gives the same offsets); composes with
-    `fused` / `fused_train` and with the torch block; each of the three falls back to the torch expressions below on its own conditions."""
+    `fused` / `fused_train` and with the torch block; each of the three falls back to the torch expressions below on its own conditions.
+    `input_grad`: handed to `fused_apply`, `sample_coarse`, `sample_fine` and `composite` -- with `fused_train=True, device_rays=True` the whole iteration
+    stays on the device while `origin`, `direction` and `view_direction` receive gradients from both passes (header group 20)."""
     def query(block, pos, vd):
         if fused_train and not random_noise_density > 0.0:
-            return fused_apply(block, pos.reshape(-1, 3), vd, dir_group=pos.shape[1])
+            return fused_apply(block, pos.reshape(-1, 3), vd, dir_group=pos.shape[1], input_grad=input_grad)
         if fused and not random_noise_density > 0.0:
             return fused_forward(block, pos.reshape(-1, 3), vd, dir_group=pos.shape[1])
         return block(pos.reshape(-1, 3), vd[:, None, :].expand_as(pos).reshape(-1, 3), random_noise_density)
@@ -485,15 +580,15 @@ def render_rays(coarse_nerf: NeRFBlock | None, nerf: NeRFBlock, origin, directio
         n = o.shape[0]
         if device_rays:
             if use_coarse:
-                t_c, pos = sample_coarse(o, d, n_samples_coarse_nerf, near_plane, far_plane, randomize_samples)
+                t_c, pos = sample_coarse(o, d, n_samples_coarse_nerf, near_plane, far_plane, randomize_samples, input_grad=input_grad)
                 dens, col = query(coarse_nerf, pos.view(n, -1, 3), vd)
-                rgb_c, depth_c, alpha_c, w_c = composite(t_c, d, dens.reshape(n, -1), col.reshape(n, -1, 3), bg)
-                t, pos = sample_fine(t_c, w_c, n_samples_nerf, randomize_samples, o, d)
+                rgb_c, depth_c, alpha_c, w_c = composite(t_c, d, dens.reshape(n, -1), col.reshape(n, -1, 3), bg, input_grad=input_grad)
+                t, pos = sample_fine(t_c, w_c, n_samples_nerf, randomize_samples, o, d, input_grad=input_grad)
                 chunks['rgb_coarse'].append(rgb_c); chunks['depth_coarse'].append(depth_c); chunks['alpha_coarse'].append(alpha_c)
             else:
-                t, pos = sample_coarse(o, d, n_samples_nerf, near_plane, far_plane, randomize_samples)
+                t, pos = sample_coarse(o, d, n_samples_nerf, near_plane, far_plane, randomize_samples, input_grad=input_grad)
             dens, col = query(nerf, pos.view(n, -1, 3), vd)
-            rgb, depth, alpha, _ = composite(t, d, dens.reshape(n, -1), col.reshape(n, -1, 3), bg)
+            rgb, depth, alpha, _ = composite(t, d, dens.reshape(n, -1), col.reshape(n, -1, 3), bg, input_grad=input_grad)
             chunks['rgb'].append(rgb); chunks['depth'].append(depth); chunks['alpha'].append(alpha)
             continue
         if use_coarse:

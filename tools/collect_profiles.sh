@@ -24,9 +24,13 @@ prof() {
 # MODE=nerf when csrc/nerf_grad.hip or the shared csrc/nerf_net.h changed; then tools/make_profile_summary.py ROUND nerf_net.hip nerf_net.h nerf_grad.hip.
 # MODE=nerf_rays: a change confined to csrc/nerf_rays.hip -- the bench command (all durations; no bench leg runs the ray stages) and one trace of
 # tools/bench_nerf_rays.py; then tools/make_profile_summary.py ROUND nerf_rays.hip (every other kernel's counters carried over).
+# MODE=nerf_input_grad: group 20 (csrc/nerf_input_grad.hip, and what it adds to csrc/nerf_rays.hip) -- no bench command (no bench leg runs these kernels; a call
+# of its own after MODE=nerf, which runs it): one trace of tools/bench_nerf_input_grad.py, one of tools/bench_nerf_rays.py (the touched ray stages), and the
+# NeRF counter groups on the new launches, each a run of its own; then tools/make_profile_summary.py ROUND nerf_input_grad.hip nerf_rays.hip (plus
+# nerf_net.hip nerf_net.h after MODE=nerf and MODE=nerf_train when the shared header moved).
 MODE=${1:-all}
 # the full bench command (bench.py --full --steps 20 --warmup 5, every leg): the per-kernel averages of the InstantNGP kernels must agree with the bench line
-[ "$MODE" != nerf_train ] && prof 900 $O/bench_stats.log --kernel-trace --stats --output-format csv -d $O/bench_stats -- python3 $R/bench.py --full --steps 20 --warmup 5
+[ "$MODE" != nerf_train ] && [ "$MODE" != nerf_input_grad ] && prof 900 $O/bench_stats.log --kernel-trace --stats --output-format csv -d $O/bench_stats -- python3 $R/bench.py --full --steps 20 --warmup 5
 # the 3DGS kernels at ONE size (the bench command runs 1 M and 6 M Gaussians through the same kernel names)
 if [ "$MODE" = nerf ] || [ "$MODE" = all ]; then
 prof 300 $O/nerf_stats.log --kernel-trace --stats --output-format csv -d $O/nerf_stats -- python3 $R/tools/bench_nerf_fused.py 5
@@ -46,7 +50,15 @@ fi
 if [ "$MODE" = nerf_rays ]; then
 prof 300 $O/nerf_rays_stats.log --kernel-trace --stats --output-format csv -d $O/nerf_rays_stats -- python3 $R/tools/bench_nerf_rays.py 7
 fi
-if [ "$MODE" = nerf ] || [ "$MODE" = nerf_train ] || [ "$MODE" = nerf_rays ]; then
+if [ "$MODE" = nerf_input_grad ]; then
+prof 300 $O/nerf_input_grad_stats.log --kernel-trace --stats --output-format csv -d $O/nerf_input_grad_stats -- python3 $R/tools/bench_nerf_input_grad.py 7
+prof 300 $O/nerf_rays_stats.log --kernel-trace --stats --output-format csv -d $O/nerf_rays_stats -- python3 $R/tools/bench_nerf_rays.py 7
+for set in "GRBM_GUI_ACTIVE SQ_WAVES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_VALU_MFMA_MOPS_F16 SQ_VALU_MFMA_BUSY_CYCLES" "TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum GRBM_GUI_ACTIVE" "SQ_WAVE_CYCLES SQ_WAIT_INST_LDS SQ_INST_CYCLES_VMEM SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_VALU"; do
+  tag=$(echo $set | tr ' ' '_' | cut -c1-32)
+  prof 300 $O/pmcni_$tag.log --pmc $set --kernel-trace --kernel-include-regex "k_nerf_(input_grad|dir_reduce|positions_bw|integrate_bw)" --output-format csv -d $O/pmcni_$tag -- python3 $R/tools/bench_nerf_input_grad.py 7
+done
+fi
+if [ "$MODE" = nerf ] || [ "$MODE" = nerf_train ] || [ "$MODE" = nerf_rays ] || [ "$MODE" = nerf_input_grad ]; then
 find $O -name "*.db" -delete; find $O -name "*_agent_info.csv" -delete; find $O -path "*_stats/*" -name "*kernel_trace.csv" -delete; du -sh $O; [ -f $O/bench_stats.log ] && tail -5 $O/bench_stats.log
 exit 0
 fi
