@@ -50,8 +50,10 @@ enum {
  * 17 = group 18 (the vanilla NeRF block's training forward and backward) is new, every earlier signature is unchanged;
  * 18 = group 19 (nrc_nerf_rays_* / nrc_nerf_sample_* / nrc_nerf_integrate_*: NeRF sampling, compositing and resampling) is new, every earlier signature is
  * unchanged;
- * 19 = group 20 (the vanilla NeRF path's gradients to sample positions, viewing directions and rays) is new, every earlier signature is unchanged. */
-#define NRC_ABI_VERSION 19
+ * 19 = group 20 (the vanilla NeRF path's gradients to sample positions, viewing directions and rays) is new, every earlier signature is unchanged;
+ * 20 = group 21 (nrc_gs_render_features_band / nrc_gs_backward_features_band: N-channel per-Gaussian features blended by the rasterizer's weights) is new,
+ * every earlier signature is unchanged. */
+#define NRC_ABI_VERSION 20
 /* library identification; also used by the loader's symbol check */
 int nrc_abi_version(void);
 const char* nrc_build_info(void);
@@ -357,7 +359,8 @@ int nrc_ngp_query_fused(const float* xyz01, const float* dirs, int64_t M, const 
  *                       atomic instruction; dL_dmean2D / dL_dopacity (and dL_dconic (P,4) / dL_dcolor (P,3), which may be NULL) are written
  *                       from the records by the per-Gaussian backward, WHICH LEAVES EVERY RECORD IT READ CLEARED (ABI 3).  records_clear = 0:
  *                       the call clears the workspace first (any contents); records_clear != 0: the caller guarantees that all P x 16 floats
- *                       are zero -- e.g. the same buffer after a previous nrc_gs_backward of the same P -- and the clearing launch is skipped.
+ *                       are zero, or as nrc_gs_backward_features_band (group 21) left them -- e.g. the same buffer after a previous nrc_gs_backward of
+ *                       the same P -- and the clearing launch is skipped.
  * ===================================================================================================== */
 /* bytes of the binning workspace `bin_hist` (depth pre-sort buffers, row-span records, cursors) for `span_capacity` span records
  * (0 = default 4 P + 65536); returns 0 when the image has more than 256 tile rows or columns: pass NULL, the per-tile key sort is used.
@@ -1216,6 +1219,40 @@ int nrc_nerf_positions_backward(const float* d_positions, const float* t, int64_
 int nrc_nerf_integrate_backward_dirs(const float* d_rgb, const float* d_alpha, const float* d_weights, const float* t, const float* directions,
                                      const float* sigma, const float* rgb_samples, const float* background, float final_delta, int64_t N, int32_t S,
                                      float* d_sigma, float* d_rgb_samples, float* d_directions, nrc_stream_t stream);
+
+/* =====================================================================================================
+ * Group 21 -- N-channel per-Gaussian features blended by the 3DGS rasterizer's own weights, differentiably (csrc/gs_features.hip).  No reference
+ *            counterpart: the upstream rasterizer blends three colour channels, and ceil(C / 3) full calls with colors_precomp triples and bg = 0 are the
+ *            only way to the same maps there.  Both calls run on the state a colour forward of group 4 left behind (point_list, ranges, splat_records,
+ *            tile_order = the tile_fill of nrc_gs_bin_render*, n_contrib, final_T) for the same P, W, H and band: no preprocess, no sort, no binning.
+ *
+ *   features (P, C) f32, the caller's tensor, 1 <= C <= 256.  For a pixel p the blended set and the weights are the colour pass's own: the entries
+ *            k <= n_contrib[p] of the tile's list with !(power > 0) and alpha >= 1/255, alpha = min(0.99, o exp(power)) in k_render's statements,
+ *            T <- fmaf(-T, alpha, T), w_i = alpha_i T_i -- bit for bit the weight the colour received.
+ *   nrc_gs_render_features_band: out_features (C, H, W), full frame, the band's pixel rows written: feature_map[c, p] = sum_i w_i(p) f[i, c] in list order
+ *            as F = fmaf(f, w, F), background 0, NOT normalised by alpha.  P == 0: the band's rows are zero.  One launch, k_render_features.
+ *   nrc_gs_backward_features_band: the backward of L = <dL_dfeature_map, feature_map> ((C, H, W), the band's rows read).  dL_dfeatures (P, C), fully written
+ *            (rows no pixel blended are zero), may be NULL: dL/df[i, c] = sum_p w_i g_c(p).  The gradient through the weights,
+ *            dL/dalpha_i(p) = T_i sum_c (f[i, c] - n_c) g_c with n_c <- alpha f_c + (1 - alpha) n_c walked back to front from final_T (no background term),
+ *            is ADDED as six per-Gaussian sums (opacity, mean2D x, y, conic xx, xy, yy) to slots [3..8] of grad_records, the (P, 16) f32, 64-byte aligned
+ *            workspace of nrc_gs_backward.  records_clear = 0: the call clears the records first; != 0: the caller guarantees they are zero.  The caller then
+ *            MUST run one of nrc_gs_backward / _band / _aux_band / _pose_band with records_clear != 0 on the same frame state and the same band: its blend
+ *            backward adds the colour's (and the maps') sums, and its per-Gaussian backward consumes and clears both -- dL_dmean2D, every leaf gradient and
+ *            dL_dcamera of that call are then the gradients of colour + maps + features together.  (With a zero dL_dpix that call adds nothing of its
+ *            own.)  There is no feature form of nrc_gs_backward_rest_step.  Sums are f32: LDS float atomics across a tile's blocks, one global float atomic
+ *            per (tile, Gaussian, value), so two runs agree to rounding, not bitwise.  Launches: up to two clears, k_render_features_bw.
+ *   C > 16 runs as ceil(C / 16) chunks in the second grid dimension of the one launch.  Neither call synchronises the host or reads anything back: both work
+ *            inside a stream capture.  NRC_ERR_INVALID before any HIP call: a band that nrc_gs_*_band refuses; C < 1 or C > 256; P < 0, W < 1, H < 1; a null
+ *            features, point_list or splat_records with P > 0; a null ranges, tile_order, n_contrib, out_features, final_T or dL_dfeature_map; grad_records
+ *            null with P > 0 or not 64-byte aligned; splat_records not 16-byte aligned.
+ * ===================================================================================================== */
+int nrc_gs_render_features_band(int32_t P, int32_t C, int32_t W, int32_t H, const float* features, const int32_t* point_list, const uint32_t* ranges,
+                                const float* splat_records, const uint32_t* tile_order, const uint32_t* n_contrib, int32_t tile_row_begin, int32_t n_tile_rows,
+                                float* out_features, nrc_stream_t stream);
+int nrc_gs_backward_features_band(int32_t P, int32_t C, int32_t W, int32_t H, const float* features, const int32_t* point_list, const uint32_t* ranges,
+                                  const float* splat_records, const uint32_t* tile_order, const uint32_t* n_contrib, const float* final_T,
+                                  const float* dL_dfeature_map, float* dL_dfeatures, float* grad_records, int32_t records_clear, int32_t tile_row_begin,
+                                  int32_t n_tile_rows, nrc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -31,6 +31,9 @@ PER_FILE_FLAGS = {
     # + no atomic optimizer: it rewrites the one-lane LDS atomics of k_render_bw into 15-instruction wave-reduction loops
     # + no SLP vectoriser: it packs the blend arithmetic of two list entries into v_pk_* and pays in v_mov (the blend states its own pairs: blend_power)
     'gs_raster.hip': ['-ffp-contract=off', '-fno-slp-vectorize', '-mllvm', '-amdgpu-atomic-optimizer-strategy=None'],
+    # gs_raster.hip's flags, all three: the feature pass recomputes the colour pass's alpha with the same statements (csrc/gs_blend.h) and must get the same
+    # bits, and its per-Gaussian sums meet in LDS through float atomics that the atomic optimizer would rewrite into wave-reduction loops
+    'gs_features.hip': ['-ffp-contract=off', '-fno-slp-vectorize', '-mllvm', '-amdgpu-atomic-optimizer-strategy=None'],
     # no SLP vectoriser either: packed f32 VALU next to MFMAs is priced above its issue slot on this chip (MI355X_MICROARCH.md), and the packing
     # costs v_mov: k_nwie_bwd 2 641 -> 2 451 vector instructions, k_gb_split 3 015 -> 2 853; the fused training iteration -1 %, the image path unchanged
     'ngp_net.hip': ['-fno-slp-vectorize'],

@@ -155,7 +155,7 @@ def _opt(t):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, sh_rest=None, raw=False, rest_step=None, tile_rows=None,
-                depth_alpha=False, viewmatrix=None, projmatrix=None, campos=None):
+                depth_alpha=False, viewmatrix=None, projmatrix=None, campos=None, features=None):
         rs = raster_settings
         lib = _lib.load()
         band = check_tile_rows(tile_rows, rs.image_height)
@@ -169,6 +169,9 @@ class _RasterizeGaussians(torch.autograd.Function):
         if depth_alpha and rest_step is not None:
             raise RuntimeError('return_depth_alpha together with rest_step: the backward pass that steps the `rest` SH tensor (nrc_gs_backward_rest_step) takes the '
                                'colour gradient only -- there is no depth-and-alpha form of it; render without rest_step and let the optimizer take that step')
+        if features is not None and rest_step is not None:
+            raise RuntimeError('features together with rest_step: the backward pass that steps the `rest` SH tensor (nrc_gs_backward_rest_step) takes the '
+                               'colour gradient only -- there is no feature form of it; render without rest_step and let the optimizer take that step')
         if band is not None and rest_step is not None:
             raise RuntimeError('rest_step together with tile_rows: the backward pass of a band holds this band\'s SHARE of the gradient only, and an Adam step '
                                'taken on a partial gradient is not the optimizer\'s step -- sum the shares over the bands first and step then')
@@ -224,6 +227,9 @@ class _RasterizeGaussians(torch.autograd.Function):
         band_mask = None if band is None else torch.empty(n1, dtype=u8, device=dev)
         n_contrib = torch.empty(H * W, dtype=i32, device=dev)
         final_T = torch.empty(H * W, dtype=f32, device=dev)
+        feat_c = None
+        if features is not None:
+            feat_c = _check_features(features, P, dev)
         global _LAST_COUNTS
 
         def preprocess(cap_spans, cap_inst, box=None, ticket=0):
@@ -335,6 +341,16 @@ class _RasterizeGaussians(torch.autograd.Function):
         global _LAST_BAND_MASK
         # (the per-tile key sort fallback, which takes the band (0, gy) only, does not write the mask: every visible Gaussian is in that band)
         _LAST_BAND_MASK = None if band is None else ((band_mask[:P] != 0) if bin_hist is not None and P > 0 else (radii[:P] > 0))
+        feature_map = None
+        if feat_c is not None:
+            # the feature pass: one launch on the state the colour pass just left (lists, tile order, records, n_contrib); a band writes its own rows only
+            C_f = int(feat_c.shape[1])
+            feature_map = torch.empty(C_f, H, W, dtype=f32, device=dev) if band is None else torch.zeros(C_f, H, W, dtype=f32, device=dev)
+            b0, bn = band if band is not None else (0, gy)
+            _lib.check(lib.nrc_gs_render_features_band(P, C_f, W, H, _lib.ptr(feat_c), _lib.ptr(point_list), _lib.ptr(ranges), _lib.ptr(splat), _lib.ptr(tile_fill),
+                                                       _lib.ptr(n_contrib), b0, bn, _lib.ptr(feature_map), st), 'gs_render_features_band')
+        ctx.features = feat_c
+        ctx.features_grad = feat_c is not None and bool(ctx.needs_input_grad[17])
         ctx.band = band
         ctx.depth_alpha = depth_alpha
         ctx.raster_settings = rs
@@ -357,12 +373,14 @@ class _RasterizeGaussians(torch.autograd.Function):
         # radii carry no gradient: without this autograd hands the backward a zero-filled (P,) int tensor for them -- a 4 MB fill launch per step
         ctx.set_materialize_grads(False)
         if depth_alpha:
-            return color, radii_out, aux[0], aux[1]
-        return color, radii_out
+            return (color, radii_out, aux[0], aux[1]) + (() if feature_map is None else (feature_map,))
+        return (color, radii_out) + (() if feature_map is None else (feature_map,))
 
     @staticmethod
     @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_out_color, _grad_radii, *grad_depth_alpha):   # the two extra output gradients exist only for a forward with depth_alpha
+    def backward(ctx, grad_out_color, _grad_radii, *grad_extra):   # the extra output gradients: depth and alpha (a forward with depth_alpha), then the feature map
+        grad_depth_alpha = grad_extra[:2] if ctx.depth_alpha else ()
+        grad_feature_map = grad_extra[2 if ctx.depth_alpha else 0] if ctx.features is not None else None
         (means3D, sh, col, sc, rot, cov, radii, points_xy, conic_opacity, rgb, clamped, cov3D, point_list, ranges, n_contrib,
          final_T, splat, tile_order, sh_rest, opac, cam_block) = ctx.saved_tensors
         raw, has_rest = ctx.raw, ctx.has_rest
@@ -404,6 +422,22 @@ class _RasterizeGaussians(torch.autograd.Function):
         dsh_rest = torch.empty(n1, M - 1, 3, dtype=f32, device=dev) if has_rest and rest_step is None else None
         dscale = torch.empty(n1, 3, dtype=f32, device=dev) if has_sr else None
         drot = torch.empty(n1, 4, dtype=f32, device=dev) if has_sr else None
+        dfeat = None
+        feat = ctx.features
+        if feat is not None:
+            # The feature backward goes FIRST: it leaves its geometry sums in slots [3..8] of the records, the colour backward below adds its own and its
+            # per-Gaussian part consumes and clears both.  A missing output gradient counts as zero: no launch, exact zeros for `features`.
+            C_f = int(feat.shape[1])
+            if grad_feature_map is not None and P > 0:
+                g_f = grad_feature_map.to(f32).reshape(C_f, H, W).contiguous()
+                dfeat = torch.empty(n1, C_f, dtype=f32, device=dev) if ctx.features_grad else None
+                b0, bn = ctx.band if ctx.band is not None else (0, (H + 15) // 16)
+                _lib.check(lib.nrc_gs_backward_features_band(P, C_f, W, H, _lib.ptr(feat), _lib.ptr(point_list), _lib.ptr(ranges), _lib.ptr(splat), _lib.ptr(tile_order),
+                                                             _lib.ptr(n_contrib), _lib.ptr(final_T), _lib.ptr(g_f), _lib.ptr(dfeat), _lib.ptr(grad_records),
+                                                             int(records_clear), b0, bn, _lib.stream_of(g)), 'gs_backward_features_band')
+                records_clear = True
+            elif ctx.features_grad:
+                dfeat = torch.zeros(n1, C_f, dtype=f32, device=dev)
         dcam = None
         if ctx.camera is not None:
             # the same backward with two extra launches between the blend backward and the per-Gaussian backward: dL/d(viewmatrix | projmatrix | campos) as float[35]
@@ -468,23 +502,51 @@ class _RasterizeGaussians(torch.autograd.Function):
         cut = (lambda t: t) if P == n1 else (lambda t: t[:P])     # (whole buffers when nothing is cut: a gradient that is not a view can be adopted as .grad without a copy)
         return (cut(dmean3D), cut(dmean2D), cut(dsh) if has_sh else None, cut(dcolor) if has_col else None,
                 cut(dopacity).reshape(ctx.opacity_shape), cut(dscale) if has_sr else None, cut(drot) if has_sr else None,
-                cut(dcov3D) if has_cov else None, None, cut(dsh_rest) if dsh_rest is not None else None, None, None, None, None) + _camera_grads(ctx.camera, dcam)
+                cut(dcov3D) if has_cov else None, None, cut(dsh_rest) if dsh_rest is not None else None, None, None, None, None) + _camera_grads(ctx.camera, dcam, feat is not None) \
+            + (() if feat is None else (cut(dfeat) if dfeat is not None else None,))
 
 
-def _camera_grads(camera, dcam):
-    """The backward's float[35] as the gradients of viewmatrix, projmatrix and campos, each in its tensor's own shape, dtype and device (None where none is needed)."""
+def _check_features(features, P: int, dev) -> torch.Tensor:
+    """`features` as the (P, C) f32 contiguous tensor the feature pass reads; ValueError / RuntimeError naming the argument otherwise."""
+    if not torch.is_tensor(features):
+        raise ValueError(f'features must be a (P, C) float32 CUDA tensor, got {type(features).__name__}')
+    if not features.is_cuda or features.device != dev:
+        raise RuntimeError(f'features must be a CUDA tensor on the device of means3D ({dev}), got {features.device}')
+    if features.dtype != torch.float32:
+        raise ValueError(f'features must have dtype torch.float32, got {features.dtype}')
+    if features.dim() != 2 or features.shape[0] != P:
+        raise ValueError(f'features must have shape (P, C) = ({P}, C), got {tuple(features.shape)}')
+    if not 1 <= features.shape[1] <= 256:
+        raise ValueError(f'features: C = {features.shape[1]} channels, 1 <= C <= 256 are supported')
+    return features.detach().contiguous()
+
+
+def _camera_grads(camera, dcam, placeholders=False):
+    """The backward's float[35] as the gradients of viewmatrix, projmatrix and campos, each in its tensor's own shape, dtype and device (None where none is needed).
+    `placeholders`: three Nones when the pose tensors were no inputs but a later input (features) needs their positions filled."""
     if camera is None:
-        return ()
+        return (None, None, None) if placeholders else ()
     needs, like = camera
     parts = (dcam[:16], dcam[16:32], dcam[32:35])
     return tuple(part.reshape(shape).to(device=device, dtype=dtype) if need else None for need, part, (shape, dtype, device) in zip(needs, parts, like))
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, sh_rest=None, raw=False, rest_step=None, tile_rows=None,
-                        return_depth_alpha=False, camera_grad=False):
+                        return_depth_alpha=False, camera_grad=False, features=None):
     """`tile_rows` = (begin, n): render and differentiate the band of 16-pixel tile rows [begin, begin + n) only (see GaussianRasterizer.forward); None: the frame.
     `return_depth_alpha`: (image, radii, depth, alpha) instead of (image, radii) -- see GaussianRasterizer.forward.
-    `camera_grad`: gradients to raster_settings.viewmatrix / projmatrix / campos, for those that require grad -- see GaussianRasterizer.forward."""
+    `camera_grad`: gradients to raster_settings.viewmatrix / projmatrix / campos, for those that require grad -- see GaussianRasterizer.forward.
+    `features`: a (P, C) tensor blended by the colour's weights; appends feature_map (C, H, W) to the outputs -- see GaussianRasterizer.forward."""
+    if features is not None:
+        if rest_step is not None:
+            raise RuntimeError('features together with rest_step: the backward pass that steps the `rest` SH tensor (nrc_gs_backward_rest_step) takes the '
+                               'colour gradient only -- there is no feature form of it; render without rest_step and let the optimizer take that step')
+        rs = raster_settings
+        pose = (None, None, None)
+        if camera_grad and torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (rs.viewmatrix, rs.projmatrix, rs.campos)):
+            pose = (rs.viewmatrix, rs.projmatrix, rs.campos)
+        return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, sh_rest, raw, None,
+                                         None if tile_rows is None else tuple(int(v) for v in tile_rows), bool(return_depth_alpha), *pose, features)
     if camera_grad:
         if rest_step is not None:
             raise RuntimeError('camera_grad together with rest_step: the backward pass that steps the `rest` SH tensor (nrc_gs_backward_rest_step) has no camera '
@@ -516,7 +578,7 @@ class GaussianRasterizer(torch.nn.Module):
             return z > 0.2
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, shs_rest=None,
-                raw_parameters=False, rest_step=None, tile_rows=None, return_depth_alpha=False, camera_grad=False):
+                raw_parameters=False, rest_step=None, tile_rows=None, return_depth_alpha=False, camera_grad=False, features=None):
         """The reference's call (Renderer.py:75-81) plus two keyword extensions for callers that own the model tensors: `shs_rest` -- `shs` is then
         (`rest_step`, round 6: an object whose take() returns (parameter, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, bc1, bc2) -- the backward pass then applies
         the optimizer's Adam step to shs_rest itself and returns no gradient for it: nerficg_amd.gaussian_splatting.RestStep)
@@ -537,7 +599,16 @@ class GaussianRasterizer(torch.nn.Module):
         (`bg` and the intrinsics receive none).  Everything else the call returns is bit for bit that of the call without the flag, and every other gradient comes from the same
         launches on the same per-Gaussian sums: the backward pass runs two more launches (a reduction over the Gaussians in a fixed order, no atomics) and reads nothing back.  Works with every parameter
         form above, with `tile_rows` (the band's share), `return_depth_alpha` and inside fixed_capacity; not together with `rest_step` (RuntimeError).  When none
-        of the three requires grad the flag changes nothing.  A pose tensor: nerficg_amd.gaussian_splatting.make_raster_settings chains the gradient on to c2w."""
+        of the three requires grad the flag changes nothing.  A pose tensor: nerficg_amd.gaussian_splatting.make_raster_settings chains the gradient on to c2w.
+        `features`: a (P, C) float32 CUDA tensor of the caller's, 1 <= C <= 256 (semantic or language features, normals, logits, ids, confidences).  The call
+        appends one output, feature_map (C, H, W): (image, radii, feature_map), with `return_depth_alpha` (image, radii, depth, alpha, feature_map).
+        feature_map[c] = sum w_i features[i, c] with the colour's own blended set and weights w_i = alpha_i T_i, bit for bit, background 0, ACCUMULATED like the
+        depth map (divide by alpha for an expectation).  It is differentiable: gradients go to `features` when it requires grad and, through the weights, to every
+        geometry input, to `means2D` and -- with `camera_grad` -- to the camera; a feature map that takes no part in the loss counts as a zero gradient (its
+        backward launch is skipped, `features.grad` is exact zeros).  The pass is one extra launch on the state the colour pass left (no second preprocess, sort
+        or binning) and one more in the backward; image, radii and everything the backward saves are bit for bit those of the call without `features`.  Works with
+        every parameter form above, with `tile_rows` (the band's rows and the band's share), `return_depth_alpha`, `camera_grad` and inside fixed_capacity; not
+        together with `rest_step` (RuntimeError).  A wrong type, shape, dtype, device or C raises ValueError / RuntimeError naming `features`."""
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
         if ((scales is None or rotations is None) and cov3D_precomp is None) or ((scales is not None or rotations is not None) and cov3D_precomp is not None):
@@ -545,4 +616,4 @@ class GaussianRasterizer(torch.nn.Module):
         empty = torch.Tensor([])
         return rasterize_gaussians(means3D, means2D, empty if shs is None else shs, empty if colors_precomp is None else colors_precomp, opacities,
                                    empty if scales is None else scales, empty if rotations is None else rotations,
-                                   empty if cov3D_precomp is None else cov3D_precomp, self.raster_settings, shs_rest, raw_parameters, rest_step, tile_rows, return_depth_alpha, camera_grad)
+                                   empty if cov3D_precomp is None else cov3D_precomp, self.raster_settings, shs_rest, raw_parameters, rest_step, tile_rows, return_depth_alpha, camera_grad, features)

@@ -645,8 +645,11 @@ class RestStep:
 
 
 def render_image_training(gaussians: Gaussians, cam: PerspectiveCamera, c2w: np.ndarray, fuse_rest_step: bool | None = None,
-                          band: tuple[int, int] | None = None, depth_alpha: bool = False, camera_grad: bool | None = None) -> dict[str, torch.Tensor]:
-    """GaussianSplatting/Renderer.py:51-86.  camera_grad (default None: on exactly when `c2w` is a tensor that requires grad): the loss is differentiated with
+                          band: tuple[int, int] | None = None, depth_alpha: bool = False, camera_grad: bool | None = None,
+                          features: torch.Tensor | None = None) -> dict[str, torch.Tensor]:
+    """GaussianSplatting/Renderer.py:51-86.  features: a (P, C) float32 tensor of the caller's (it is NOT carried through densification: the caller owns it); the
+    outputs gain 'features', (C, H, W), blended with the colour's weights and differentiable to the tensor and the geometry (the rasterizer's `features`) -- refused
+    together with the fused f_rest step (RuntimeError), like depth_alpha.  camera_grad (default None: on exactly when `c2w` is a tensor that requires grad): the loss is differentiated with
     respect to the pose as well (the rasterizer's `camera_grad`; pose refinement, tracking against a frozen model) -- refused together with the fused f_rest step
     (RuntimeError), like a band.  depth_alpha: the outputs gain 'alpha' and 'depth', (1, H, W) like 'rgb' is (3, H, W), both differentiable: alpha = 1 - T of
     the blend, depth = (sum w z) / (alpha + 1e-6), the normalisation of InstantNGP/Renderer.py:82 (the rasterizer's `return_depth_alpha`).  Refused together with the
@@ -670,6 +673,9 @@ def render_image_training(gaussians: Gaussians, cam: PerspectiveCamera, c2w: np.
     if depth_alpha and fuse:
         raise RuntimeError('render_image_training: depth_alpha= together with the fused f_rest step -- the backward pass that steps f_rest takes the colour '
                            'gradient only (the rasterizer refuses return_depth_alpha with rest_step); leave fuse_rest_step off for frames with a depth or alpha loss')
+    if features is not None and fuse:
+        raise RuntimeError('render_image_training: features= together with the fused f_rest step -- the backward pass that steps f_rest takes the colour '
+                           'gradient only (the rasterizer refuses features with rest_step); leave fuse_rest_step off for frames with a feature loss')
     # the carrier of the screen-space gradient (Renderer.py:56-58: zeros_like + 0, retain_grad): the rasterizer never reads its VALUES, only hands it a
     # gradient -- a leaf of uninitialised memory receives the same .grad without a 12 MB fill and a 24 MB add per step
     viewspace_points = torch.empty_like(positions).requires_grad_(True)
@@ -677,15 +683,17 @@ def render_image_training(gaussians: Gaussians, cam: PerspectiveCamera, c2w: np.
     if gaussians.baked:  # a baked model holds activated values
         image, radii, *aux = rasterizer(means3D=positions, means2D=viewspace_points, shs=gaussians.get_features_dc, shs_rest=gaussians.get_features_rest,
                                         opacities=gaussians.get_opacities, scales=gaussians.get_scales, rotations=gaussians.get_rotations, tile_rows=band,
-                                        return_depth_alpha=depth_alpha, camera_grad=camera_grad)
+                                        return_depth_alpha=depth_alpha, camera_grad=camera_grad, features=features)
     else:  # raw parameters straight into the kernels: no get_features concatenation, no separate exp / sigmoid / normalize passes (a25)
         rest_step = RestStep(gaussians) if fuse and not getattr(gaussians.optimizer, 'capturable', False) and not torch.cuda.is_current_stream_capturing() and torch.is_grad_enabled() and gaussians._features_rest.requires_grad and gaussians._features_rest.shape[1] > 0 and torch.is_tensor(c2w) else None
         image, radii, *aux = rasterizer(means3D=positions, means2D=viewspace_points, shs=gaussians._features_dc, shs_rest=gaussians._features_rest,
                                         opacities=gaussians._opacities, scales=gaussians._scales, rotations=gaussians._rotations, raw_parameters=True, rest_step=rest_step,
-                                        tile_rows=band, return_depth_alpha=depth_alpha, camera_grad=camera_grad)
+                                        tile_rows=band, return_depth_alpha=depth_alpha, camera_grad=camera_grad, features=features)
     outputs = _TrainingOutputs({'rgb': image, 'viewspace_points': viewspace_points, 'radii': radii})
     if depth_alpha:
         outputs.update(_depth_alpha_outputs(aux[0], aux[1], True))
+    if features is not None:
+        outputs['features'] = aux[-1]
     if band is not None:
         outputs['band_mask'] = last_band_mask()
     return outputs
@@ -749,8 +757,10 @@ class _TrainingOutputs(dict):
 
 @torch.no_grad()
 def render_image_inference(gaussians: Gaussians, cam: PerspectiveCamera, c2w: np.ndarray, scale_modifier: float = 1.0, to_chw: bool = False,
-                           use_baked_covariance: bool = True, band: tuple[int, int] | None = None, depth_alpha: bool = False):
-    """depth_alpha: the outputs gain 'alpha' (1 - T of the blend) and 'depth' (accumulated view-space depth / (alpha + 1e-6)), (H, W, 1) or (1, H, W) with to_chw, as
+                           use_baked_covariance: bool = True, band: tuple[int, int] | None = None, depth_alpha: bool = False,
+                           features: torch.Tensor | None = None):
+    """features: a (P, C) float32 tensor of the caller's; the outputs gain 'features', the map blended with the colour's weights (the rasterizer's `features`),
+    (H, W, C) or (C, H, W) with to_chw.  depth_alpha: the outputs gain 'alpha' (1 - T of the blend) and 'depth' (accumulated view-space depth / (alpha + 1e-6)), (H, W, 1) or (1, H, W) with to_chw, as
     instant_ngp.render_image returns them.  band = (tile_row_begin, n_tile_rows): only that band of tile rows of the frame is rendered (zero elsewhere; parallel.gather_band_images composes the
     frame from the ranks' bands).  GaussianSplatting/Renderer.py:89-155 with the fused SH path (USE_FUSED_SH_CONVERSION = True, the shipped default); a baked model
     (trained checkpoint, Model.py:248-273) is rasterized from its baked covariances like the reference's USE_BAKED_COVARIANCE branch
@@ -763,15 +773,17 @@ def render_image_inference(gaussians: Gaussians, cam: PerspectiveCamera, c2w: np
         covariances = None  # "Baked covariance requested but not available"
     if covariances is not None:
         image, _, *aux = rasterizer(means3D=positions, means2D=torch.empty_like(positions), shs=gaussians.get_features, opacities=gaussians.get_opacities,
-                                    cov3D_precomp=covariances, tile_rows=band, return_depth_alpha=depth_alpha)
+                                    cov3D_precomp=covariances, tile_rows=band, return_depth_alpha=depth_alpha, features=features)
     else:
         image, _, *aux = rasterizer(means3D=positions, means2D=torch.empty_like(positions), shs=gaussians.get_features,
                                     opacities=gaussians.get_opacities, scales=gaussians.get_scales, rotations=gaussians.get_rotations, tile_rows=band,
-                                    return_depth_alpha=depth_alpha)
+                                    return_depth_alpha=depth_alpha, features=features)
     image.clamp_(0.0, 1.0)
     outputs = {'rgb': image if to_chw else image.permute(1, 2, 0)}
     if depth_alpha:
         outputs.update(_depth_alpha_outputs(aux[0], aux[1], to_chw))
+    if features is not None:
+        outputs['features'] = aux[-1] if to_chw else aux[-1].permute(1, 2, 0)
     return outputs
 
 

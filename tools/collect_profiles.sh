@@ -28,6 +28,9 @@ prof() {
 # of its own after MODE=nerf, which runs it): one trace of tools/bench_nerf_input_grad.py, one of tools/bench_nerf_rays.py (the touched ray stages), and the
 # NeRF counter groups on the new launches, each a run of its own; then tools/make_profile_summary.py ROUND nerf_input_grad.hip nerf_rays.hip (plus
 # nerf_net.hip nerf_net.h after MODE=nerf and MODE=nerf_train when the shared header moved).
+# MODE=gs_features: group 21 (csrc/gs_features.hip, csrc/gs_blend.h; no existing source changes) -- the bench command (all durations; no bench leg runs the feature
+# pass), one trace of tools/bench_gs_features.py and three counter groups on the two new launches, each a run of its own; then
+# tools/make_profile_summary.py ROUND gs_features.hip gs_blend.h (every other kernel's counters carried over).
 MODE=${1:-all}
 # the full bench command (bench.py --full --steps 20 --warmup 5, every leg): the per-kernel averages of the InstantNGP kernels must agree with the bench line
 [ "$MODE" != nerf_train ] && [ "$MODE" != nerf_input_grad ] && prof 900 $O/bench_stats.log --kernel-trace --stats --output-format csv -d $O/bench_stats -- python3 $R/bench.py --full --steps 20 --warmup 5
@@ -58,7 +61,14 @@ for set in "GRBM_GUI_ACTIVE SQ_WAVES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_VA
   prof 300 $O/pmcni_$tag.log --pmc $set --kernel-trace --kernel-include-regex "k_nerf_(input_grad|dir_reduce|positions_bw|integrate_bw)" --output-format csv -d $O/pmcni_$tag -- python3 $R/tools/bench_nerf_input_grad.py 7
 done
 fi
-if [ "$MODE" = nerf ] || [ "$MODE" = nerf_train ] || [ "$MODE" = nerf_rays ] || [ "$MODE" = nerf_input_grad ]; then
+if [ "$MODE" = gs_features ]; then
+prof 400 $O/gs_features_stats.log --kernel-trace --stats --output-format csv -d $O/gs_features_stats -- python3 $R/tools/bench_gs_features.py 9
+for set in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_WAVE_CYCLES GRBM_GUI_ACTIVE"; do
+  tag=$(echo $set | tr ' ' '_' | cut -c1-32)
+  prof 400 $O/pmcgs_feat_$tag.log --pmc $set --kernel-trace --kernel-include-regex "k_render_features" --output-format csv -d $O/pmcgs_feat_$tag -- python3 $R/tools/bench_gs_features.py 9
+done
+fi
+if [ "$MODE" = nerf ] || [ "$MODE" = nerf_train ] || [ "$MODE" = nerf_rays ] || [ "$MODE" = nerf_input_grad ] || [ "$MODE" = gs_features ]; then
 find $O -name "*.db" -delete; find $O -name "*_agent_info.csv" -delete; find $O -path "*_stats/*" -name "*kernel_trace.csv" -delete; du -sh $O; [ -f $O/bench_stats.log ] && tail -5 $O/bench_stats.log
 exit 0
 fi
