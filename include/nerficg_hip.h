@@ -52,8 +52,9 @@ enum {
  * unchanged;
  * 19 = group 20 (the vanilla NeRF path's gradients to sample positions, viewing directions and rays) is new, every earlier signature is unchanged;
  * 20 = group 21 (nrc_gs_render_features_band / nrc_gs_backward_features_band: N-channel per-Gaussian features blended by the rasterizer's weights) is new,
- * every earlier signature is unchanged. */
-#define NRC_ABI_VERSION 20
+ * every earlier signature is unchanged;
+ * 21 = group 22 (nrc_gs_contributions_band: per-Gaussian contribution statistics of a rendered view) is new, every earlier signature is unchanged. */
+#define NRC_ABI_VERSION 21
 /* library identification; also used by the loader's symbol check */
 int nrc_abi_version(void);
 const char* nrc_build_info(void);
@@ -1253,6 +1254,33 @@ int nrc_gs_backward_features_band(int32_t P, int32_t C, int32_t W, int32_t H, co
                                   const float* splat_records, const uint32_t* tile_order, const uint32_t* n_contrib, const float* final_T,
                                   const float* dL_dfeature_map, float* dL_dfeatures, float* grad_records, int32_t records_clear, int32_t tile_row_begin,
                                   int32_t n_tile_rows, nrc_stream_t stream);
+
+/* =====================================================================================================
+ * Group 22 -- per-Gaussian contribution statistics of a rendered 3DGS view (csrc/gs_contrib.hip).  No reference counterpart: the upstream rasterizer reports
+ *            per pixel only.  The call stands in for what the compaction and scoring methods built on 3DGS each patch into their own rasterizer fork: the
+ *            maximum blending weight over the training views (RadSplat pruning), hit counts and importance sums (LightGaussian, Mini-Splatting),
+ *            error-weighted scores for densification (Taming-3DGS), sensitivity pruning (PUP 3D-GS) and the removal of Gaussians no view sees.  It runs on the
+ *            state a colour forward of group 4 left behind (point_list, ranges, splat_records, tile_order = the tile_fill of nrc_gs_bin_render*, n_contrib)
+ *            for the same P, W, H and band: no preprocess, no sort, no binning, one launch (k_gs_contributions).  Nothing here is differentiable.
+ *
+ *   The blended set of a pixel p and the weights are the colour pass's own, as in group 21: the entries k <= n_contrib[p] of the tile's list with
+ *            !(power > 0) and alpha >= 1/255, alpha = min(0.99, o exp(power)) in k_render's statements, T <- fmaf(-T, alpha, T), w_i = alpha_i T_i -- bit for
+ *            bit the weight the colour received.
+ *   pixel_weights (H * W) f32, finite, or NULL (= 1 everywhere): the map m.  A pixel PARTICIPATES iff m(p) != 0.  Only the band's pixel rows are read.
+ *   weight_sum (P) f32:  weight_sum[i] += sum over the participating pixels that blended i of m(p) w_i(p), accumulated in f32 (DPP row sums, LDS float atomics
+ *            across a tile's blocks, one global float atomic per (tile, Gaussian): two runs agree to rounding, not bitwise).
+ *   weight_max (P) f32:  weight_max[i] = max(weight_max[i], largest w_i(p) over the participating pixels that blended i): the colour's w, no rounding added.
+ *            Compared as bit patterns: the buffer must hold values >= 0 (zeros, or an earlier call's maxima).
+ *   hits (P) int32:      hits[i] += number of participating pixels that blended i, exact.
+ *   All three ACCUMULATE into the caller's buffers (one call per view gives multi-view statistics); clear != 0 zeroes the wanted ones first.  Any of the three
+ *            may be NULL (not wanted), not all three.  Gaussians outside every list are untouched.  The bands of a partition add up to the frame.
+ *   P == 0: NRC_OK, no launch.  The call neither synchronises the host nor reads anything back: it works inside a stream capture.  NRC_ERR_INVALID before any
+ *            HIP call: a band that nrc_gs_*_band refuses; P < 0, W < 1, H < 1; a null point_list or splat_records with P > 0; a null ranges, tile_order or
+ *            n_contrib; all three outputs null; splat_records not 16-byte aligned; pixel_weights or an output not 4-byte aligned.
+ * ===================================================================================================== */
+int nrc_gs_contributions_band(int32_t P, int32_t W, int32_t H, const int32_t* point_list, const uint32_t* ranges, const float* splat_records,
+                              const uint32_t* tile_order, const uint32_t* n_contrib, const float* pixel_weights, float* weight_sum, float* weight_max,
+                              int32_t* hits, int32_t clear, int32_t tile_row_begin, int32_t n_tile_rows, nrc_stream_t stream);
 
 #ifdef __cplusplus
 }

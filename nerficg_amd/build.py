@@ -34,6 +34,9 @@ PER_FILE_FLAGS = {
     # gs_raster.hip's flags, all three: the feature pass recomputes the colour pass's alpha with the same statements (csrc/gs_blend.h) and must get the same
     # bits, and its per-Gaussian sums meet in LDS through float atomics that the atomic optimizer would rewrite into wave-reduction loops
     'gs_features.hip': ['-ffp-contract=off', '-fno-slp-vectorize', '-mllvm', '-amdgpu-atomic-optimizer-strategy=None'],
+    # gs_raster.hip's flags, all three, for the same two reasons: the contribution pass recomputes the colour pass's alpha (csrc/gs_blend.h) and reports
+    # w = alpha T itself as weight_max, and one lane per DPP row adds to LDS words that the atomic optimizer would turn into wave-reduction loops
+    'gs_contrib.hip': ['-ffp-contract=off', '-fno-slp-vectorize', '-mllvm', '-amdgpu-atomic-optimizer-strategy=None'],
     # no SLP vectoriser either: packed f32 VALU next to MFMAs is priced above its issue slot on this chip (MI355X_MICROARCH.md), and the packing
     # costs v_mov: k_nwie_bwd 2 641 -> 2 451 vector instructions, k_gb_split 3 015 -> 2 853; the fused training iteration -1 %, the image path unchanged
     'ngp_net.hip': ['-fno-slp-vectorize'],

@@ -78,6 +78,7 @@ def _camera_block(rs, dev) -> torch.Tensor:
 
 _FIXED_CAPACITY: tuple[int, int] | None = None
 _LAST_COUNTS: torch.Tensor | None = None
+_FRAME_STATE_SINK: list = [None]   # a list while a GaussianRasterizer.forward is running: the forward appends the frame state that contributions() reads
 
 
 @contextlib.contextmanager
@@ -349,6 +350,8 @@ class _RasterizeGaussians(torch.autograd.Function):
             b0, bn = band if band is not None else (0, gy)
             _lib.check(lib.nrc_gs_render_features_band(P, C_f, W, H, _lib.ptr(feat_c), _lib.ptr(point_list), _lib.ptr(ranges), _lib.ptr(splat), _lib.ptr(tile_fill),
                                                        _lib.ptr(n_contrib), b0, bn, _lib.ptr(feature_map), st), 'gs_render_features_band')
+        if _FRAME_STATE_SINK[0] is not None:   # GaussianRasterizer.forward is the caller: what contributions() runs on (references only, nothing is created for it)
+            _FRAME_STATE_SINK[0].append(dict(point_list=point_list, ranges=ranges, splat=splat, tile_fill=tile_fill, n_contrib=n_contrib, dims=(P, W, H), band=band))
         ctx.features = feat_c
         ctx.features_grad = feat_c is not None and bool(ctx.needs_input_grad[17])
         ctx.band = band
@@ -569,6 +572,69 @@ class GaussianRasterizer(torch.nn.Module):
     def __init__(self, raster_settings: GaussianRasterizationSettings) -> None:
         super().__init__()
         self.raster_settings = raster_settings
+        self._frame_state = None   # of this object's most recent forward call: see contributions()
+
+    def release_state(self) -> None:
+        """Drops the references to the most recent forward's frame state (tile lists, ranges, splat records, tile order, n_contrib) that contributions() reads."""
+        self._frame_state = None
+
+    def contributions(self, pixel_weights=None, *, out=None, weight_sum=True, weight_max=True, hits=True, clear=False):
+        """Per-Gaussian contribution statistics of the view THIS OBJECT'S MOST RECENT forward call rendered (C ABI group 22, csrc/gs_contrib.hip): what pruning
+        and scoring methods ask of a view -- RadSplat's maximum blending weight, the hit counts and importance sums of LightGaussian / Mini-Splatting,
+        error-weighted scores as in Taming-3DGS, or simply which Gaussians no view sees.  That call may have been a training call or one under torch.no_grad(), a whole
+        frame or a `tile_rows` band (the band's pixels only: the bands of a partition add up to the frame).  One launch on the state the colour pass left; no
+        preprocess, sort or binning; nothing is differentiable and nothing any other call returns changes.
+        With the colour pass's own blended set and weights w_i(p) = alpha_i T_i (bit for bit) and m = `pixel_weights`, an (H, W) float32 CUDA tensor of finite
+        values (None: 1 everywhere), a pixel PARTICIPATES iff m(p) != 0, and per Gaussian i
+            'weight_sum' (P,) float32   += sum over the participating pixels that blended i of m(p) w_i(p)       (f32 sums: two runs agree to rounding)
+            'weight_max' (P,) float32    = max(itself, the largest such w_i(p))                                  (exact: the colour's w)
+            'hits'       (P,) int32     += the number of such pixels                                             (exact)
+        Returns a dict of the requested statistics (`weight_sum`, `weight_max`, `hits` = False leaves one out; not all three).  `out`: a dict an earlier call
+        returned, for the same P and device -- the call ACCUMULATES into its tensors (one call per view gives the multi-view statistics) and returns it;
+        `clear=True` zeroes the requested ones first.  Gaussians outside every tile list are untouched.  It is a second call, not a forward argument, so that m
+        can be computed from the rendered image: render -> m from the image -> contributions(m).
+        The forward keeps references to point_list, ranges, the splat records, the tile order and n_contrib on this object (tensors it creates anyway): they
+        stay alive until the next forward call of this object or release_state().  RuntimeError naming the problem: no forward call yet, `pixel_weights` of a wrong
+        shape, dtype or device, an `out` that does not match."""
+        state = self._frame_state
+        if state is None:
+            raise RuntimeError('contributions: this rasterizer object has not rendered anything yet (or release_state() was called) -- call it after a forward call')
+        wanted = [k for k, on in (('weight_sum', weight_sum), ('weight_max', weight_max), ('hits', hits)) if on]
+        if not wanted:
+            raise RuntimeError('contributions: at least one of weight_sum, weight_max and hits must be requested')
+        P, W, H = state['dims']
+        dev = state['n_contrib'].device
+        dtypes = dict(weight_sum=torch.float32, weight_max=torch.float32, hits=torch.int32)
+        m = None
+        if pixel_weights is not None:
+            if not torch.is_tensor(pixel_weights) or not pixel_weights.is_cuda or pixel_weights.device != dev:
+                raise RuntimeError(f'contributions: pixel_weights must be a CUDA tensor on the device of the rendered frame ({dev}), got '
+                                   f'{pixel_weights.device if torch.is_tensor(pixel_weights) else type(pixel_weights).__name__}')
+            if pixel_weights.dtype != torch.float32:
+                raise RuntimeError(f'contributions: pixel_weights must have dtype torch.float32, got {pixel_weights.dtype}')
+            if tuple(pixel_weights.shape) != (H, W):
+                raise RuntimeError(f'contributions: pixel_weights must have shape (H, W) = ({H}, {W}), got {tuple(pixel_weights.shape)}')
+            m = pixel_weights.detach().contiguous()
+        fresh = out is None
+        if fresh:
+            out = {k: torch.empty(P, dtype=dtypes[k], device=dev) for k in wanted}
+        else:
+            if not isinstance(out, dict):
+                raise RuntimeError(f'contributions: out must be a dict an earlier call returned, got {type(out).__name__}')
+            for k in wanted:
+                t = out.get(k)
+                if not torch.is_tensor(t):
+                    raise RuntimeError(f'contributions: out has no tensor {k!r} (request the same statistics as the call that made it)')
+                if tuple(t.shape) != (P,) or t.dtype != dtypes[k] or t.device != dev or not t.is_contiguous():
+                    raise RuntimeError(f'contributions: out[{k!r}] must be a contiguous ({P},) {dtypes[k]} tensor on {dev}, got {tuple(t.shape)} {t.dtype} on {t.device}')
+        if P > 0:
+            band = state['band'] if state['band'] is not None else (0, (H + 15) // 16)
+            lib = _lib.load()
+            get = lambda k: _lib.ptr(out[k]) if k in wanted else None
+            _lib.check(lib.nrc_gs_contributions_band(P, W, H, _lib.ptr(state['point_list']), _lib.ptr(state['ranges']), _lib.ptr(state['splat']), _lib.ptr(state['tile_fill']),
+                                                     _lib.ptr(state['n_contrib']), _lib.ptr(m), get('weight_sum'), get('weight_max'), get('hits'), int(fresh or clear),
+                                                     band[0], band[1], _lib.stream_of(state['n_contrib'])), 'gs_contributions_band')
+        return out
 
     def markVisible(self, positions: torch.Tensor) -> torch.Tensor:
         """Frustum test of the upstream rasterizer: view-space z > 0.2."""
@@ -614,6 +680,14 @@ class GaussianRasterizer(torch.nn.Module):
         if ((scales is None or rotations is None) and cov3D_precomp is None) or ((scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
         empty = torch.Tensor([])
-        return rasterize_gaussians(means3D, means2D, empty if shs is None else shs, empty if colors_precomp is None else colors_precomp, opacities,
-                                   empty if scales is None else scales, empty if rotations is None else rotations,
-                                   empty if cov3D_precomp is None else cov3D_precomp, self.raster_settings, shs_rest, raw_parameters, rest_step, tile_rows, return_depth_alpha, camera_grad, features)
+        self._frame_state = None
+        sink: list = []
+        previous, _FRAME_STATE_SINK[0] = _FRAME_STATE_SINK[0], sink
+        try:
+            out = rasterize_gaussians(means3D, means2D, empty if shs is None else shs, empty if colors_precomp is None else colors_precomp, opacities,
+                                      empty if scales is None else scales, empty if rotations is None else rotations,
+                                      empty if cov3D_precomp is None else cov3D_precomp, self.raster_settings, shs_rest, raw_parameters, rest_step, tile_rows, return_depth_alpha, camera_grad, features)
+        finally:
+            _FRAME_STATE_SINK[0] = previous
+        self._frame_state = sink[-1] if sink else None   # what contributions() runs on: references to tensors the forward created anyway
+        return out

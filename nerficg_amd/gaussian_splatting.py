@@ -409,6 +409,47 @@ class Gaussians(torch.nn.Module):
         self.n_observations = n_obs.view(torch.int32)
 
     @torch.no_grad()
+    def prune_by_contribution(self, stats: dict, min_weight_max: float | None = None, min_hits: int | None = None,
+                              keep_fraction: float | None = None) -> dict[str, int]:
+        """Removes the Gaussians that the statistics of accumulate_contributions (or GaussianRasterizer.contributions) score low, through prune_points, so the
+        optimizer state follows as it does for densification.  A Gaussian goes when ANY given criterion says so:
+            min_weight_max   its largest blending weight over the views is below the threshold (RadSplat prunes at 0.01 .. 0.25);
+            min_hits         fewer pixels than this blended it (min_hits=1: nothing ever saw it);
+            keep_fraction    it is outside the top ceil(keep_fraction P) by 'weight_sum' (the importance sum; with an error map as pixel weights, an
+                             error-weighted score): the k-th value is taken with torch.kthvalue on the device and ties at the threshold are kept.
+        Returns {'pruned': n, 'kept': n}.  ValueError: no criterion, a keep_fraction outside [0, 1], a statistic a criterion needs is missing, or `stats`
+        belongs to another number of Gaussians."""
+        if min_weight_max is None and min_hits is None and keep_fraction is None:
+            raise ValueError('prune_by_contribution: give at least one of min_weight_max, min_hits and keep_fraction')
+        P, dev = self._positions.shape[0], self._positions.device
+        needed = [k for k, v in (('weight_max', min_weight_max), ('hits', min_hits), ('weight_sum', keep_fraction)) if v is not None]
+        for k in needed:
+            t = stats.get(k)
+            if not torch.is_tensor(t):
+                raise ValueError(f'prune_by_contribution: stats has no {k!r}, which the given criterion needs')
+            if tuple(t.shape) != (P,):
+                raise ValueError(f'prune_by_contribution: stats[{k!r}] has shape {tuple(t.shape)}, the model holds {P} Gaussians -- statistics of another model state')
+        prune = torch.zeros(P, dtype=torch.bool, device=dev)
+        if min_weight_max is not None:
+            prune |= stats['weight_max'].to(dev) < float(min_weight_max)
+        if min_hits is not None:
+            prune |= stats['hits'].to(dev) < int(min_hits)
+        if keep_fraction is not None:
+            if not 0.0 <= float(keep_fraction) <= 1.0:
+                raise ValueError(f'prune_by_contribution: keep_fraction = {keep_fraction}, a fraction in [0, 1] is needed')
+            n_keep = min(P, int(np.ceil(float(keep_fraction) * P)))
+            if n_keep == 0:
+                prune |= True
+            elif n_keep < P:
+                score = stats['weight_sum'].to(dev)
+                threshold = torch.kthvalue(score, P - n_keep + 1).values      # the n_keep-th largest; stays on the device
+                prune |= score < threshold
+        n_pruned = int(prune.sum())
+        if n_pruned > 0:
+            self.prune_points(prune)
+        return {'pruned': n_pruned, 'kept': P - n_pruned}
+
+    @torch.no_grad()
     def add_densification_stats(self, viewspace_point_tensor: torch.Tensor, visibility: torch.Tensor) -> None:
         """Model.py:243-246.  `visibility`: the rasterizer's int32 radii (used as they are) or the boolean mask radii > 0."""
         from . import _lib
@@ -758,7 +799,7 @@ class _TrainingOutputs(dict):
 @torch.no_grad()
 def render_image_inference(gaussians: Gaussians, cam: PerspectiveCamera, c2w: np.ndarray, scale_modifier: float = 1.0, to_chw: bool = False,
                            use_baked_covariance: bool = True, band: tuple[int, int] | None = None, depth_alpha: bool = False,
-                           features: torch.Tensor | None = None):
+                           features: torch.Tensor | None = None, _rasterizer_out: list | None = None):
     """features: a (P, C) float32 tensor of the caller's; the outputs gain 'features', the map blended with the colour's weights (the rasterizer's `features`),
     (H, W, C) or (C, H, W) with to_chw.  depth_alpha: the outputs gain 'alpha' (1 - T of the blend) and 'depth' (accumulated view-space depth / (alpha + 1e-6)), (H, W, 1) or (1, H, W) with to_chw, as
     instant_ngp.render_image returns them.  band = (tile_row_begin, n_tile_rows): only that band of tile rows of the frame is rendered (zero elsewhere; parallel.gather_band_images composes the
@@ -784,7 +825,35 @@ def render_image_inference(gaussians: Gaussians, cam: PerspectiveCamera, c2w: np
         outputs.update(_depth_alpha_outputs(aux[0], aux[1], to_chw))
     if features is not None:
         outputs['features'] = aux[-1] if to_chw else aux[-1].permute(1, 2, 0)
+    if _rasterizer_out is not None:   # accumulate_contributions: the object that holds this frame's state
+        _rasterizer_out.append(rasterizer)
     return outputs
+
+
+@torch.no_grad()
+def accumulate_contributions(gaussians: Gaussians, views, pixel_weights=None) -> dict:
+    """Per-Gaussian contribution statistics over a set of views (GaussianRasterizer.contributions, C ABI group 22), the input of
+    Gaussians.prune_by_contribution: every view is rendered through render_image_inference (no autograd state) and scored with one more launch.
+    views: an iterable of (cam, c2w).  pixel_weights: None (every pixel counts 1), a sequence with one (H, W) float32 map per view, or a callable
+    (image (3, H, W), index) -> map, e.g. a per-pixel error against the view's target; a pixel whose weight is 0 does not take part.
+    Returns {'weight_sum', 'weight_max' (P,) float32, 'hits' (P,) int32, 'n_views': int}: the sum of m w, the largest blending weight and the number of
+    pixels that blended each Gaussian, over all views."""
+    stats, n_views = None, 0
+    for index, (cam, c2w) in enumerate(views):
+        holder: list = []
+        image = render_image_inference(gaussians, cam, c2w, to_chw=True, _rasterizer_out=holder)['rgb']
+        if callable(pixel_weights):
+            m = pixel_weights(image, index)
+        else:
+            m = None if pixel_weights is None else pixel_weights[index]
+        stats = holder[0].contributions(m, out=stats)
+        holder[0].release_state()
+        n_views += 1
+    if stats is None:
+        P, dev = gaussians.get_positions.shape[0], gaussians.get_positions.device
+        stats = dict(weight_sum=torch.zeros(P, device=dev), weight_max=torch.zeros(P, device=dev), hits=torch.zeros(P, dtype=torch.int32, device=dev))
+    stats['n_views'] = n_views
+    return stats
 
 
 FUSED_PHOTOMETRIC_LOSS = True   # training_loss as one node (nerficg_amd.fused_ssim.photometric_loss); False: l1_loss + fused_ssim as tensor operations

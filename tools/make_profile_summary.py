@@ -60,6 +60,9 @@ if ntstats:
 nrstats = sorted(glob.glob(str(RAW / 'nerf_rays_stats' / '*' / '*kernel_stats.csv')), key=os.path.getmtime)   # tools/bench_nerf_rays.py: the NeRF ray stages and the torch operators
 if nrstats:
     shutil.copy(nrstats[-1], OUT / f'{ROUND}_nerf_rays_kernel_stats.csv')
+gcstats = sorted(glob.glob(str(RAW / 'gs_contrib_stats' / '*' / '*kernel_stats.csv')), key=os.path.getmtime)   # tools/bench_gs_contributions.py: the contribution pass, the frame, the detour
+if gcstats:
+    shutil.copy(gcstats[-1], OUT / f'{ROUND}_gs_contributions_kernel_stats.csv')
 nistats = sorted(glob.glob(str(RAW / 'nerf_input_grad_stats' / '*' / '*kernel_stats.csv')), key=os.path.getmtime)   # tools/bench_nerf_input_grad.py: a pose-refinement iteration
 if nistats:
     shutil.copy(nistats[-1], OUT / f'{ROUND}_nerf_input_grad_kernel_stats.csv')
@@ -81,7 +84,7 @@ for k in names:
     for n, vals in src[k].items():
         acc[k][n] = vals
 keep = ('k_grid_encode', 'k_ngp_mlp', 'k_render', 'k_composite_image', 'k_preprocess', 'k_span_', 'k_item_', 'k_depth_keys', 'k_radix_', 'k_scan_tiles', 'k_march_wave',
-        'k_grid_bwd', 'k_nwie_', 'k_composite_train', 'k_gb_', 'k_train_', 'k_amp_', 'k_adam', 'k_nerf_')
+        'k_grid_bwd', 'k_nwie_', 'k_composite_train', 'k_gb_', 'k_train_', 'k_amp_', 'k_adam', 'k_nerf_', 'k_gs_contributions')
 lines = [f'# rocprofv3 --pmc summary (MI355X, {ROUND})', '',
          'Collected by `tools/collect_profiles.sh` (one `--pmc` group per run, `--kernel-trace` only), averaged per kernel over all launches of',
          '`tools/bench_query.py` (InstantNGP 800x800 image pipeline), `tools/bench_gs.py` (3DGS, 1 M Gaussians, 1297x840) and `tools/bench_train.py`',
