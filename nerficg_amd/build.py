@@ -21,6 +21,13 @@ ARCH = 'gfx950'
 
 COMMON_FLAGS = ['-O3', '-fPIC', f'--offload-arch={ARCH}', '-std=c++17', '-Wall', '-Wno-unused-function',
                 '-Wno-unused-result', '-Wno-unused-value', '-fno-gpu-rdc', '-DNDEBUG']
+# The translation units that include csrc/gs_blend.h get ONE flag list: the feature and contribution passes recompute the colour pass's alpha with the
+# header's statements and must get the same bits (weight_max is w = alpha T itself).
+#   no FMA contraction: see below
+#   no SLP vectoriser: it packs the blend arithmetic of two list entries into v_pk_* and pays in v_mov (the blend states its own pairs: blend_power)
+#   no atomic optimizer: it rewrites the one-lane LDS atomics of k_render_bw, and the per-row LDS float atomics of the two other passes, into
+#   15-instruction wave-reduction loops
+GS_BLEND_FLAGS = ['-ffp-contract=off', '-fno-slp-vectorize', '-mllvm', '-amdgpu-atomic-optimizer-strategy=None']
 # translation units whose f32 arithmetic decides integer indices: no FMA contraction (bit-exact vs oracle/)
 PER_FILE_FLAGS = {
     'ngp_march.hip': ['-ffp-contract=off'],
@@ -28,15 +35,9 @@ PER_FILE_FLAGS = {
     'knn.hip': ['-ffp-contract=off'],
     'gs_densify.hip': ['-ffp-contract=off'],   # thresholds decide the row list: same f32 sequence as oracle/gs_densify.py   # squared distances decide the neighbour set: same f32 sequence as oracle/knn_oracle.c
   # HBM-bound anyway; keeps the update bit-identical to oracle/adam_oracle.c
-    # + no atomic optimizer: it rewrites the one-lane LDS atomics of k_render_bw into 15-instruction wave-reduction loops
-    # + no SLP vectoriser: it packs the blend arithmetic of two list entries into v_pk_* and pays in v_mov (the blend states its own pairs: blend_power)
-    'gs_raster.hip': ['-ffp-contract=off', '-fno-slp-vectorize', '-mllvm', '-amdgpu-atomic-optimizer-strategy=None'],
-    # gs_raster.hip's flags, all three: the feature pass recomputes the colour pass's alpha with the same statements (csrc/gs_blend.h) and must get the same
-    # bits, and its per-Gaussian sums meet in LDS through float atomics that the atomic optimizer would rewrite into wave-reduction loops
-    'gs_features.hip': ['-ffp-contract=off', '-fno-slp-vectorize', '-mllvm', '-amdgpu-atomic-optimizer-strategy=None'],
-    # gs_raster.hip's flags, all three, for the same two reasons: the contribution pass recomputes the colour pass's alpha (csrc/gs_blend.h) and reports
-    # w = alpha T itself as weight_max, and one lane per DPP row adds to LDS words that the atomic optimizer would turn into wave-reduction loops
-    'gs_contrib.hip': ['-ffp-contract=off', '-fno-slp-vectorize', '-mllvm', '-amdgpu-atomic-optimizer-strategy=None'],
+    'gs_raster.hip': GS_BLEND_FLAGS,
+    'gs_features.hip': GS_BLEND_FLAGS,
+    'gs_contrib.hip': GS_BLEND_FLAGS,
     # no SLP vectoriser either: packed f32 VALU next to MFMAs is priced above its issue slot on this chip (MI355X_MICROARCH.md), and the packing
     # costs v_mov: k_nwie_bwd 2 641 -> 2 451 vector instructions, k_gb_split 3 015 -> 2 853; the fused training iteration -1 %, the image path unchanged
     'ngp_net.hip': ['-fno-slp-vectorize'],

@@ -3,8 +3,8 @@
 //
 // The pass runs on the state a colour forward left behind (tile lists, tile order, splat records, n_contrib): no preprocess, no sort, no binning.  For a pixel p the
 // blended set and the weights are the colour pass's own, as gs_features.hip states them: the entries k <= n_contrib[p] of the tile's list with !(power > 0) and
-// alpha >= 1/255, alpha = min(0.99, o exp_blend(blend_power(...))), T <- fmaf(-T, alpha, T), w = alpha T.  The alpha statements are the colour blend's (gs_blend.h) and
-// this translation unit is built with gs_raster.hip's flags, so w is the colour's weight bit for bit.  With m the caller's per-pixel map (1 without one) a pixel
+// alpha >= 1/255, alpha = min(0.99, o exp_blend(blend_power(...))), T <- fmaf(-T, alpha, T), w = alpha T.  The alpha statements are the colour blend's own (gs_blend.h: the
+// one definition gs_raster.hip includes too; replay_pack) under the one flag list of the three translation units (build.py), so w is the colour's weight bit for bit.  With m the caller's per-pixel map (1 without one) a pixel
 // PARTICIPATES iff m(p) != 0, and for every Gaussian i
 //     weight_sum[i] += sum_{p participates, i blended at p} m(p) w_i(p)        (f32)
 //     weight_max[i]  = max(weight_max[i], max_{p participates, i blended at p} w_i(p))     (the colour's w, no rounding added)
@@ -41,24 +41,17 @@ __global__ void __launch_bounds__(256) k_gs_contributions(int W, int H, int gx, 
     __shared__ uint32_t s_max[BATCH];     //                                              max w, as its bit pattern
     __shared__ int s_hits[BATCH];         //                                              blending pixels
     const int tile = (int)tile_order[blockIdx.x];
-    const int tile_x = tile % gx, tile_y = tile / gx;
-    const int px = tile_x * TILE + tile_px(threadIdx.x), py = tile_y * TILE + tile_py(threadIdx.x);
-    const bool inside = px < W && py < H;
-    const float fx = (float)px, fy = (float)py;
-    const float tx0 = (float)(tile_x * TILE), ty0 = (float)(tile_y * TILE);
-    const int block = threadIdx.x >> 4;
+    const TilePixel tp(tile, gx, W, H);
     const int row_shift = (int)(threadIdx.x & 48u);   // this row's 16 bits of the wave's ballot
     const bool row_lead = (threadIdx.x & 15u) == 0u;
     const uint32_t r0 = ranges[2 * tile], r1 = ranges[2 * tile + 1];
-    const size_t pix = (size_t)py * W + px;
-    const float m = inside ? (pixel_weights ? pixel_weights[pix] : 1.0f) : 0.f;
-    const uint32_t last = (inside && m != 0.f) ? n_contrib[pix] : 0u;   // a pixel that does not participate blends nothing here
+    const size_t pix = (size_t)tp.py * W + tp.px;
+    const float m = tp.inside ? (pixel_weights ? pixel_weights[pix] : 1.0f) : 0.f;
+    const uint32_t last = (tp.inside && m != 0.f) ? n_contrib[pix] : 0u;   // a pixel that does not participate blends nothing here
     float T = 1.0f;
-    const uint2* list4 = reinterpret_cast<const uint2*>(st.list[block]);
-    // as in the feature pass's forward kernel: what a row past the end of its list can pick up through a stale offset must be finite (it meets a weight of exactly 0) and addressable
-    st.a[threadIdx.x] = make_float4(0.f, 0.f, 0.f, 0.f); st.b[threadIdx.x] = make_float4(0.f, 0.f, 0.f, 0.f);
-    reinterpret_cast<uint4*>(&st.list[0][0])[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
-    reinterpret_cast<uint4*>(&st.list[0][0])[256 + threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
+    const uint2* list4 = reinterpret_cast<const uint2*>(st.list[tp.block]);
+    stage_clear_records(st);
+    stage_clear_lists(st);
     s_sum[threadIdx.x] = 0.f; s_max[threadIdx.x] = 0u; s_hits[threadIdx.x] = 0;
     for (uint32_t base = r0; base < r1; base += BATCH) {
         if (__syncthreads_count(base - r0 < last) == 0) break;   // no participating pixel of the tile blended anything this far back
@@ -67,7 +60,7 @@ __global__ void __launch_bounds__(256) k_gs_contributions(int W, int H, int gx, 
         int id = 0;
         if (k < r1) {
             id = point_list[k];
-            flags = stage_entry<false>(st, splat, id, tx0, ty0);
+            flags = stage_entry<false>(st, splat, id, tp.tx0, tp.ty0);
         }
         int n_wave;
         const int n_mine = block_lists(st, flags, &n_wave);
@@ -75,18 +68,10 @@ __global__ void __launch_bounds__(256) k_gs_contributions(int W, int H, int gx, 
         for (int jj = 0; jj < n_wave; jj += 4) {
             const uint2 pack = list4[jj >> 2];
             int off[4];   // 16 j
-            off[0] = (int)(pack.x & 0xffffu); off[1] = (int)(pack.x >> 16); off[2] = (int)(pack.y & 0xffffu); off[3] = (int)(pack.y >> 16);
+            unpack_offsets(pack, off);
             float alpha[4];
             bool ok[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const float4 a_j = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(st.a) + off[u]);
-                const float4 b_j = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(st.b) + off[u]);
-                const v2f d = (v2f){a_j.x, a_j.y} - (v2f){fx, fy};
-                const float power = blend_power((v2f){b_j.x, b_j.y}, b_j.z, d);
-                alpha[u] = fminf(0.99f, b_j.w * exp_blend(power));
-                ok[u] = (jj + u < n_mine) & (pos0 + ((uint32_t)off[u] >> 4) <= last) & !(power > 0.0f) & !(alpha[u] < 1.0f / 255.0f);
-            }
+            replay_pack(st, off, jj, n_mine, pos0, last, tp.fx, tp.fy, alpha, ok);
             if (__ballot(ok[0] | ok[1] | ok[2] | ok[3]) == 0ull) continue;   // wave-uniform
 #pragma unroll
             for (int u = 0; u < 4; u++) {
@@ -119,17 +104,12 @@ __global__ void __launch_bounds__(256) k_gs_contributions(int W, int H, int gx, 
     }
 }
 
-// the band rule and the null / alignment checks of gs_features.hip's features_args_ok, for this group's arguments
+// the saved state (gs_blend.h), at least one statistic asked for, and 4-byte alignment of this group's own arrays
 bool contributions_args_ok(int32_t P, int32_t W, int32_t H, const int32_t* point_list, const uint32_t* ranges, const float* splat_records, const uint32_t* tile_order,
                            const uint32_t* n_contrib, const float* pixel_weights, const float* weight_sum, const float* weight_max, const int32_t* hits,
                            int32_t tile_row_begin, int32_t n_tile_rows) {
-    if (H < 1 || tile_row_begin < 0 || n_tile_rows < 1) return false;
-    if ((int64_t)tile_row_begin + n_tile_rows > (int64_t)((H + TILE - 1) / TILE)) return false;
-    if (P < 0 || W < 1) return false;
-    if (!ranges || !tile_order || !n_contrib) return false;
-    if (P > 0 && (!point_list || !splat_records)) return false;
+    if (!gs_saved_state_ok(P, W, H, point_list, ranges, splat_records, tile_order, n_contrib, tile_row_begin, n_tile_rows)) return false;
     if (!weight_sum && !weight_max && !hits) return false;
-    if (reinterpret_cast<uintptr_t>(splat_records) & 15u) return false;
     if ((reinterpret_cast<uintptr_t>(pixel_weights) | reinterpret_cast<uintptr_t>(weight_sum) | reinterpret_cast<uintptr_t>(weight_max) | reinterpret_cast<uintptr_t>(hits)) & 3u)
         return false;
     return true;

@@ -3,8 +3,9 @@
 // A feature pass runs on the state a colour forward left behind (tile lists, tile order, splat records, n_contrib, final_T): no preprocess, no sort,
 // no binning.  For a pixel p the blended set and the weights are the colour pass's own: the entries k <= n_contrib[p] of the tile's list with
 // !(power > 0) and alpha >= 1/255, alpha = min(0.99, o exp_blend(blend_power(...))), T <- fmaf(-T, alpha, T), w = alpha T; the map is
-// F_c = fmaf(f_c, w, F_c) in list order, background 0, not normalised.  The alpha statements are the colour blend's (gs_blend.h) and this translation unit is built
-// with gs_raster.hip's flags, so w is the colour's weight bit for bit -- a feature column that holds a colour gives that colour's plane (bg = 0) bitwise.
+// F_c = fmaf(f_c, w, F_c) in list order, background 0, not normalised.  The alpha statements are the colour blend's own -- gs_blend.h holds the one definition that
+// gs_raster.hip includes too, the forward kernel walks a batch through its replay_pack -- and the three translation units share one flag list (build.py), so w is
+// the colour's weight bit for bit: a feature column that holds a colour gives that colour's plane (bg = 0) bitwise.
 //
 //   k_render_features<CH>     one workgroup per (tile of the band in tile_order, chunk of CH channels); the per-4x4-block work lists of the colour blend; a batch's
 //                             256 x CH features staged in LDS (16 KB at CH = 16, read back as 16-byte vectors); alpha once per entry, CH multiply-adds.
@@ -55,33 +56,26 @@ __global__ void __launch_bounds__(256) k_render_features(int W, int H, int gx, i
     const int tile = (int)tile_order[blockIdx.x];
     const int c0 = (int)blockIdx.y * CH;
     const int nch = min(CH, C - c0);
-    const int tile_x = tile % gx, tile_y = tile / gx;
-    const int px = tile_x * TILE + tile_px(threadIdx.x), py = tile_y * TILE + tile_py(threadIdx.x);
-    const bool inside = px < W && py < H;
-    const float fx = (float)px, fy = (float)py;
-    const float tx0 = (float)(tile_x * TILE), ty0 = (float)(tile_y * TILE);
-    const int block = threadIdx.x >> 4;
+    const TilePixel tp(tile, gx, W, H);
     const uint32_t r0 = ranges[2 * tile], r1 = ranges[2 * tile + 1];
-    const size_t pix = (size_t)py * W + px, hw = (size_t)H * W;
-    const uint32_t last = inside ? n_contrib[pix] : 0u;   // contributor number of the last entry the colour pass blended here
+    const size_t pix = (size_t)tp.py * W + tp.px, hw = (size_t)H * W;
+    const uint32_t last = tp.inside ? n_contrib[pix] : 0u;   // contributor number of the last entry the colour pass blended here
     float T = 1.0f;
     float F[CH];
 #pragma unroll
     for (int k = 0; k < CH; k++) F[k] = 0.f;
-    const uint2* list4 = reinterpret_cast<const uint2*>(st.list[block]);
-    // as in the colour blend: what a row past the end of its list can pick up through a stale offset must be finite (it meets a weight of exactly 0) and addressable
-    st.a[threadIdx.x] = make_float4(0.f, 0.f, 0.f, 0.f); st.b[threadIdx.x] = make_float4(0.f, 0.f, 0.f, 0.f);
+    const uint2* list4 = reinterpret_cast<const uint2*>(st.list[tp.block]);
+    stage_clear_records(st);
 #pragma unroll
-    for (int g = 0; g < CH / 4; g++) s_f[threadIdx.x][g] = make_float4(0.f, 0.f, 0.f, 0.f);
-    reinterpret_cast<uint4*>(&st.list[0][0])[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
-    reinterpret_cast<uint4*>(&st.list[0][0])[256 + threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
+    for (int g = 0; g < CH / 4; g++) s_f[threadIdx.x][g] = make_float4(0.f, 0.f, 0.f, 0.f);   // the staged features of a stale offset: finite too
+    stage_clear_lists(st);
     for (uint32_t base = r0; base < r1; base += BATCH) {
         if (__syncthreads_count(base - r0 < last) == 0) break;   // no pixel of the tile blended anything this far back
         const uint32_t k = base + threadIdx.x;
         unsigned flags = 0u;
         if (k < r1) {
             const int id = point_list[k];
-            flags = stage_entry<false>(st, splat, id, tx0, ty0);
+            flags = stage_entry<false>(st, splat, id, tp.tx0, tp.ty0);
             if (flags) {
                 float v[CH];
                 load_feature_chunk<CH>(features, id, C, c0, nch, vec4, v);
@@ -95,18 +89,10 @@ __global__ void __launch_bounds__(256) k_render_features(int W, int H, int gx, i
         for (int jj = 0; jj < n_wave; jj += 4) {
             const uint2 pack = list4[jj >> 2];
             int off[4];   // 16 j
-            off[0] = (int)(pack.x & 0xffffu); off[1] = (int)(pack.x >> 16); off[2] = (int)(pack.y & 0xffffu); off[3] = (int)(pack.y >> 16);
+            unpack_offsets(pack, off);
             float alpha[4];
             bool ok[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const float4 a_j = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(st.a) + off[u]);
-                const float4 b_j = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(st.b) + off[u]);
-                const v2f d = (v2f){a_j.x, a_j.y} - (v2f){fx, fy};
-                const float power = blend_power((v2f){b_j.x, b_j.y}, b_j.z, d);
-                alpha[u] = fminf(0.99f, b_j.w * exp_blend(power));
-                ok[u] = (jj + u < n_mine) & (pos0 + ((uint32_t)off[u] >> 4) <= last) & !(power > 0.0f) & !(alpha[u] < 1.0f / 255.0f);
-            }
+            replay_pack(st, off, jj, n_mine, pos0, last, tp.fx, tp.fy, alpha, ok);
             if (__ballot(ok[0] | ok[1] | ok[2] | ok[3]) == 0ull) continue;   // wave-uniform
 #pragma unroll
             for (int u = 0; u < 4; u++) {
@@ -123,7 +109,7 @@ __global__ void __launch_bounds__(256) k_render_features(int W, int H, int gx, i
         }
         __syncthreads();
     }
-    if (inside) {
+    if (tp.inside) {
 #pragma unroll
         for (int k = 0; k < CH; k++)
             if (k < nch) out[(size_t)(c0 + k) * hw + pix] = F[k];
@@ -307,19 +293,12 @@ __global__ void __launch_bounds__(256) k_render_features_bw(int W, int H, int gx
     }
 }
 
-// a band = tile rows [begin, begin + n) of the frame's ceil(H / 16) rows: the rule of the band entry points of group 4
-bool features_band_ok(int32_t H, int32_t tile_row_begin, int32_t n_tile_rows) {
-    if (H < 1 || tile_row_begin < 0 || n_tile_rows < 1) return false;
-    return (int64_t)tile_row_begin + n_tile_rows <= (int64_t)((H + TILE - 1) / TILE);
-}
+// the saved state (gs_blend.h) and the feature table
 bool features_args_ok(int32_t P, int32_t C, int32_t W, int32_t H, const float* features, const int32_t* point_list, const uint32_t* ranges, const float* splat_records,
                       const uint32_t* tile_order, const uint32_t* n_contrib, int32_t tile_row_begin, int32_t n_tile_rows) {
-    if (!features_band_ok(H, tile_row_begin, n_tile_rows)) return false;
-    if (P < 0 || W < 1 || C < 1 || C > FEAT_C_MAX) return false;
-    if (!ranges || !tile_order || !n_contrib) return false;
-    if (P > 0 && (!features || !point_list || !splat_records)) return false;
-    if ((reinterpret_cast<uintptr_t>(splat_records) & 15u) || (reinterpret_cast<uintptr_t>(features) & 3u)) return false;
-    return true;
+    if (!gs_saved_state_ok(P, W, H, point_list, ranges, splat_records, tile_order, n_contrib, tile_row_begin, n_tile_rows)) return false;
+    if (C < 1 || C > FEAT_C_MAX || (P > 0 && !features)) return false;
+    return (reinterpret_cast<uintptr_t>(features) & 3u) == 0;
 }
 int features_vec4(int32_t C, const float* features) { return (C % 4 == 0 && (reinterpret_cast<uintptr_t>(features) & 15u) == 0) ? 1 : 0; }
 

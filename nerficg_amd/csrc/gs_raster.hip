@@ -32,9 +32,8 @@
 
 #include "common.h"
 #include "adam_math.h"
+#include "gs_blend.h"
 
-#define TILE 16
-#define BATCH 256
 #define SORT_LDS_CAP 8192  // 64-bit keys sorted in LDS per tile (64 KB)
 
 namespace {
@@ -1192,163 +1191,7 @@ __global__ void __launch_bounds__(1024) k_tile_order(int t_first, int n_tiles, c
 }
 
 // ------------------------------------------------------------------------------------------------ 5. render
-// thread -> pixel of the 16x16 tile: wave = 8x8 quadrant, DPP row (16 lanes) = 4x4 block of the quadrant.  block index b = 4 * wave + row,
-// block (cx, cy) of the 4x4 block grid of the tile: cx = 2 * (wave & 1) + (row & 1), cy = 2 * (wave >> 1) + (row >> 1).
-__device__ __forceinline__ int tile_px(unsigned t) { return (int)((t & 3u) + ((t >> 4) & 1u) * 4u + ((t >> 6) & 1u) * 8u); }
-__device__ __forceinline__ int tile_py(unsigned t) { return (int)(((t >> 2) & 3u) + ((t >> 5) & 1u) * 4u + (t >> 7) * 8u); }
-// The tile lists come from the square 3-sigma bound of preprocess (reference semantics, kept bit-exact), but a pixel only blends a
-// Gaussian where alpha = o exp(power) >= 1/255, i.e. inside the ellipse A dx^2 + 2 B dx dy + C dy^2 <= 2 ln(255 o).  On the bench
-// scene 52 % of the (tile, Gaussian) pairs of a list have no such pixel in the tile, and the box of a pair that has is ~5 pixels wide
-// (tools/gs_stats.py): it reaches 2.5 of the four 8x8 quadrants (160 lanes) but only ~5 of the sixteen 4x4 blocks (80 lanes).
-// Both render kernels therefore keep ONE WORK LIST PER 4x4 BLOCK: while a batch of 256 list entries is staged into LDS every thread tests
-// its entry's box against the 16 blocks; 16 ballots and a prefix over the 4 waves turn the flags into 16 ascending index lists; and every
-// DPP row of a wave walks ITS OWN list -- the four rows of a wave blend four different Gaussians in the same instruction.  The box is
-// conservative (margins below), so exactly the same pixels blend exactly the same Gaussians in the same order: bit-identical pictures.
-// bit b set when the alpha >= 1/255 ellipse of the record can reach a pixel centre of block b (block = 4 x 4 pixels of the 16 x 16 tile).
-// Two conservative tests: the ellipse's bounding box against the four column / row bands, then, per row band, the x-interval the ellipse
-// spans inside the band (chords at the band's two edges -- clamped to the ellipse's y-range --, widened to the box where the leftmost /
-// rightmost point of the ellipse lies inside the band) against the column bands.  On the bench scene the box keeps 6.2 blocks per
-// (tile, Gaussian) pair of a blended prefix, the band intervals 4.7, an exact per-pixel test 4.5 (tools/gs_stats.py).
-__device__ __forceinline__ unsigned block_flags(const float4& q0, const float4& q1, const float4& q2, float tx0, float ty0) {
-    const float X = q0.x, Y = q0.y, ex = q1.z, ey = q1.w;
-    if (!(ex >= 0.f)) return 0u;  // never reaches the threshold
-    unsigned col = 0, row = 0;
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-        const float x0 = tx0 + (float)(4 * c), y0 = ty0 + (float)(4 * c);
-        col |= (unsigned)(X + ex >= x0 && X - ex <= x0 + 3.f) << c;
-        row |= (unsigned)(Y + ey >= y0 && Y - ey <= y0 + 3.f) << c;
-    }
-    if (col == 0u || row == 0u) return 0u;
-    unsigned cols[4] = {col, col, col, col};
-    if (ex < __builtin_inff()) {
-        const float ta = q2.x, da = q2.y, ba = q2.z, yoff = q2.w;   // half chord at offset d from the centre row: sqrt(tau / A - (det / A^2) d^2)
-        float lo[5], hi[5];
-#pragma unroll
-        for (int k = 0; k < 5; k++) {
-            const float d = fminf(fmaxf(Y - (ty0 + (float)(4 * k)), -ey), ey);
-            const float w = __builtin_amdgcn_sqrtf(fmaxf(ta - da * d * d, 0.f));
-            const float mid = X + ba * d;
-            lo[k] = mid - w; hi[k] = mid + w;
-        }
-        const float yl = Y + yoff, yr = Y - yoff;
-#pragma unroll
-        for (int sl = 0; sl < 4; sl++) {
-            const float ca = fmaxf(ty0 + (float)(4 * sl), Y - ey), cb = fminf(ty0 + (float)(4 * sl + 4), Y + ey);
-            float l = fminf(lo[sl], lo[sl + 1]), h = fmaxf(hi[sl], hi[sl + 1]);
-            if ((yl >= ca && yl <= cb) || (yr >= ca && yr <= cb)) { l = fminf(l, X - ex); h = fmaxf(h, X + ex); }
-            l -= 0.02f; h += 0.02f;
-            unsigned cb4 = 0;
-#pragma unroll
-            for (int c = 0; c < 4; c++) {
-                const float x0 = tx0 + (float)(4 * c);
-                cb4 |= (unsigned)(h >= x0 && l <= x0 + 3.f) << c;
-            }
-            cols[sl] = col & cb4;
-        }
-    }
-    // block b = 4 * (2 * (cy >> 1) + (cx >> 1)) + 2 * (cy & 1) + (cx & 1)
-    unsigned f = 0;
-#pragma unroll
-    for (int cy = 0; cy < 4; cy++) {
-        const unsigned c4 = ((row >> cy) & 1u) ? cols[cy] : 0u;
-        f |= (c4 & 3u) << (8 * (cy >> 1) + 2 * (cy & 1));
-        f |= (c4 >> 2) << (8 * (cy >> 1) + 4 + 2 * (cy & 1));
-    }
-    return f;
-}
-// The exponent of a Gaussian at a pixel: -1/2 (A dx^2 + C dy^2) - B dx dy, as SIX instructions (one of them packed) with explicit fused multiply-adds where the source-order
-// form takes nine (this translation unit is built without contraction: the integer decisions of the per-Gaussian kernels must not move).  The blend
-// kernels are bound by VALU issue (profiles/: 0.70-0.78 of the issue slots at 315 M blends per frame), so instructions per blend are what they cost.
-// The upstream binary is an nvcc build with -fmad=true, i.e. it fuses in these places too; WHICH pairs it fuses is not recoverable, so the oracle
-// (oracle/gs_oracle_impl.h: GS_BLEND_POWER / test_T / the colour sums) states the same fusions and n_contrib / final_T stay bit-exact against it.
-typedef float v2f __attribute__((ext_vector_type(2)));
-// (A, C) and (dx, dy) travel as register PAIRS: the two first products are one v_pk_mul_f32, the pixel offset one v_pk_add_f32 -- the same
-// roundings as the scalar form, two VALU instructions less per blend.  (This translation unit is built with -fno-slp-vectorize: left to itself
-// the vectoriser pairs the products of two DIFFERENT list entries and pays the packing back in v_mov, 20 per four blends.)
-__device__ __forceinline__ float blend_power(v2f ac, float B, v2f d) {
-    const v2f p = ac * d;                                  // (A dx, C dy)
-    const float t2 = fmaf(p.y, d.y, p.x * d.x);
-    return fmaf(-0.5f, t2, -((B * d.x) * d.y));
-}
-// expf for the blend loops, WITHOUT the two range guards of the library routine: the same nine instructions (Cody-Waite split of x log2(e), v_exp_f32 on the
-// fraction, v_ldexp_f32 by the integer part), hence bit for bit the library's value wherever the result is a normal number, -87.3 <= x <= 88.72
-// (tools/micro/exp_blend_check.hip: 2 x 10^8 inputs -- a sweep of [-104, 0], every float in [-1e-3, 0], 2^13 floats around every multiple of ln 2 --
-// 0 differences there; below, where the result is a denormal, the two differ in how they flush: a blend needs alpha >= 1/255, i.e. x >= -5.6, so none
-// of those values is ever used).  The four instructions dropped -- two compares and two selects forcing 0 / inf outside the range -- were a tenth of
-// k_render's VALU instructions per blend (40 -> 36; 168 -> 157 us at 1 M Gaussians).  x > 88.72 (power > 0: the blend discards the entry) overflows to
-// inf in v_ldexp_f32 like the library's select.
-__device__ __forceinline__ float exp_blend(float x) {
-    const float ph = x * 0x1.715476p+0f;
-    float pl = fmaf(x, 0x1.715476p+0f, -ph);
-    pl = fmaf(x, 0x1.4ae0bep-26f, pl);
-    const float e = __builtin_rintf(ph);
-    const float a = (ph - e) + pl;
-    return __builtin_amdgcn_ldexpf(__builtin_amdgcn_exp2f(a), (int)e);
-}
-#define N_BLOCKS 16
-// One staged batch: thread t read entry t's 64-byte record; what the blend loop needs goes to LDS as two 16-byte vectors and a scalar.
-// LT = what a block list holds per entry: uint8_t = the batch index j (k_render_bw: its LDS budget, with the 18 KB of per-Gaussian sums, has no
-// room for more), uint16_t = 16 j, the BYTE OFFSET of the entry's records in a[] / b[] / c[] (k_render: the address arrives with the list read, three
-// VALU instructions per blend less).  Blue sits in a float4 array of its own so that all three records of an entry live at the same offset.
-template <typename LT>
-struct StageLdsT {
-    float4 a[BATCH];      // X, Y, r, g
-    float4 b[BATCH];      // A, C, B, o  (conic xx, yy, xy, opacity: the pair (A, C) is what blend_power multiplies with (dx, dy))
-    float4 c[BATCH];      // b, z, -, -  (z: staged by the depth-and-alpha instances only)
-    uint16_t flags[BATCH];
-    __attribute__((aligned(16))) LT list[N_BLOCKS][BATCH];
-};
-template <bool AUX, typename LT>
-__device__ __forceinline__ unsigned stage_entry(StageLdsT<LT>& st, const float4* __restrict__ splat, int id, float tx0, float ty0) {
-    const float4* rec = splat + 4 * (size_t)id;
-    const float4 q0 = rec[0], q1 = rec[1], q2 = rec[2], q3 = rec[3];
-    const unsigned flags = block_flags(q0, q1, q2, tx0, ty0);
-    if (flags) {
-        st.a[threadIdx.x] = make_float4(q0.x, q0.y, q3.x, q3.y);
-        st.b[threadIdx.x] = make_float4(q0.z, q1.x, q0.w, q1.y);
-        if constexpr (AUX) *reinterpret_cast<float2*>(&st.c[threadIdx.x]) = make_float2(q3.z, q3.w);
-        else st.c[threadIdx.x].x = q3.z;
-    }
-    return flags;
-}
-// Builds the 16 per-block lists of a staged batch: the 16 lanes of DPP row b (= the threads whose pixels form block b) build list b, lane l
-// from the flags of entries 16 l .. 16 l + 15 (two 16-byte LDS reads), ranked with a row prefix sum.  st.list[b] receives the batch indices
-// of the entries that reach block b in ascending order.  Returns the length of the calling thread's own list; *n_wave = the longest of the
-// calling wave's four lists.
-template <typename LT>
-__device__ __forceinline__ int block_lists(StageLdsT<LT>& st, unsigned flags, int* n_wave) {
-    st.flags[threadIdx.x] = (uint16_t)flags;
-    __syncthreads();
-    const int b = threadIdx.x >> 4, l16 = threadIdx.x & 15;
-    const uint4 fa = reinterpret_cast<const uint4*>(st.flags)[2 * l16], fb = reinterpret_cast<const uint4*>(st.flags)[2 * l16 + 1];
-    const uint32_t w[8] = {fa.x, fa.y, fa.z, fa.w, fb.x, fb.y, fb.z, fb.w};
-    uint32_t mask = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-        const uint32_t t = (w[k] >> b) & 0x00010001u;
-        mask |= ((t & 1u) | (t >> 15)) << (2 * k);
-    }
-    const int cnt = __popc(mask);
-    int incl = cnt;
-    incl += __builtin_amdgcn_update_dpp(0, incl, 0x111, 0xf, 0xf, true);  // row_shr:1, zero fill
-    incl += __builtin_amdgcn_update_dpp(0, incl, 0x112, 0xf, 0xf, true);
-    incl += __builtin_amdgcn_update_dpp(0, incl, 0x114, 0xf, 0xf, true);
-    incl += __builtin_amdgcn_update_dpp(0, incl, 0x118, 0xf, 0xf, true);
-    const int mine = __shfl(incl, 15, 16);
-    LT* dst = st.list[b] + (incl - cnt);
-    uint32_t m = mask;
-    while (m) {
-        const int i = __builtin_ctz(m);
-        m &= m - 1u;
-        *dst++ = (LT)((16 * l16 + i) * (sizeof(LT) == 2 ? 16 : 1));
-    }
-    *n_wave = max(max(__builtin_amdgcn_readlane(mine, 0), __builtin_amdgcn_readlane(mine, 16)),
-                  max(__builtin_amdgcn_readlane(mine, 32), __builtin_amdgcn_readlane(mine, 48)));
-    __syncthreads();
-    return mine;
-}
-
+// The pixel layout of a tile, the per-block work lists, the staged batch, blend_power and exp_blend: gs_blend.h (shared with the passes that replay this blend).
 // AUX: the instance that also blends the depth channel -- the view-space depth z of the splat record as a fourth "colour" with background 0, the same
 // weight alpha T, one multiply-add per entry -- and writes out_depth_alpha (2, H, W): plane 0 = sum w z, plane 1 = sum w = 1 - T.  The colour arithmetic,
 // n_contrib and final_T are those of the default instance, bit for bit; the default instance is the kernel it was before AUX existed.
@@ -1360,28 +1203,20 @@ __global__ void __launch_bounds__(256) k_render(GsCam cam, const uint32_t* __res
     __shared__ StageLdsT<uint16_t> st;
     if (pose) { bg0 = pose[35]; bg1 = pose[36]; bg2 = pose[37]; }
     const int tile = (int)tile_order[blockIdx.x];  // longest lists first
-    const int tile_x = tile % cam.gx, tile_y = tile / cam.gx;
-    const int px = tile_x * TILE + tile_px(threadIdx.x), py = tile_y * TILE + tile_py(threadIdx.x);
-    const bool inside = px < cam.W && py < cam.H;
-    const float fx = (float)px, fy = (float)py;
-    const float tx0 = (float)(tile_x * TILE), ty0 = (float)(tile_y * TILE);
-    const int block = threadIdx.x >> 4;  // = 4 * wave + DPP row
+    const TilePixel tp(tile, cam.gx, cam.W, cam.H);
     const uint32_t r0 = ranges[2 * tile], r1 = ranges[2 * tile + 1];
-    bool done = !inside;
+    bool done = !tp.inside;
     float T = 1.0f, C0 = 0.f, C1 = 0.f, C2 = 0.f;
     [[maybe_unused]] float Dz = 0.f;
     uint32_t last = 0;
-    const uint2* list4 = reinterpret_cast<const uint2*>(st.list[block]);   // four 16-bit entries of this row's list per LDS read
-    // everything the blend loop reads from LDS must be FINITE also for a row that is past the end of its list and picks up a stale index (see the
-    // weight below): thread t clears slot t, which only thread t ever stages into
-    st.a[threadIdx.x] = make_float4(0.f, 0.f, 0.f, 0.f); st.b[threadIdx.x] = make_float4(0.f, 0.f, 0.f, 0.f); st.c[threadIdx.x] = make_float4(0.f, 0.f, 0.f, 0.f);
-    // ... and every list entry it can pick up must be a valid offset: the lists start as zeros too (later batches leave offsets of earlier entries behind)
-    reinterpret_cast<uint4*>(&st.list[0][0])[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
-    reinterpret_cast<uint4*>(&st.list[0][0])[256 + threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
+    const uint2* list4 = reinterpret_cast<const uint2*>(st.list[tp.block]);   // four 16-bit entries of this row's list per LDS read
+    stage_clear_records(st);
+    st.c[threadIdx.x] = make_float4(0.f, 0.f, 0.f, 0.f);   // blue and z: read by this kernel alone
+    stage_clear_lists(st);
     for (uint32_t base = r0; base < r1; base += BATCH) {
         if (__syncthreads_count(done) == 256) break;
         const uint32_t k = base + threadIdx.x;
-        const unsigned flags = k < r1 ? stage_entry<AUX>(st, splat, point_list[k], tx0, ty0) : 0u;
+        const unsigned flags = k < r1 ? stage_entry<AUX>(st, splat, point_list[k], tp.tx0, tp.ty0) : 0u;
         int n_wave;
         const int n_mine = block_lists(st, flags, &n_wave);
         const uint32_t pos0 = base - r0 + 1u;  // contributor number of batch entry 0 = its position in the tile list + 1
@@ -1395,8 +1230,8 @@ __global__ void __launch_bounds__(256) k_render(GsCam cam, const uint32_t* __res
             // running state, four interleaved chains -- and only then (3) the short serial part (transmittance test, masks, accumulation) in
             // list order.  Entries past the end of the row's list and the reference's four early-outs (done / power > 0 / alpha < 1/255 /
             // saturation) are lane masks; same arithmetic, same order per pixel: bit-identical pixels.
-            int off[4];   // 16 j: entries behind the list end are stale offsets of earlier batches (or zeros): readable, masked below
-            off[0] = (int)(pack.x & 0xffffu); off[1] = (int)(pack.x >> 16); off[2] = (int)(pack.y & 0xffffu); off[3] = (int)(pack.y >> 16);
+            int off[4];
+            unpack_offsets(pack, off);
             float4 a_j[4], b_j[4];
             float c_j[4];
             [[maybe_unused]] float z_j[4];
@@ -1413,7 +1248,7 @@ __global__ void __launch_bounds__(256) k_render(GsCam cam, const uint32_t* __res
             bool ok[4];
 #pragma unroll
             for (int u = 0; u < 4; u++) {
-                const v2f d = (v2f){a_j[u].x, a_j[u].y} - (v2f){fx, fy};
+                const v2f d = (v2f){a_j[u].x, a_j[u].y} - (v2f){tp.fx, tp.fy};
                 const float power = blend_power((v2f){b_j[u].x, b_j[u].y}, b_j[u].z, d);
                 alpha[u] = fminf(0.99f, b_j[u].w * exp_blend(power));
                 ok[u] = (jj + u < n_mine) & !(power > 0.0f) & !(alpha[u] < 1.0f / 255.0f);
@@ -1438,8 +1273,8 @@ __global__ void __launch_bounds__(256) k_render(GsCam cam, const uint32_t* __res
         if (last_off >= 0) last = pos0 + ((uint32_t)last_off >> 4);   // contributor number of the last entry this pixel blended (one add per batch, not per blend)
         __syncthreads();
     }
-    if (inside) {
-        const size_t pix = (size_t)py * cam.W + px, hw = (size_t)cam.H * cam.W;
+    if (tp.inside) {
+        const size_t pix = (size_t)tp.py * cam.W + tp.px, hw = (size_t)cam.H * cam.W;
         final_T[pix] = T;
         n_contrib[pix] = last;
         out_color[pix] = C0 + T * bg0; out_color[hw + pix] = C1 + T * bg1; out_color[2 * hw + pix] = C2 + T * bg2;
@@ -1458,22 +1293,10 @@ __device__ __forceinline__ float row_sum_to_lane15(float v) {
     v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x118, 0xf, 0xf, true));  // row_shr:8
     return v;
 }
-// the four accumulators of the blend backward's global atomics, cleared by one launch (3 + 4 + 1 + 3 floats per Gaussian)
-// The blend backward's per-Gaussian accumulator: ONE 64-byte record per Gaussian,
-//   [0..2] dL/dcolour   [3] dL/dopacity   [4..5] dL/dmean2D (x, y)   [6..8] dL/dconic (xx, xy, yy)   [9] dL/dz (depth-and-alpha backward)   [10..15] unused,
-// so that the nine sums a tile flushes for a Gaussian are one contiguous 36-byte group of ONE atomic wave-instruction.  Round 2 kept them in four
-// arrays (colour (P,3), opacity (P), mean2D (P,3), conic (P,4)): nine atomic instructions per flushing thread, every lane of each in another
-// cache line -- float atomics execute at the memory side, per 64-byte request, and that shape is the slow one (MI355X_MICROARCH.md, Global float
-// atomics: "64 lanes in 64 different rows ~17x slower").  Ablation (round 3): without the flush k_render_bw took 367 instead of 485 us.
-#define GREC 16
+// the blend backward's gradient records (GREC floats per Gaussian: gs_blend.h), cleared by one launch
 __global__ void __launch_bounds__(256) k_zero_grads(int P, float4* __restrict__ grad_rec) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < (int64_t)P * (GREC / 4)) grad_rec[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-}
-// a + (b of the partner lane); CTRL: row_mirror 0x140 (lane ^ 15), row_half_mirror 0x141 (^ 7), quad_perm [3,2,1,0] 0x1b (^ 3), [1,0,3,2] 0xb1 (^ 1)
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float keep, float send) {
-    return keep + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, send), CTRL, 0xf, 0xf, true));
 }
 // (a + partner's a) in all lanes, (b + partner's b) in the lanes of the banks of BANKS.  The masked form has no builtin; the s_nop covers
 // the two wait states a DPP read needs after a VALU write of the same register, which the compiler cannot see through the asm.
@@ -2399,11 +2222,6 @@ int64_t nrc_gs_bin_hist_bytes(int32_t P, int32_t W, int32_t H, int64_t span_capa
     return gs_bin_ws(nullptr, P, gx, gy, span_capacity > 0 ? span_capacity : gs_default_span_cap(P)).words * (int64_t)sizeof(uint32_t);
 }
 
-// a band = tile rows [begin, begin + n) of the frame's gy rows; checked by the band entry points before anything else (no HIP call in front of it)
-static bool gs_band_ok(int32_t H, int32_t tile_row_begin, int32_t n_tile_rows) {
-    if (H < 1 || tile_row_begin < 0 || n_tile_rows < 1) return false;
-    return (int64_t)tile_row_begin + n_tile_rows <= (int64_t)((H + TILE - 1) / TILE);
-}
 static int32_t gs_all_rows(int32_t H) { return H >= 1 ? (H + TILE - 1) / TILE : 1; }   // (H < 1 is refused by the entry point's own checks)
 
 int64_t nrc_gs_bin_hist_bytes_band(int32_t P, int32_t W, int32_t H, int64_t span_capacity, int32_t tile_row_begin, int32_t n_tile_rows) {
