@@ -53,8 +53,10 @@ enum {
  * 19 = group 20 (the vanilla NeRF path's gradients to sample positions, viewing directions and rays) is new, every earlier signature is unchanged;
  * 20 = group 21 (nrc_gs_render_features_band / nrc_gs_backward_features_band: N-channel per-Gaussian features blended by the rasterizer's weights) is new,
  * every earlier signature is unchanged;
- * 21 = group 22 (nrc_gs_contributions_band: per-Gaussian contribution statistics of a rendered view) is new, every earlier signature is unchanged. */
-#define NRC_ABI_VERSION 21
+ * 21 = group 22 (nrc_gs_contributions_band: per-Gaussian contribution statistics of a rendered view) is new, every earlier signature is unchanged;
+ * 22 = nrc_ngp_set_encoder_vertex_levels / _vertex_view, nrc_ngp_vertex_view_bytes, nrc_ngp_build_vertex_view (group 6: the vertex view of the leading
+ * hashed levels) are new, every earlier signature is unchanged. */
+#define NRC_ABI_VERSION 22
 /* library identification; also used by the loader's symbol check */
 int nrc_abi_version(void);
 const char* nrc_build_info(void);
@@ -652,6 +654,24 @@ int nrc_ngp_build_block_view(const void* table_f16, int32_t n_levels, int32_t lo
                              void* view, nrc_stream_t stream);
 int nrc_ngp_set_encoder_block_view(const void* view);
 int nrc_ngp_set_encoder_block_levels(int32_t levels);
+/* Vertex view of the hashed levels that follow the block view's levels (at most 4 consecutive hashed levels, as long as the view stays below 128 MB;
+ * levels 5-8 of the shipped grid, res 81 112 154 213: 63.2 MB): level by level a dense array of the 4-byte fp16 pairs of its vertices, vertex (x, y, z)
+ * in [0, R)^3 at dword x + R * (y + R * z), R = res + 2, holding the table entry the spatial hash names for that vertex.  The image encoder reads a
+ * sample's corners at these levels as four 8-byte loads (the two x-neighbours of a (y, z) pair are adjacent) instead of four 16-byte loads, a
+ * predicated round of four more and the hash; the features are identical with and without the view for every sample inside the model box.  A
+ * position outside it gets meaningless features either way, and not the same ones: the view clamps the cell coordinates to res, the table path
+ * hashes whatever cell it is given.  A buffer of its own: the block view, its size and its functions are what they were.
+ *   nrc_ngp_vertex_view_bytes  : size of the view of a grid (0: no level qualifies, e.g. the first hashed level alone passes 128 MB; < 0: an error code)
+ *   nrc_ngp_build_vertex_view  : fills `view` from table_f16 -- again whenever the table's VALUES change (one gather pass over the view)
+ *   nrc_ngp_set_encoder_vertex_view : as nrc_ngp_set_encoder_block_view -- for the NEXT call of the four entry points on the calling host thread, taken
+ *       by that call whichever way it ends, never checked, NULL or no call = the table path.
+ *   nrc_ngp_set_encoder_vertex_levels : how many of the view's levels the encoder reads through it (0 .. 4), -1: the library's default, the measured
+ *       best.  A setting of the CALLING HOST THREAD; it exists for tests and measurements, the renderer does not call it. */
+int64_t nrc_ngp_vertex_view_bytes(int32_t n_levels, int32_t log2_hashmap_size, int32_t base_resolution, float per_level_scale);
+int nrc_ngp_build_vertex_view(const void* table_f16, int32_t n_levels, int32_t log2_hashmap_size, int32_t base_resolution, float per_level_scale,
+                              void* view, nrc_stream_t stream);
+int nrc_ngp_set_encoder_vertex_view(const void* view);
+int nrc_ngp_set_encoder_vertex_levels(int32_t levels);
 int nrc_ngp_encode_samples(const float* ts, const int32_t* row_tile, const float* ray_od, int64_t first_row, int64_t n_rows, const float* xyz_min3,
                            const float* xyz_size3, const void* table_f16, int32_t n_levels, int32_t log2_hashmap_size,
                            int32_t base_resolution, float per_level_scale, void* features_f16, const int32_t* arena_tile_off,

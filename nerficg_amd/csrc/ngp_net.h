@@ -44,6 +44,21 @@ struct BlockView {
     uint32_t first[NRC_ENC_BLOCK_MAX + 1];  // byte offset of the level's first record; [levels] = bytes
 };
 
+// Vertex view of the hashed levels that follow the block view's levels (image encoder only): level begin + i, i < levels, as a dense array of the 4-byte
+// fp16 pairs of its vertices, vertex (x, y, z) in [0, R)^3 at dword x + R * (y + R * z) behind byte first[i] of the view, R = res + 2 (a cell coordinate is
+// clamped to res, as in the block view, so gx + 1 <= res + 1).  In this order the two x-neighbours of a (y, z) pair are adjacent whatever the cell is: one
+// 8-byte load serves both, four per level, no hash, no straddle, no fix-up round (grid_level_features_vertex).  A separate buffer and kernel argument:
+// the block view is what it was.  Built by k_build_vertex_view whenever the table is refreshed.
+#define NRC_ENC_VERTEX_MAX 4                    // levels a view holds at most: levels 5-8 of the shipped grid (res 81 .. 213) are 63.2 MB
+#define NRC_ENC_VERTEX_MAX_BYTES (128u << 20)   // ... and the view of any other grid stops in front of the level that would pass this
+struct VertexView {
+    const void* ptr;                         // nullptr: no view
+    uint32_t bytes;
+    int32_t begin, levels;                   // levels begin <= l < begin + levels read the view
+    uint32_t first[NRC_ENC_VERTEX_MAX + 1];  // byte offset of the level's first vertex; [levels] = bytes
+    uint32_t R[NRC_ENC_VERTEX_MAX];          // vertices per axis
+};
+
 __device__ __forceinline__ f16v zero16() {
     f16v z;
 #pragma unroll
@@ -342,6 +357,26 @@ __device__ __forceinline__ void grid_level_features_block(__amdgpu_buffer_rsrc_t
     const auto lo = __builtin_amdgcn_raw_buffer_load_b128(view, rec << 5, first_byte, 0);
     const auto hi = __builtin_amdgcn_raw_buffer_load_b128(view, rec << 5, first_byte + 16u, 0);
     const uint32_t v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    f0 = 0.f; f1 = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; k++) fma_half2(w[k], v[k], f0, f1);
+}
+
+// hashed levels through the vertex view (VertexView): ONE base address from the cell (three v_min, two multiply-adds, a shift) and four 8-byte loads,
+// each the two x-neighbours of a (y, z) pair; the level's first byte and the three row / plane strides ride in the loads' scalar offsets.  Same fp16
+// values, same weights, same FMA order as grid_level_features_hashed: identical features for every position whose cell lies in [0, res]^3 -- what
+// positions in [0, 1]^3 (and a rounding beyond) never leave.  Outside the box the cell is clamped where the table path hashes whatever it gets: different
+// and equally meaningless features, as for the block view.  The loads are 4-byte aligned (8-byte only for even gx); buffer loads of a dword or more ask
+// for dword alignment only.
+__device__ __forceinline__ void grid_level_features_vertex(__amdgpu_buffer_rsrc_t view, uint32_t first_byte, uint32_t gx, uint32_t gy, uint32_t gz,
+                                                           uint32_t res, uint32_t R, const float (&w)[8], float& f0, float& f1) {
+    const uint32_t vtx = __umul24(__umul24(min(gz, res), R) + min(gy, res), R) + min(gx, res);
+    const uint32_t row = R << 2, plane = __umul24(R, R) << 2;   // (scalar)
+    const auto a = __builtin_amdgcn_raw_buffer_load_b64(view, vtx << 2, first_byte, 0);
+    const auto b = __builtin_amdgcn_raw_buffer_load_b64(view, vtx << 2, first_byte + row, 0);
+    const auto c = __builtin_amdgcn_raw_buffer_load_b64(view, vtx << 2, first_byte + plane, 0);
+    const auto d = __builtin_amdgcn_raw_buffer_load_b64(view, vtx << 2, first_byte + plane + row, 0);
+    const uint32_t v[8] = {a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
     f0 = 0.f; f1 = 0.f;
 #pragma unroll
     for (int k = 0; k < 8; k++) fma_half2(w[k], v[k], f0, f1);

@@ -328,7 +328,7 @@ __device__ __forceinline__ void fetch_dir(const QueryIn& in, int64_t i, float& d
 template <int SRC>
 __global__ void __launch_bounds__(256) k_grid_encode(QueryIn in, int64_t base, int64_t n, const __half2* __restrict__ table, GridCfg g,
                                                          uint4* __restrict__ feat, int narrow_levels, int lvl_range, int lane_shape = 0, int xcd_run = 0,
-                                                         BlockView bv = BlockView{}) {
+                                                         BlockView bv = BlockView{}, VertexView vv = VertexView{}) {
     int64_t bid = blockIdx.x;
     if constexpr (SRC == SRC_TILED) {
         // workgroups are dealt round-robin over the 8 XCDs; each XCD takes a CONTIGUOUS eighth of a range of slots instead of every eighth
@@ -386,6 +386,7 @@ __global__ void __launch_bounds__(256) k_grid_encode(QueryIn in, int64_t base, i
     const bool live = state > 0;
     const __amdgpu_buffer_rsrc_t trs = make_table_rsrc(table, g.total_entries * 4u);
     const __amdgpu_buffer_rsrc_t vrs = make_table_rsrc(bv.ptr, bv.bytes);   // (SRC_TILED: the cell-block view of levels < bv.levels, see BlockView)
+    const __amdgpu_buffer_rsrc_t xrs = make_table_rsrc(vv.ptr, vv.bytes);   // (SRC_TILED: the vertex view of levels vv.begin .. + vv.levels, see VertexView)
     uint4* out = feat + ((j >> 5) * 4) * 32 + (j & 31);
     const int rot = (int)((j >> 5) & 3);
     const int lvl_lo = lvl_range & 0xff, lvl_hi = (lvl_range >> 8) & 0xff;   // NRC_ENC_LEVELS (measurement only; 0 .. 16 normally)
@@ -406,6 +407,10 @@ __global__ void __launch_bounds__(256) k_grid_encode(QueryIn in, int64_t base, i
                     uint32_t gx, gy, gz;
                     grid_cell(px, py, pz, g.scale[level], gx, gy, gz, c.w);
                     grid_level_features_block(vrs, bv.first[level], gx, gy, gz, g.res[level], c.w, f0, f1);
+                } else if (SRC == SRC_TILED && level >= vv.begin && level < vv.begin + vv.levels) {   // (hashed levels behind the block view's: vertex_view_cfg)
+                    uint32_t gx, gy, gz;
+                    grid_cell(px, py, pz, g.scale[level], gx, gy, gz, c.w);
+                    grid_level_features_vertex(xrs, vv.first[level - vv.begin], gx, gy, gz, g.res[level], vv.R[level - vv.begin], c.w, f0, f1);
                 } else if (g.hashed[level]) {   // (the narrow levels are the leading dense ones: launch_encode)
                     grid_corners_u<true>(px, py, pz, g.scale[level], g.res[level], g.size[level], g.offset[level], c);
                     grid_level_features_hashed(trs, c, f0, f1);
@@ -481,6 +486,22 @@ __global__ void __launch_bounds__(256) k_build_block_view(const uint32_t* __rest
     view[2 * rec + 1] = make_uint4(table[c.e[4]], table[c.e[5]], table[c.e[6]], table[c.e[7]]);
 }
 
+// Fills the vertex view (VertexView) from the fp16 table: one thread per vertex.  The entry is corner 0 of the cell grid_corners_u<true> finds for a position
+// on the vertex -- the hash is the encoder's own, stated nowhere else.
+__global__ void __launch_bounds__(256) k_build_vertex_view(const uint32_t* __restrict__ table, GridCfg g, VertexView vv, uint32_t* __restrict__ view) {
+    const uint32_t v = blockIdx.x * 256u + threadIdx.x;
+    if (v >= vv.bytes / 4u) return;
+    int i = 0;
+    while (i + 1 < vv.levels && v * 4u >= vv.first[i + 1]) i++;
+    const int level = vv.begin + i;
+    const uint32_t r = v - vv.first[i] / 4u, R = vv.R[i];
+    const uint32_t x = r % R, y = r / R % R, z = r / (R * R);
+    const float scale = g.scale[level];   // >= 1 (vertex_view_cfg): fmaf(scale, x / scale, 0.5f) lies within a rounding of x + 0.5
+    Corner8 c;
+    grid_corners_u<true>((float)x / scale, (float)y / scale, (float)z / scale, scale, g.res[level], g.size[level], g.offset[level], c);
+    view[v] = table[c.e[0]];
+}
+
 // SH degree 4 of the ray direction as the colour net's k-step-0 B fragments, once per RAY of the tiled layout:
 //   ray_sh[(tile * 2 + hh) * 64 + lane] = fp16 coefficients 8hh .. 8hh+7 of ray (tile, lane)
 // (a sample's direction is its ray's: evaluating per sample would repeat ~80 VALU instructions 120 times per ray)
@@ -534,8 +555,12 @@ __device__ __forceinline__ void mlp_stage_weights(h8 (*wlds)[64], const __half* 
 // The MFMA chain of NT tiles of 32 samples: density net -> 16-row head -> colour net -> rgb head.  B: first-layer B fragments (fragment-major
 // features), X0: colour-net k-step 0 (SH of the direction).  Out, on lane r < 32 of tile u (sample r): h0[u] = fp16 density feature 0 and
 // rgb[u] = fp16 sigmoid of the colour head -- the values the packed records hold.
-template <int NT>
-__device__ __forceinline__ void mlp_chain(const h8 (*wlds)[64], const h8 (&B)[NT][2], const h8 (&X0)[NT], _Float16 (&h0)[NT], _Float16 (&rgbh)[NT][3]) {
+// PRE: the caller's rows share their directions (one ray tile per wave), so it ran the colour net's k-step 0 once (mlp_sh_step) and passes the
+// accumulators P instead of X0; the k-step-1 MFMA takes P as its C operand, which is what it took from the k-step-0 MFMA in front of it: the same
+// instructions on the same operands, 4 of the 32 32x32x16 MFMAs and two LDS fragment reads per row fewer.  P is only read.
+template <int NT, bool PRE>
+__device__ __forceinline__ void mlp_chain_from(const h8 (*wlds)[64], const h8 (&B)[NT][2], const h8 (*X0)/*[NT], !PRE*/, const f16v (*P)[2]/*[NT][2], PRE*/,
+                                               _Float16 (&h0)[NT], _Float16 (&rgbh)[NT][3]) {
     const int lane = threadIdx.x & 63;
 #define D0(mt, s) wlds[MLP_F_D0 + 2 * (mt) + (s)][lane]
 #define DO(s) wlds[MLP_F_DO + (s)][lane]
@@ -548,7 +573,7 @@ __device__ __forceinline__ void mlp_chain(const h8 (*wlds)[64], const h8 (&B)[NT
     f4v o[NT][2];         // head accumulators, one per 16-sample block
 #pragma unroll
     for (int u = 0; u < NT; u++) {
-        X[u][0] = X0[u];
+        if constexpr (!PRE) X[u][0] = X0[u];
         acc[u][0] = zero16(); acc[u][1] = zero16();
         o[u][0] = f4v{0.f, 0.f, 0.f, 0.f}; o[u][1] = o[u][0];
     }
@@ -581,15 +606,18 @@ __device__ __forceinline__ void mlp_chain(const h8 (*wlds)[64], const h8 (&B)[NT
     for (int u = 0; u < NT; u++) {
         X[u][1] = head_join(o[u][0], o[u][1]);  // colour-net k-step 1 = fp16(h), natural order, back on the sample's lanes
         h0[u] = X[u][1][0];              // fp16 density feature 0 (lane half 0, element 0)
-        acc[u][0] = zero16(); acc[u][1] = zero16();
+        if constexpr (!PRE) { acc[u][0] = zero16(); acc[u][1] = zero16(); }
     }
 #pragma unroll
     for (int mt = 0; mt < 2; mt++)
 #pragma unroll
-        for (int s = 0; s < 2; s++) {
+        for (int s = PRE ? 1 : 0; s < 2; s++) {
             const h8 w = C0(mt, s);
 #pragma unroll
-            for (int u = 0; u < NT; u++) acc[u][mt] = mlp_mfma(w, X[u][s], acc[u][mt]);
+            for (int u = 0; u < NT; u++) {
+                if constexpr (PRE) acc[u][mt] = mlp_mfma(w, X[u][1], P[u][mt]);   // C = the tile's k-step 0, D = this row's accumulator: no copy of P
+                else acc[u][mt] = mlp_mfma(w, X[u][s], acc[u][mt]);
+            }
         }
 #pragma unroll
     for (int u = 0; u < NT; u++) {
@@ -634,10 +662,31 @@ __device__ __forceinline__ void mlp_chain(const h8 (*wlds)[64], const h8 (&B)[NT
     }
 #undef D0
 #undef DO
-#undef C0
 #undef C1
 #undef CO
 }
+// the form of k_ngp_mlp and k_nwie_fwd: every row brings its own directions
+template <int NT>
+__device__ __forceinline__ void mlp_chain(const h8 (*wlds)[64], const h8 (&B)[NT][2], const h8 (&X0)[NT], _Float16 (&h0)[NT], _Float16 (&rgbh)[NT][3]) {
+    mlp_chain_from<NT, false>(wlds, B, X0, nullptr, h0, rgbh);
+}
+// the form of k_ngp_mlp_composite: P from mlp_sh_step, once per ray tile
+template <int NT>
+__device__ __forceinline__ void mlp_chain(const h8 (*wlds)[64], const h8 (&B)[NT][2], const f16v (&P)[NT][2], _Float16 (&h0)[NT], _Float16 (&rgbh)[NT][3]) {
+    mlp_chain_from<NT, true>(wlds, B, nullptr, P, h0, rgbh);
+}
+// colour-net k-step 0 of NT 32-sample tiles: P[u][mt] = C0(mt, 0) x X0[u] on a zero accumulator, exactly the first colour MFMA of the chain above
+template <int NT>
+__device__ __forceinline__ void mlp_sh_step(const h8 (*wlds)[64], const h8 (&X0)[NT], f16v (&P)[NT][2]) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int mt = 0; mt < 2; mt++) {
+        const h8 w = C0(mt, 0);
+#pragma unroll
+        for (int u = 0; u < NT; u++) P[u][mt] = mlp_mfma(w, X0[u], zero16());
+    }
+}
+#undef C0
 template <int SRC>
 __global__ void __launch_bounds__(256, NRC_MLP_WAVES) k_ngp_mlp(QueryIn in, int64_t base, int64_t n, const uint4* __restrict__ feat,
                                                     const h8* __restrict__ ray_sh, const __half* __restrict__ Wd,
@@ -900,9 +949,14 @@ __global__ void __launch_bounds__(256, NRC_MLP_WAVES) k_ngp_mlp_composite(const 
         const bool inside = px < ic.width && py < ic.height;
         const int N = inside ? ray_cnt[(int64_t)lt * 64 + lane] : 0;
         NrcRayAcc acc = nrc_ray_acc(N > 0);
-        h8 X0[NT];   // colour-net k-step 0 = SH of the rays: the same for every row of the tile
+        // colour-net k-step 0 = SH of the rays: the same for every row of the tile, so its MFMAs run here, once, and the rows start the colour layer from P
+        f16v P[NT][2];
+        {
+            h8 X0[NT];
 #pragma unroll
-        for (int u = 0; u < NT; u++) X0[u] = ray_sh[((int64_t)lt * 2 + hh) * 64 + r + 32 * u];
+            for (int u = 0; u < NT; u++) X0[u] = ray_sh[((int64_t)lt * 2 + hh) * 64 + r + 32 * u];
+            mlp_sh_step<NT>(wlds, X0, P);
+        }
         const float* tcol = ts + (((int64_t)lt * arena_rows) << 6) + lane;
         const uint4* fcol = feat + (int64_t)(rb - row0) * (NT * 128) + r;   // 32-sample tile 2 (row - row0) + u at fcol + (2 k + u) * 128
         const int rot0 = (2 * (rb - row0)) & 3;
@@ -927,7 +981,7 @@ __global__ void __launch_bounds__(256, NRC_MLP_WAVES) k_ngp_mlp_composite(const 
             const float t = nt_;
             if (k + 1 < R) fetch(k + 1);
             _Float16 h0[NT], rgbh[NT][3];
-            mlp_chain<NT>(wlds, B, X0, h0, rgbh);
+            mlp_chain<NT>(wlds, B, P, h0, rgbh);
             // fp16 outputs exactly as the packed records hold them, (h0, r) and (g, b); sample 32 u + r sits on lane r of tile u
             uint32_t w01[NT], w23[NT];
 #pragma unroll
@@ -1003,6 +1057,27 @@ void block_view_cfg(const GridCfg& g, int n_levels, BlockView& bv) {
     for (int k = l; k <= NRC_ENC_BLOCK_MAX; k++) bv.first[k] = (uint32_t)bytes;
 }
 
+// The levels a vertex view of this grid holds, and where: the consecutive hashed levels that follow the block view's levels, at most NRC_ENC_VERTEX_MAX
+// of them, while the view stays below NRC_ENC_VERTEX_MAX_BYTES.  (scale >= 1: the builder places its position by a division by the scale.)  vv.ptr stays null.
+void vertex_view_cfg(const GridCfg& g, int n_levels, VertexView& vv) {
+    BlockView bv;
+    block_view_cfg(g, n_levels, bv);
+    vv = VertexView{};
+    vv.begin = bv.levels;
+    uint64_t bytes = 0;
+    int i = 0;
+    for (; i < NRC_ENC_VERTEX_MAX && vv.begin + i < n_levels && g.hashed[vv.begin + i] && g.scale[vv.begin + i] >= 1.f; i++) {
+        const uint64_t R = (uint64_t)g.res[vv.begin + i] + 2u, level_bytes = R * R * R * 4u;
+        if (bytes + level_bytes > NRC_ENC_VERTEX_MAX_BYTES) break;
+        vv.first[i] = (uint32_t)bytes;
+        vv.R[i] = (uint32_t)R;
+        bytes += level_bytes;
+    }
+    vv.levels = i;
+    vv.bytes = (uint32_t)bytes;
+    for (int k = i; k <= NRC_ENC_VERTEX_MAX; k++) vv.first[k] = (uint32_t)bytes;
+}
+
 int pick_blocks(int64_t M) {
     // every workgroup stages the network's weight fragments in LDS (24 KB) before its first tile: few workgroups with several tiles per wave beat
     // one tile per wave (cap on the number of workgroups: 512 below 1 Mi samples, 2 048 above)
@@ -1057,9 +1132,31 @@ static BlockView block_view_of(const void* view, const GridCfg& g, int n_levels)
     if (!bv.ptr || bv.levels <= 0) { bv.ptr = nullptr; bv.levels = 0; }
     return bv;
 }
+// The vertex view of the table (VertexView), handed over and taken like the block view: nrc_ngp_set_encoder_vertex_view for the calling thread's NEXT
+// frame entry point, gone whichever way that call ends.  nrc_ngp_set_encoder_vertex_levels: how many of the view's levels are read there,
+// -1 = NRC_ENC_VERTEX_LEVELS; per host thread.
+#ifndef NRC_ENC_VERTEX_LEVELS
+#define NRC_ENC_VERTEX_LEVELS 4   // measured: 0, 1, 2, 3, 4 -- LABBOOK R27
+#endif
+static thread_local const void* g_enc_vertex_view = nullptr;
+static thread_local int g_enc_vertex_levels_override = -1;
+static const void* take_vertex_view() {
+    const void* view = g_enc_vertex_view;
+    g_enc_vertex_view = nullptr;
+    return view;
+}
+static VertexView vertex_view_of(const void* view, const GridCfg& g, int n_levels) {
+    VertexView vv;
+    vertex_view_cfg(g, n_levels, vv);
+    const int want = g_enc_vertex_levels_override >= 0 ? g_enc_vertex_levels_override : NRC_ENC_VERTEX_LEVELS;
+    vv.ptr = view;
+    if (want < vv.levels) vv.levels = want;   // (the levels behind it stay in the view, unread)
+    if (!vv.ptr || vv.levels <= 0) { vv.ptr = nullptr; vv.levels = 0; }
+    return vv;
+}
 template <int SRC>
 static void launch_encode(const QueryIn& in, int64_t base, int64_t n, const void* table, const GridCfg& g, uint4* feat, hipStream_t s,
-                          const BlockView& bv = BlockView{}) {
+                          const BlockView& bv = BlockView{}, const VertexView& vv = VertexView{}) {
     // levels whose cells are larger than a wave's footprint: narrow gathers (see grid_level_features_narrow)
     int narrow = 0;
     while (narrow < NRC_MAX_LEVELS && !g.hashed[narrow] && g.size[narrow] > 8) narrow++;
@@ -1086,7 +1183,7 @@ static void launch_encode(const QueryIn& in, int64_t base, int64_t n, const void
     const int lane_shape = (3 << 4) | 1;
     const int lanes = (SRC == SRC_TILED && (base & 1023) == 0) ? (g_enc_shape_override ? g_enc_shape_override : lane_shape) : 0;
     hipLaunchKernelGGL(k_grid_encode<SRC>, dim3((unsigned)(lanes ? 4 * nrc_cdiv(n, 1024) : nrc_cdiv(n, 256)), rows), dim3(256), 0, s, in, base, n, (const __half2*)table, g, feat,
-                       narrow, lvl_range, lanes, g_enc_xcd_run_override ? g_enc_xcd_run_override : NRC_ENC_XCD_RUN, bv);
+                       narrow, lvl_range, lanes, g_enc_xcd_run_override ? g_enc_xcd_run_override : NRC_ENC_XCD_RUN, bv, vv);
 }
 
 template <int SRC>
@@ -1100,7 +1197,8 @@ static void launch_mlp(const QueryIn& in, int64_t base, int64_t n, const void* f
 // feature buffers -- 11.27 ms per image against 10.99 ms in one stream; the encode grid fills every CU, the MLP blocks only queue.)
 template <int SRC>
 static int run_query(const QueryIn& in, int64_t M, int64_t n_ray_tiles, const void* wd, const void* wc, const void* table, const GridCfg& g,
-                     float* sigmas, float* rgbs, void* packed, void* workspace, hipStream_t s, const BlockView& bv = BlockView{}) {
+                     float* sigmas, float* rgbs, void* packed, void* workspace, hipStream_t s, const BlockView& bv = BlockView{},
+                     const VertexView& vv = VertexView{}) {
     uint4* feat = (uint4*)workspace;
     h8* ray_sh = (h8*)((char*)workspace + query_feat_bytes(M));
     if constexpr (SRC == SRC_TILED)
@@ -1109,7 +1207,7 @@ static int run_query(const QueryIn& in, int64_t M, int64_t n_ray_tiles, const vo
     NRC_STAGE(s, nullptr);      // (armed stage timer: the two kernels of every chunk IN the frame's own sequence -- bench.py's in-frame ruler)
     for (int64_t base = 0; base < M; base += NRC_QUERY_CHUNK) {
         const int64_t n = (M - base) < NRC_QUERY_CHUNK ? (M - base) : NRC_QUERY_CHUNK;
-        launch_encode<SRC>(in, base, n, table, g, feat, s, bv);
+        launch_encode<SRC>(in, base, n, table, g, feat, s, bv, vv);
         NRC_STAGE(s, "k_grid_encode");
         launch_mlp<SRC>(in, base, n, feat, ray_sh, wd, wc, sigmas, rgbs, packed, s);
         NRC_STAGE(s, "k_ngp_mlp");
@@ -1267,12 +1365,45 @@ int nrc_ngp_build_block_view(const void* table_f16, int32_t n_levels, int32_t lo
     NRC_LAUNCH_CHECK();
     return NRC_OK;
 }
+int nrc_ngp_set_encoder_vertex_levels(int32_t levels) {
+    if (levels < -1 || levels > NRC_ENC_VERTEX_MAX) return NRC_ERR_INVALID;
+    g_enc_vertex_levels_override = levels;
+    return NRC_OK;
+}
+int nrc_ngp_set_encoder_vertex_view(const void* view) {
+    g_enc_vertex_view = view;
+    return NRC_OK;
+}
+int64_t nrc_ngp_vertex_view_bytes(int32_t n_levels, int32_t log2_hashmap_size, int32_t base_resolution, float per_level_scale) {
+    GridCfg g;
+    const int rc = make_grid_cfg(n_levels, log2_hashmap_size, base_resolution, per_level_scale, g, nullptr);
+    if (rc != NRC_OK) return rc;
+    VertexView vv;
+    vertex_view_cfg(g, n_levels, vv);
+    return (int64_t)vv.bytes;
+}
+int nrc_ngp_build_vertex_view(const void* table_f16, int32_t n_levels, int32_t log2_hashmap_size, int32_t base_resolution, float per_level_scale,
+                              void* view, nrc_stream_t stream) {
+    NRC_ENTER();
+    GridCfg g;
+    const int rc = make_grid_cfg(n_levels, log2_hashmap_size, base_resolution, per_level_scale, g, nullptr);
+    if (rc != NRC_OK) return rc;
+    VertexView vv;
+    vertex_view_cfg(g, n_levels, vv);
+    if (vv.bytes == 0) return NRC_OK;
+    if (!table_f16 || !view) return NRC_ERR_INVALID;
+    hipLaunchKernelGGL(k_build_vertex_view, dim3((unsigned)nrc_cdiv((int64_t)(vv.bytes / 4u), 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const uint32_t*)table_f16, g, vv, (uint32_t*)view);
+    NRC_LAUNCH_CHECK();
+    return NRC_OK;
+}
 int nrc_ngp_encode_samples(const float* ts, const int32_t* row_tile, const float* ray_od, int64_t first_row, int64_t n_rows, const float* xyz_min3,
                            const float* xyz_size3, const void* table_f16, int32_t n_levels, int32_t log2_hashmap_size,
                            int32_t base_resolution, float per_level_scale, void* features_f16, const int32_t* arena_tile_off, int32_t arena_rows,
                            nrc_stream_t stream) {
     NRC_ENTER();
     const void* view = take_block_view();
+    const void* vview = take_vertex_view();
     const int64_t n = n_rows * 64;
     if (n_rows < 0 || first_row < 0 || n > NRC_QUERY_CHUNK || !table_f16 || !xyz_min3 || !xyz_size3) return NRC_ERR_INVALID;
     if ((arena_tile_off != nullptr) != (arena_rows > 0) || arena_rows < 0) return NRC_ERR_INVALID;
@@ -1285,7 +1416,8 @@ int nrc_ngp_encode_samples(const float* ts, const int32_t* row_tile, const float
     QueryIn in = {};
     in.ts = ts; in.row_tile = row_tile; in.ray_od = ray_od; in.tile_off = arena_tile_off; in.arena_rows = arena_rows;
     for (int k = 0; k < 3; k++) { in.mn[k] = xyz_min3[k]; in.sz[k] = xyz_size3[k]; }
-    launch_encode<SRC_TILED>(in, first_row * 64, n, table_f16, g, (uint4*)features_f16, (hipStream_t)stream, block_view_of(view, g, n_levels));
+    launch_encode<SRC_TILED>(in, first_row * 64, n, table_f16, g, (uint4*)features_f16, (hipStream_t)stream, block_view_of(view, g, n_levels),
+                             vertex_view_of(vview, g, n_levels));
     NRC_LAUNCH_CHECK();
     return NRC_OK;
 }
@@ -1316,6 +1448,7 @@ int nrc_ngp_query_samples(const float* ts, int32_t* row_tile, const float* ray_o
                           int32_t arena_rows, nrc_stream_t stream) {
     NRC_ENTER();
     const void* view = take_block_view();
+    const void* vview = take_vertex_view();
     const int64_t M = n_rows * 64;
     if ((arena_tile_off != nullptr) != (arena_rows > 0) || arena_rows < 0) return NRC_ERR_INVALID;
     if (n_rows < 0 || n_ray_tiles < 0 || !density_weights_f16 || !color_weights_f16 || !table_f16 || !xyz_min3 || !xyz_size3) return NRC_ERR_INVALID;
@@ -1330,7 +1463,7 @@ int nrc_ngp_query_samples(const float* ts, int32_t* row_tile, const float* ray_o
     in.tile_off = arena_tile_off; in.arena_rows = arena_rows;
     for (int k = 0; k < 3; k++) { in.mn[k] = xyz_min3[k]; in.sz[k] = xyz_size3[k]; }
     run_query<SRC_TILED>(in, M, n_ray_tiles, density_weights_f16, color_weights_f16, table_f16, g, nullptr, nullptr, packed_f16, workspace, (hipStream_t)stream,
-                         block_view_of(view, g, n_levels));
+                         block_view_of(view, g, n_levels), vertex_view_of(vview, g, n_levels));
     NRC_LAUNCH_CHECK();
     return NRC_OK;
 }
@@ -1354,6 +1487,7 @@ int nrc_ngp_render_layers(const float* ts, int32_t* row_tile, const float* ray_o
                           int32_t arena_rows, nrc_stream_t stream) {
     NRC_ENTER();
     const void* view = take_block_view();
+    const void* vview = take_vertex_view();
     const int64_t M = n_rows * 64;
     if ((arena_row_k != nullptr) != (arena_rows > 0) || arena_rows < 0) return NRC_ERR_INVALID;
     if (n_rows < 0 || n_ray_tiles < 1 || !density_weights_f16 || !color_weights_f16 || !table_f16 || !xyz_min3 || !xyz_size3 || !bg3_host ||
@@ -1380,6 +1514,7 @@ int nrc_ngp_render_layers(const float* ts, int32_t* row_tile, const float* ray_o
     in.row_k = arena_row_k; in.arena_rows = arena_rows;
     for (int k = 0; k < 3; k++) { in.mn[k] = xyz_min3[k]; in.sz[k] = xyz_size3[k]; }
     const BlockView bv = block_view_of(view, g, n_levels);
+    const VertexView vv = vertex_view_of(vview, g, n_levels);
     nrc_launch_layers_init(n_ray_tiles, ray_cnt, state, ray_alive, next_k, tile_alive, skipped_rows, s);
     hipLaunchKernelGGL(k_ray_sh, dim3((unsigned)nrc_cdiv(n_ray_tiles * 64, 256)), dim3(256), 0, s, ray_od, n_ray_tiles, ray_sh);
     // front to back: encode + MLP on a slab of rows, composite it, finished tiles drop out of the following slabs.  No host
@@ -1388,7 +1523,7 @@ int nrc_ngp_render_layers(const float* ts, int32_t* row_tile, const float* ray_o
     do {
         const int64_t cn = (M - base) < NRC_QUERY_CHUNK ? (M - base) : NRC_QUERY_CHUNK;
         if (cn > 0) {
-            launch_encode<SRC_TILED>(in, base, cn, table_f16, g, feat, s, bv);
+            launch_encode<SRC_TILED>(in, base, cn, table_f16, g, feat, s, bv, vv);
             launch_mlp<SRC_TILED>(in, base, cn, feat, ray_sh, density_weights_f16, color_weights_f16, nullptr, nullptr, packed_f16, s);
         }
         nrc_launch_composite_layers(packed_f16, ts, ray_cnt, tile_rows, tile_off, row_of, row_tile, (base + cn) / 64, width, height, tile_begin, n_ray_tiles, cascades,
@@ -1426,6 +1561,7 @@ int nrc_ngp_render_frame(const float* ts_arena, int32_t* row_tile, const float* 
                          nrc_stream_t stream) {
     NRC_ENTER();
     const void* view = take_block_view();
+    const void* vview = take_vertex_view();
     const int64_t budget = frame_budget(row_budget);
     if (n_rows < 0 || n_ray_tiles < 1 || width < 1 || height < 1 || tile_begin < 0 || cascades < 1 || grid_size < 1 || max_samples < 1 ||
         budget < 2 * (int64_t)max_samples || !density_weights_f16 || !color_weights_f16 || !table_f16 || !xyz_min3 || !xyz_size3 || !bg3_host)
@@ -1461,6 +1597,7 @@ int nrc_ngp_render_frame(const float* ts_arena, int32_t* row_tile, const float* 
     hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
     const int64_t resident = (int64_t)(n_cu > 0 ? n_cu : 256) * NRC_MLP_WAVES, mlp_blocks = nrc_cdiv(n_ray_tiles, 4) < resident ? nrc_cdiv(n_ray_tiles, 4) : resident;
     const BlockView bv = block_view_of(view, g, n_levels);
+    const VertexView vv = vertex_view_of(vview, g, n_levels);
     NRC_STAGE(s, nullptr);
     // SH of every ray + the ray tile of every row (for the encoder)
     hipLaunchKernelGGL(k_ray_sh, dim3((unsigned)nrc_cdiv(n_ray_tiles * 64, 256)), dim3(256), 0, s, ray_od, n_ray_tiles, ray_sh, tile_off, row_tile, n_rows);
@@ -1471,7 +1608,7 @@ int nrc_ngp_render_frame(const float* ts_arena, int32_t* row_tile, const float* 
     for (int64_t c = 0; c < chunks; c++) {
         if (n_rows > 0) {
             in.chunk_rows = chunk_tab + 4 * c + 2;
-            launch_encode<SRC_TILED>(in, 0, feat_rows * 64, table_f16, g, feat, s, bv);
+            launch_encode<SRC_TILED>(in, 0, feat_rows * 64, table_f16, g, feat, s, bv, vv);
             NRC_STAGE(s, "k_grid_encode");
         }
         hipLaunchKernelGGL(k_ngp_mlp_composite, dim3((unsigned)mlp_blocks), dim3(256), 0, s, feat, ray_sh, (const __half*)density_weights_f16,

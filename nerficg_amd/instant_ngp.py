@@ -415,19 +415,25 @@ class InstantNGPRenderer:
 
     def _block_view_ptr(self):
         """The cell-block view of the grid's dense levels for the image encoder (tinycudann._block_view: built here if the fp16 table changed, valid
-        from frame to frame otherwise).  Taken where a frame's arguments are marshalled -- ahead of the wait for the row count."""
-        return _lib.ptr(self.model.encoding_xyz._block_view())
+        from frame to frame otherwise) and the vertex view of the hashed levels behind them (tinycudann._vertex_view), as a pair.  Taken where a
+        frame's arguments are marshalled -- ahead of the wait for the row count."""
+        enc = self.model.encoding_xyz
+        return _lib.ptr(enc._block_view()), _lib.ptr(enc._vertex_view())
 
     @staticmethod
-    def _frame_entry(fn, args, what: str, view) -> None:
-        """One of the library's frame entry points with the view handed over in front of it (nrc_ngp_set_encoder_block_view: the call takes it).
-        Cleared behind the call as well: a call that never reached the library (an argument ctypes refuses) must not leave it to the next one."""
+    def _frame_entry(fn, args, what: str, views) -> None:
+        """One of the library's frame entry points with the two views (_block_view_ptr) handed over in front of it (nrc_ngp_set_encoder_block_view /
+        _vertex_view: the call takes them).  Cleared behind the call as well: a call that never reached the library (an argument ctypes refuses) must
+        not leave them to the next one."""
         lib = _lib.load()
-        lib.nrc_ngp_set_encoder_block_view(view)
+        block, vertex = views
+        lib.nrc_ngp_set_encoder_block_view(block)
+        lib.nrc_ngp_set_encoder_vertex_view(vertex)
         try:
             _lib.check(fn(*args), what)
         finally:
             lib.nrc_ngp_set_encoder_block_view(None)
+            lib.nrc_ngp_set_encoder_vertex_view(None)
 
     def _fused_size_rows(self, ws: dict, rows: int, nt: int) -> None:
         if rows > ws['cap']:

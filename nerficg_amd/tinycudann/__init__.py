@@ -225,6 +225,8 @@ class NetworkWithInputEncoding(torch.nn.Module):
         self._half_key = None
         self._view = None       # _block_view
         self._view_key = None
+        self._vview = None      # _vertex_view
+        self._vview_key = None
         self._half_captures = 0  # times the fp16 copy was handed to an optimizer step that a HIP graph was recording (_half_for_optimizer)
         # nerficg_amd.apex_optimizers.FusedAdam updates `params` through a raw pointer: it finds this module through the parameter and
         # has the step kernel rewrite the fp16 copy as well (_half_for_optimizer / _half_written_by_optimizer)
@@ -315,6 +317,35 @@ class NetworkWithInputEncoding(torch.nn.Module):
                 _lib.check(lib.nrc_ngp_build_block_view(_lib.ptr(self._table16()), *cfg, _lib.ptr(view), _lib.stream_of(view)), 'ngp_build_block_view')
             self._view, self._view_key = view, key
         return self._view
+
+    def _vertex_view(self):
+        """Vertex view of the hashed levels behind the block view's (include/nerficg_hip.h, nrc_ngp_build_vertex_view; 63 MB for the shipped grid), allocated
+        and built on first use -- a model that never renders a frame never pays for it -- and cached under the key of the fp16 copy like _block_view:
+        rebuilt (one gather pass over the view) when the copy was.  Where _block_view rebuilds for EVERY frame (a recorded HIP graph writes the copy, or
+        the frame itself is being recorded) there is no vertex view: its build (65 us) costs more than it saves on any frame below about 64 M samples
+        (DESIGN 3.1), and those levels read the table, which is always current.  None for a grid without such levels."""
+        if self.encoding != 0 or not self.default_layout:
+            return None
+        if self._half_captures or torch.cuda.is_current_stream_capturing():
+            self._vview = self._vview_key = None
+            return None
+        self._refresh_half()
+        key = (self._half_key, self._half.data_ptr())
+        if self._vview_key != key:
+            lib, g = _lib.load(), self.grid_cfg
+            cfg = (g['n_levels'], g['log2_hashmap_size'], g['base_resolution'], float(g['per_level_scale']))
+            nbytes = int(lib.nrc_ngp_vertex_view_bytes(*cfg))
+            if nbytes < 0:
+                _lib.check(nbytes, 'ngp_vertex_view_bytes')
+            view = self._vview
+            if nbytes == 0:
+                view = None
+            elif view is None or view.numel() != nbytes or view.device != self._half.device:
+                view = torch.empty(nbytes, dtype=torch.uint8, device=self._half.device)
+            if view is not None:
+                _lib.check(lib.nrc_ngp_build_vertex_view(_lib.ptr(self._table16()), *cfg, _lib.ptr(view), _lib.stream_of(view)), 'ngp_build_vertex_view')
+            self._vview, self._vview_key = view, key
+        return self._vview
 
     @property
     def default_layout(self) -> bool:
