@@ -55,7 +55,8 @@ enum {
  * every earlier signature is unchanged;
  * 21 = group 22 (nrc_gs_contributions_band: per-Gaussian contribution statistics of a rendered view) is new, every earlier signature is unchanged;
  * 22 = nrc_ngp_set_encoder_vertex_levels / _vertex_view, nrc_ngp_vertex_view_bytes, nrc_ngp_build_vertex_view (group 6: the vertex view of the leading
- * hashed levels) are new, every earlier signature is unchanged. */
+ * hashed levels) are new, every earlier signature is unchanged.  Added under 22 without a bump (additive: no earlier signature, record slot or default
+ * launch changes): group 23, nrc_gs_backward_absgrad_band -- slots [10], [11] of a gradient record carry sum_pixels |dL_pixel/dmean2D| in that call only. */
 #define NRC_ABI_VERSION 22
 /* library identification; also used by the loader's symbol check */
 int nrc_abi_version(void);
@@ -1301,6 +1302,38 @@ int nrc_gs_backward_features_band(int32_t P, int32_t C, int32_t W, int32_t H, co
 int nrc_gs_contributions_band(int32_t P, int32_t W, int32_t H, const int32_t* point_list, const uint32_t* ranges, const float* splat_records,
                               const uint32_t* tile_order, const uint32_t* n_contrib, const float* pixel_weights, float* weight_sum, float* weight_max,
                               int32_t* hits, int32_t clear, int32_t tile_row_begin, int32_t n_tile_rows, nrc_stream_t stream);
+
+/* =====================================================================================================
+ * Group 23 -- absolute screen-space gradients of the 3DGS rasterizer (csrc/gs_raster.hip: k_render_bw<., true>).  The densification statistic of AbsGS, gsplat's
+ *            absgrad=True, which Mip-Splatting and GOF rely on: the norm of dL_dmean2D is a SIGNED sum over pixels that cancels where a large Gaussian blurs
+ *            fine texture; the sum of the per-pixel magnitudes does not.  It exists only inside the blend backward, before its row reduction.
+ *
+ *   nrc_gs_backward_absgrad_band : nrc_gs_backward_pose_band (dL_ddepth_alpha, pose_partials and dL_dcamera stay optional as there) + dL_dmean2D_abs (P, 3) f32:
+ *            dL_dmean2D_abs[i][0] = sum over the band's tiles and the pixels that blended i of | -w (dx A + dy B) W/2 |
+ *            dL_dmean2D_abs[i][1] = sum ...                                                   of | -w (dy C + dx B) H/2 |        dL_dmean2D_abs[i][2] = 0
+ *            with w = o G dL/dalpha of the WHOLE call (colour, and with dL_ddepth_alpha the depth and alpha channels): the addends of dL_dmean2D[i][0..1], their
+ *            absolute value taken PER PIXEL before any row, block, tile or band sum, in the units of dL_dmean2D (the factors W/2, H/2 included).  Every row is
+ *            written: exact zeros for culled Gaussians and for Gaussians no pixel of the band blended.  Bands: the band's share; the shares of a partition sum
+ *            to the frame's.  Every other output is the one nrc_gs_backward_pose_band computes from the same per-Gaussian sums (float atomics in another order).
+ *   Gradient record (64 bytes, 16 f32 per Gaussian): [0..2] colour, [3] opacity, [4], [5] mean2D x, y, [6..8] conic xx, xy, yy, [9] dL/dz (depth-and-alpha
+ *            backward only), [10], [11] sum |dL_pixel/dmean2D| x, y (this call only; never written otherwise), [12..15] free.  The call leaves every record it
+ *            read all zero again, slots [10], [11] included.
+ *   dL_dmean2D_abs == NULL: nrc_gs_backward_pose_band itself (same kernels, same launches).  P == 0: nothing is written to dL_dmean2D_abs.  The same validation
+ *            before any HIP call as nrc_gs_backward_pose_band (bad band, dL_dcamera without or with a misaligned workspace, grad_records not 64-byte aligned).
+ *            There is no absgrad form of nrc_gs_backward_rest_step or of nrc_gs_backward_features_band: the feature backward forms its share of dL/dalpha in
+ *            another kernel, and |a + b| cannot be assembled from two kernels' sums.
+ * ===================================================================================================== */
+int nrc_gs_backward_absgrad_band(int32_t P, int32_t D, int32_t M, int32_t W, int32_t H, const float* bg, const float* means3D, const float* shs,
+                    const float* shs_rest, int32_t raw_parameters, const float* opacities, const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
+                    const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix, const float* campos,
+                    const float* camera_dev, float tan_fovx, float tan_fovy, const int32_t* radii, const float* points_xy, const float* conic_opacity,
+                    const float* rgb, const uint8_t* clamped, const float* cov3D, const int32_t* point_list,
+                    const uint32_t* ranges, const float* splat_records, const uint32_t* tile_order, const uint32_t* n_contrib,
+                    const float* final_T, const float* dL_dpix,
+                    float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
+                    float* dL_dcov3D, float* dL_dsh, float* dL_dsh_rest, float* dL_dscale, float* dL_drot, float* grad_records,
+                    int32_t records_clear, int32_t tile_row_begin, int32_t n_tile_rows, const float* dL_ddepth_alpha, float* pose_partials,
+                    float* dL_dcamera, float* dL_dmean2D_abs, nrc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1333,12 +1333,22 @@ __device__ __forceinline__ float dpp_add2(float a, float b) {
 //   therefore taken from max(|g_rgb|, |g_a|, |g_d| max(1, z_max)): every sum is still linear in that quantity with the same class bounds.
 //   The tenth sum is a plain row sum deposited by lane 15 of the row (a lane the transposing reduction leaves without a column): the default instance
 //   keeps its nine columns, its LDS and its instructions.
-template <bool AUX>
+// ABS: the instances that also sum the ABSOLUTE values of the two mean2D addends, per pixel, before any reduction (AbsGS's densification signal:
+// sum_pixels |dL_pixel/dmean2D| does not cancel where a large Gaussian blurs fine texture).  |d_mx| and |d_my| of gradients() take one 16-lane
+// butterfly of their own (five DPP adds: sum |d_mx| in lanes 0-7 of the row, sum |d_my| in lanes 8-15), and lanes 3 and 11 -- odd lanes that hold no
+// column -- deposit them as two further columns of s_acc (Q_ABS, Q_ABS + 1) with the other columns' one ds_add_u64; the flush adds them to slots
+// [10], [11] of the record.  Without AUX that is 11 columns: 4 workgroups per CU still fit the LDS; with AUX 12 columns and 3 workgroups.
+// Fixed point: class BW_S_MEAN, whose bound 2^19 is a bound on
+// sum_pixels |addend| / gmax over a tile -- derived from the magnitudes, for terms that may all have one sign -- so it covers sum |addend| as it stands.
+// The flush constants are those of columns 4 and 5 without the minus sign.  The ABS = false instances keep their columns, LDS and instructions.
+template <bool AUX, bool ABS>
 __global__ void __launch_bounds__(256) k_render_bw(GsCam cam, const uint32_t* __restrict__ ranges, const int32_t* __restrict__ point_list,
                                                    const float4* __restrict__ splat, const uint32_t* __restrict__ tile_order, float bg0, float bg1, float bg2,
                                                    const float* __restrict__ pose, const uint32_t* __restrict__ n_contrib, const float* __restrict__ final_T,
                                                    const float* __restrict__ dL_dpix, float* __restrict__ grad_rec, const float* __restrict__ dL_daux) {
-    constexpr int NQ = AUX ? 10 : 9;
+    constexpr int Q_Z = 9;                  // AUX: the column of dL/dz
+    constexpr int Q_ABS = AUX ? 10 : 9;     // ABS: the columns of sum |d_mx|, sum |d_my| (slots [10], [11] of the record in both cases)
+    constexpr int NQ = ABS ? Q_ABS + 2 : AUX ? 10 : 9;
     __shared__ StageLdsT<uint8_t> st;
     __shared__ unsigned long long s_acc[BATCH][NQ];  // per-Gaussian gradient sums of the tile's 16 blocks (fixed point), flushed once per batch
     __shared__ int s_id[BATCH];                     // Gaussian of batch entry t (-1: nothing staged)
@@ -1406,9 +1416,10 @@ __global__ void __launch_bounds__(256) k_render_bw(GsCam cam, const uint32_t* __
     // transposing row reduction (see the loop): the lane that ends up with column q of s_acc, its scale, and the partner-selection bits
     const int l16 = lane & 15;
     const bool b3 = l16 & 8, b2 = l16 & 4, b1 = l16 & 2, b0 = l16 & 1;
-    const bool q_has = !b0 || l16 == 1;
-    const int q_col = b0 ? 4 : (b3 ? 5 : 0) + (b2 ? 2 : 0) + (b1 ? 1 : 0);  // columns: c0 c1 c2 op mx | my cx cy cw
-    const int q_s = q_col < 3 ? BW_S_COLOR : q_col == 3 ? BW_S_OPACITY : q_col < 6 ? BW_S_MEAN : BW_S_CONIC;
+    const bool q_abs = ABS && (l16 == 3 || l16 == 11);   // ABS: lanes 3 and 11 hold columns Q_ABS (sum |d_mx|) and Q_ABS + 1 (sum |d_my|)
+    const bool q_has = ABS ? (!b0 || l16 == 1 || q_abs) : (!b0 || l16 == 1);
+    const int q_col = q_abs ? (b3 ? Q_ABS + 1 : Q_ABS) : b0 ? 4 : (b3 ? 5 : 0) + (b2 ? 2 : 0) + (b1 ? 1 : 0);  // columns: c0 c1 c2 op mx | my cx cy cw
+    const int q_s = q_col < 3 ? BW_S_COLOR : q_col == 3 ? BW_S_OPACITY : (q_col < 6 || q_abs) ? BW_S_MEAN : BW_S_CONIC;
     const float q_scale = ldexpf(1.0f, q_s - gexp);
     const int blast_v = lane < N_BLOCKS ? s_blast[lane] : 0;  // lanes 0..15 of every wave: the 16 block maxima
     int n_eff = blast_v;
@@ -1515,7 +1526,18 @@ __global__ void __launch_bounds__(256) k_render_bw(GsCam cam, const uint32_t* __
             const float u0 = dpp_add<0x1b>(b1 ? t1 : t0, b1 ? t0 : t1), u4 = dpp_add<0x1b>(t4, t4);
             // last step: a lane keeps ONE of (u0, u4) and its partner lane ^ 1 the other -- select what I keep and what the partner needs first, then
             // one exchange-and-add (selecting afterwards took two exchanges)
-            return dpp_add<0xb1>(b0 ? u4 : u0, b0 ? u0 : u4);
+            const float mine = dpp_add<0xb1>(b0 ? u4 : u0, b0 ? u0 : u4);
+            if constexpr (ABS) {
+                // |.| per pixel, then a plain butterfly: the mirror step leaves the pair sums of |d_mx| in lanes 0-7 and of |d_my| in lanes 8-15, three
+                // unmasked steps (partners ^ 7, ^ 3, ^ 1) complete both sums in every lane of their half; an inactive lane adds |0|
+                float a = dpp_add2<0x140, 0xc>(__builtin_fabsf(d_mx), __builtin_fabsf(d_my));
+                a = dpp_add<0x141>(a, a);
+                a = dpp_add<0x1b>(a, a);
+                a = dpp_add<0xb1>(a, a);
+                return q_abs ? a : mine;
+            } else {
+                return mine;
+            }
         };
         // the nine sums of the row leave with ONE 64-bit integer LDS atomic
         auto deposit = [&](int jj, int j, float mine) {
@@ -1543,7 +1565,7 @@ __global__ void __launch_bounds__(256) k_render_bw(GsCam cam, const uint32_t* __
                 const float hs = t * 0x1p-32f;
                 const float hf = __builtin_floorf(hs);
                 const uint32_t lo32 = (uint32_t)(int)__builtin_fmaf(-__builtin_rintf(hs), 0x1p32f, t);
-                atomicAdd(&s_acc[j][NQ - 1], ((unsigned long long)(uint32_t)(int)hf << 32) | lo32);
+                atomicAdd(&s_acc[j][Q_Z], ((unsigned long long)(uint32_t)(int)hf << 32) | lo32);
             }
         };
         // BW_PAIR entries per trip: their record reads, exponentials and reductions are independent instruction streams (only T and the
@@ -1575,11 +1597,15 @@ __global__ void __launch_bounds__(256) k_render_bw(GsCam cam, const uint32_t* __
             const int q = threadIdx.x & 15;
             const float inv = (q < 3 || (AUX && q == 9)) ? ldexpf(1.0f, gexp - BW_S_COLOR) : q == 3 ? ldexpf(1.0f, gexp - BW_S_OPACITY)
                             : q == 4 ? -ddelx_dx * ldexpf(1.0f, gexp - BW_S_MEAN) : q == 5 ? -ddely_dy * ldexpf(1.0f, gexp - BW_S_MEAN)
+                            : (ABS && q == 10) ? ddelx_dx * ldexpf(1.0f, gexp - BW_S_MEAN) : (ABS && q == 11) ? ddely_dy * ldexpf(1.0f, gexp - BW_S_MEAN)
                                                                                            : -0.5f * ldexpf(1.0f, gexp - BW_S_CONIC);
+            // ABS: lanes 10 and 11 take columns Q_ABS, Q_ABS + 1 to slots [10], [11]; without AUX lane 9 has no column
+            const bool q_live = ABS ? (q < 9 || (AUX && q == 9) || q == 10 || q == 11) : q < NQ;
+            const int qc = (ABS && q >= 10) ? q - 10 + Q_ABS : q;
             for (int e = threadIdx.x >> 4; e < nb_raw; e += 16) {
                 const int id = s_id[e];
-                if (id >= 0 && q < NQ) {
-                    const long long a = (long long)s_acc[e][q];
+                if (id >= 0 && q_live) {
+                    const long long a = (long long)s_acc[e][qc];
                     if (a != 0ll) atomicAdd(grad_rec + (size_t)id * GREC + q, (float)a * inv);
                 }
             }
@@ -1595,7 +1621,7 @@ __device__ __forceinline__ void preprocess_bw_one(int i, const GsCam& cam, const
                                                   float* __restrict__ grad_rec, float* __restrict__ dL_dmean2D, float* __restrict__ dL_dconic,
                                                   float* __restrict__ dL_dcolor, float* __restrict__ dL_dmean3D,
                                                   float* __restrict__ dL_dcov3D, float* __restrict__ dL_dscale, float* __restrict__ dL_drot,
-                                                  const float* __restrict__ opacities, float* __restrict__ dL_dopacity) {
+                                                  const float* __restrict__ opacities, float* __restrict__ dL_dopacity, float* __restrict__ dL_dmean2D_abs) {
     // the blend kernel's sums of this Gaussian: one 64-byte record (see k_zero_grads); the API's per-quantity tensors are written from it
     const float4 r0 = *reinterpret_cast<const float4*>(grad_rec + (size_t)i * GREC), r1 = *reinterpret_cast<const float4*>(grad_rec + (size_t)i * GREC + 4);
     const float2 r2 = *reinterpret_cast<const float2*>(grad_rec + (size_t)i * GREC + 8);   // [8] conic yy, [9] dL/dz (depth-and-alpha backward only; 0 otherwise)
@@ -1604,6 +1630,11 @@ __device__ __forceinline__ void preprocess_bw_one(int i, const GsCam& cam, const
     *reinterpret_cast<float4*>(grad_rec + (size_t)i * GREC) = make_float4(0.f, 0.f, 0.f, 0.f);
     *reinterpret_cast<float4*>(grad_rec + (size_t)i * GREC + 4) = make_float4(0.f, 0.f, 0.f, 0.f);
     *reinterpret_cast<float2*>(grad_rec + (size_t)i * GREC + 8) = make_float2(0.f, 0.f);
+    if (dL_dmean2D_abs) {   // absgrad backward only: slots [10], [11] = sum |dL_pixel/dmean2D| x, y (k_render_bw<., true>); read, handed out and cleared like the rest
+        const float2 r3 = *reinterpret_cast<const float2*>(grad_rec + (size_t)i * GREC + 10);
+        *reinterpret_cast<float2*>(grad_rec + (size_t)i * GREC + 10) = make_float2(0.f, 0.f);
+        dL_dmean2D_abs[3 * i] = r3.x; dL_dmean2D_abs[3 * i + 1] = r3.y; dL_dmean2D_abs[3 * i + 2] = 0.f;
+    }
     const float gcol[3] = {r0.x, r0.y, r0.z};
     {
         float g_op = r0.w;
@@ -1800,7 +1831,7 @@ __global__ void __launch_bounds__(PBW_BLOCK) k_preprocess_bw(int P, GsCam cam_ar
                                                              float* __restrict__ dL_dconic, float* __restrict__ dL_dcolor,
                                                              float* __restrict__ dL_dmean3D, float* __restrict__ dL_dcov3D, float* __restrict__ dL_dsh,
                                                              float* __restrict__ dL_dsh_rest, float* __restrict__ dL_dscale, float* __restrict__ dL_drot,
-                                                             float* __restrict__ dL_dopacity, RestAdam ra) {
+                                                             float* __restrict__ dL_dopacity, RestAdam ra, float* __restrict__ dL_dmean2D_abs) {
     __shared__ float s_sh[PBW_BLOCK * (3 * PBW_MAXM + 1)];
     const GsCam cam = cam_with_pose(cam_arg, pose);
     const int first = blockIdx.x * PBW_BLOCK, i = first + threadIdx.x;
@@ -1816,8 +1847,9 @@ __global__ void __launch_bounds__(PBW_BLOCK) k_preprocess_bw(int P, GsCam cam_ar
     float* sh_row = s_sh + threadIdx.x * pitch;
     if (visible) {
         preprocess_bw_one(i, cam, means3D, sh_row, use_sh, scales, rotations, use_scale_rot, clamped, cov3D, grad_rec, dL_dmean2D, dL_dconic, dL_dcolor,
-                          dL_dmean3D, dL_dcov3D, dL_dscale, dL_drot, opacities, dL_dopacity);
+                          dL_dmean3D, dL_dcov3D, dL_dscale, dL_drot, opacities, dL_dopacity, dL_dmean2D_abs);
     } else if (i < P) {
+        if (dL_dmean2D_abs) { dL_dmean2D_abs[3 * i] = 0.f; dL_dmean2D_abs[3 * i + 1] = 0.f; dL_dmean2D_abs[3 * i + 2] = 0.f; }
         if (use_sh) for (int k = 0; k < row_len; k++) sh_row[k] = 0.f;
         dL_dopacity[i] = 0.f;
         dL_dmean2D[3 * i] = 0.f; dL_dmean2D[3 * i + 1] = 0.f; dL_dmean2D[3 * i + 2] = 0.f;
@@ -2433,13 +2465,14 @@ static int gs_backward_impl(int32_t P, int32_t D, int32_t M, int32_t W, int32_t 
                     float* dL_dmean2D, float* dL_dconic,
                     float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dsh_rest, float* dL_dscale,
                     float* dL_drot, float* grad_records, int32_t records_clear, nrc_stream_t stream, RestAdam ra, int32_t n_rows, const float* dL_ddepth_alpha,
-                    float* pose_partials = nullptr, float* dL_dcamera = nullptr) {
+                    float* pose_partials = nullptr, float* dL_dcamera = nullptr, float* dL_dmean2D_abs = nullptr) {
     GsCam cam;
     const int rc = make_cam(cam, W, H, D, M, viewmatrix_host, projmatrix_host, campos_host, camera_dev, tan_fovx, tan_fovy, scale_modifier, raw_parameters);
     if (rc != NRC_OK) return rc;
     if (P < 0 || (!bg_host && !camera_dev)) return NRC_ERR_INVALID;
     const float bg[3] = {bg_host ? bg_host[0] : 0.f, bg_host ? bg_host[1] : 0.f, bg_host ? bg_host[2] : 0.f};
     if (dL_dcamera && (!pose_partials || ra.p)) return NRC_ERR_INVALID;   // (there is no camera gradient in the form that steps `rest`)
+    if (dL_dmean2D_abs && ra.p) return NRC_ERR_INVALID;                   // (nor an absgrad form of it)
     if (P == 0) {
         if (dL_dcamera) {   // no Gaussians: the camera gradient is 35 zeros
             hipLaunchKernelGGL(k_pose_finish, dim3(1), dim3(POSE_FIN_GROUPS * POSE_SLAB), 0, (hipStream_t)stream, 0, (const float*)pose_partials, dL_dcamera);
@@ -2463,12 +2496,16 @@ static int gs_backward_impl(int32_t P, int32_t D, int32_t M, int32_t W, int32_t 
     }
     // n_rows tile rows (< gy for a band): tile_order lists the tiles of the forward's band, one workgroup each
     // dL_ddepth_alpha: the instance that also takes the two extra pixel gradients (slot [9] of the records); NULL: the colour-only kernel
-    if (dL_ddepth_alpha)
-        hipLaunchKernelGGL(k_render_bw<true>, dim3(cam.gx * n_rows), dim3(256), 0, s, cam, ranges, point_list, (const float4*)splat_records, tile_order, bg[0], bg[1], bg[2],
-                           camera_dev, n_contrib, final_T, dL_dpix, grad_records, dL_ddepth_alpha);
-    else
-        hipLaunchKernelGGL(k_render_bw<false>, dim3(cam.gx * n_rows), dim3(256), 0, s, cam, ranges, point_list, (const float4*)splat_records, tile_order, bg[0], bg[1], bg[2],
-                           camera_dev, n_contrib, final_T, dL_dpix, grad_records, (const float*)nullptr);
+    // dL_dmean2D_abs: the instances that also sum |dL_pixel/dmean2D| into slots [10], [11]; NULL: today's two kernels
+#define GS_RBW_LAUNCH(AUX_, ABS_, AUXPTR_) \
+        hipLaunchKernelGGL((k_render_bw<AUX_, ABS_>), dim3(cam.gx * n_rows), dim3(256), 0, s, cam, ranges, point_list, (const float4*)splat_records, tile_order, bg[0], bg[1], bg[2], \
+                           camera_dev, n_contrib, final_T, dL_dpix, grad_records, AUXPTR_)
+    if (dL_ddepth_alpha) {
+        if (dL_dmean2D_abs) GS_RBW_LAUNCH(true, true, dL_ddepth_alpha); else GS_RBW_LAUNCH(true, false, dL_ddepth_alpha);
+    } else {
+        if (dL_dmean2D_abs) GS_RBW_LAUNCH(false, true, (const float*)nullptr); else GS_RBW_LAUNCH(false, false, (const float*)nullptr);
+    }
+#undef GS_RBW_LAUNCH
     NRC_STAGE(s, "k_render_bw");
     if (dL_dcamera) {
         // the camera gradient reads the records the blend backward just filled, before k_preprocess_bw consumes and clears them
@@ -2482,7 +2519,7 @@ static int gs_backward_impl(int32_t P, int32_t D, int32_t M, int32_t W, int32_t 
         NRC_STAGE(s, "k_pose_finish");
     }
 #define GS_PBW_ARGS P, cam, camera_dev, means3D, shs, shs_rest, opacities, use_sh, scales, rotations, use_sr, radii, clamped, cov3D, grad_records, dL_dmean2D, dL_dconic, dL_dcolor, \
-                    dL_dmean3D, dL_dcov3D, dL_dsh, dL_dsh_rest, dL_dscale, dL_drot, dL_dopacity, ra
+                    dL_dmean3D, dL_dcov3D, dL_dsh, dL_dsh_rest, dL_dscale, dL_drot, dL_dopacity, ra, dL_dmean2D_abs
     if (ra.p) hipLaunchKernelGGL(k_preprocess_bw<2>, dim3(nrc_cdiv(P, PBW_BLOCK)), dim3(PBW_BLOCK), 0, s, GS_PBW_ARGS);
     else if (shs_rest) hipLaunchKernelGGL(k_preprocess_bw<1>, dim3(nrc_cdiv(P, PBW_BLOCK)), dim3(PBW_BLOCK), 0, s, GS_PBW_ARGS);
     else hipLaunchKernelGGL(k_preprocess_bw<0>, dim3(nrc_cdiv(P, PBW_BLOCK)), dim3(PBW_BLOCK), 0, s, GS_PBW_ARGS);
@@ -2566,6 +2603,27 @@ int nrc_gs_backward_pose_band(int32_t P, int32_t D, int32_t M, int32_t W, int32_
                             ranges, splat_records, tile_order, n_contrib, final_T, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
                             dL_dsh_rest, dL_dscale, dL_drot, grad_records, records_clear, stream, RestAdam{nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, 0.f, 1.f, 1.f}, n_tile_rows,
                             dL_ddepth_alpha, dL_dcamera ? pose_partials : nullptr, dL_dcamera);
+}
+
+/* nrc_gs_backward_pose_band that also returns sum_pixels |dL_pixel/dmean2D| per Gaussian (group 23); dL_dmean2D_abs == NULL: that call itself */
+int nrc_gs_backward_absgrad_band(int32_t P, int32_t D, int32_t M, int32_t W, int32_t H, const float* bg_host, const float* means3D, const float* shs,
+                    const float* shs_rest, int32_t raw_parameters, const float* opacities, const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
+                    const float* cov3D_precomp, const float* viewmatrix_host, const float* projmatrix_host, const float* campos_host,
+                    const float* camera_dev, float tan_fovx, float tan_fovy, const int32_t* radii, const float* points_xy, const float* conic_opacity,
+                    const float* rgb, const uint8_t* clamped, const float* cov3D, const int32_t* point_list, const uint32_t* ranges,
+                    const float* splat_records, const uint32_t* tile_order, const uint32_t* n_contrib, const float* final_T, const float* dL_dpix,
+                    float* dL_dmean2D, float* dL_dconic,
+                    float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dsh_rest, float* dL_dscale,
+                    float* dL_drot, float* grad_records, int32_t records_clear, int32_t tile_row_begin, int32_t n_tile_rows, const float* dL_ddepth_alpha,
+                    float* pose_partials, float* dL_dcamera, float* dL_dmean2D_abs, nrc_stream_t stream) {
+    if (!gs_band_ok(H, tile_row_begin, n_tile_rows)) return NRC_ERR_INVALID;
+    if (dL_dcamera && (!pose_partials || (reinterpret_cast<uintptr_t>(pose_partials) & 15u))) return NRC_ERR_INVALID;
+    NRC_ENTER();
+    return gs_backward_impl(P, D, M, W, H, bg_host, means3D, shs, shs_rest, raw_parameters, opacities, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
+                            viewmatrix_host, projmatrix_host, campos_host, camera_dev, tan_fovx, tan_fovy, radii, points_xy, conic_opacity, rgb, clamped, cov3D, point_list,
+                            ranges, splat_records, tile_order, n_contrib, final_T, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
+                            dL_dsh_rest, dL_dscale, dL_drot, grad_records, records_clear, stream, RestAdam{nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, 0.f, 1.f, 1.f}, n_tile_rows,
+                            dL_ddepth_alpha, dL_dcamera ? pose_partials : nullptr, dL_dcamera, dL_dmean2D_abs);
 }
 
 int nrc_gs_camera_block_backward(const float* c2w_dev, const float* proj_t_dev, const float* dL_dcamera, float* dL_dc2w_out, nrc_stream_t stream) {

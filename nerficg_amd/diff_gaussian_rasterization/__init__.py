@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import contextlib
 import warnings
+import weakref
 from typing import NamedTuple
 
 import torch
@@ -156,7 +157,7 @@ def _opt(t):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, sh_rest=None, raw=False, rest_step=None, tile_rows=None,
-                depth_alpha=False, viewmatrix=None, projmatrix=None, campos=None, features=None):
+                depth_alpha=False, viewmatrix=None, projmatrix=None, campos=None, features=None, absgrad=False):
         rs = raster_settings
         lib = _lib.load()
         band = check_tile_rows(tile_rows, rs.image_height)
@@ -173,6 +174,13 @@ class _RasterizeGaussians(torch.autograd.Function):
         if features is not None and rest_step is not None:
             raise RuntimeError('features together with rest_step: the backward pass that steps the `rest` SH tensor (nrc_gs_backward_rest_step) takes the '
                                'colour gradient only -- there is no feature form of it; render without rest_step and let the optimizer take that step')
+        absgrad = bool(absgrad)
+        if absgrad and rest_step is not None:
+            raise RuntimeError('absgrad together with rest_step: the backward pass that steps the `rest` SH tensor (nrc_gs_backward_rest_step) takes the '
+                               'colour gradient only -- there is no absgrad form of it; render without rest_step and let the optimizer take that step')
+        if absgrad and features is not None:
+            raise RuntimeError('absgrad together with features: the feature backward (nrc_gs_backward_features_band) forms its share of dL/dalpha in another kernel, '
+                               'and |a + b| per pixel cannot be assembled from two kernels\' sums -- there is no absgrad form of it; render the features in a call of their own')
         if band is not None and rest_step is not None:
             raise RuntimeError('rest_step together with tile_rows: the backward pass of a band holds this band\'s SHARE of the gradient only, and an Adam step '
                                'taken on a partial gradient is not the optimizer\'s step -- sum the shares over the bands first and step then')
@@ -356,6 +364,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.features_grad = feat_c is not None and bool(ctx.needs_input_grad[17])
         ctx.band = band
         ctx.depth_alpha = depth_alpha
+        # absgrad: the backward leaves sum_pixels |dL_pixel/dmean2D| on the tensor OBJECT the caller passed as means2D (weakly held: ctx must not keep it alive)
+        ctx.absgrad = weakref.ref(means2D) if absgrad else None
         ctx.raster_settings = rs
         ctx.dims = (P, D, M, W, H)
         ctx.num_rendered = n_inst if fixed is None else -1
@@ -442,7 +452,32 @@ class _RasterizeGaussians(torch.autograd.Function):
             elif ctx.features_grad:
                 dfeat = torch.zeros(n1, C_f, dtype=f32, device=dev)
         dcam = None
-        if ctx.camera is not None:
+        if ctx.absgrad is not None:
+            # the instances of the blend backward that also sum |dL_pixel/dmean2D| (slots [10], [11] of the records), with or without the maps and the camera gradient
+            b0, bn = ctx.band if ctx.band is not None else (0, (H + 15) // 16)
+            partials = None
+            if ctx.camera is not None:
+                partials = torch.empty(int(lib.nrc_gs_pose_partials_floats(P)), dtype=f32, device=dev)
+                dcam = torch.empty(35, dtype=f32, device=dev)
+            dabs = torch.empty(P, 3, dtype=f32, device=dev)   # (every row is written; P == 0: nothing to write)
+            _lib.check(lib.nrc_gs_backward_absgrad_band(
+                P, D, M, W, H, None, _lib.ptr(means3D), _lib.ptr(sh if has_sh else None), _lib.ptr(sh_rest if has_rest else None), int(raw),
+                _lib.ptr(opac if raw else None), _lib.ptr(col if has_col else None),
+                _lib.ptr(sc if has_sr else None), float(rs.scale_modifier), _lib.ptr(rot if has_sr else None), _lib.ptr(cov if has_cov else None),
+                None, None, None, _lib.ptr(cam_block), float(rs.tanfovx), float(rs.tanfovy), _lib.ptr(radii), _lib.ptr(points_xy), _lib.ptr(conic_opacity),
+                _lib.ptr(rgb), _lib.ptr(clamped), _lib.ptr(cov3D), _lib.ptr(point_list), _lib.ptr(ranges), _lib.ptr(splat), _lib.ptr(tile_order), _lib.ptr(n_contrib), _lib.ptr(final_T),
+                _lib.ptr(g), _lib.ptr(dmean2D), None, _lib.ptr(dopacity), _lib.ptr(dcolor), _lib.ptr(dmean3D), _lib.ptr(dcov3D),
+                _lib.ptr(dsh), _lib.ptr(dsh_rest), _lib.ptr(dscale), _lib.ptr(drot), _lib.ptr(grad_records), int(records_clear), b0, bn, _lib.ptr(g_aux),
+                _lib.ptr(partials), _lib.ptr(dcam), _lib.ptr(dabs) if P > 0 else None, _lib.stream_of(g)), 'gs_backward_absgrad_band')
+            target = ctx.absgrad()
+            if target is not None:
+                # like .grad it accumulates: two bands rendered on one leaf sum to the frame
+                have = getattr(target, 'absgrad', None)
+                if torch.is_tensor(have) and have.shape == dabs.shape and have.dtype == f32 and have.device == dabs.device:
+                    have.add_(dabs)
+                else:
+                    target.absgrad = dabs
+        elif ctx.camera is not None:
             # the same backward with two extra launches between the blend backward and the per-Gaussian backward: dL/d(viewmatrix | projmatrix | campos) as float[35]
             b0, bn = ctx.band if ctx.band is not None else (0, (H + 15) // 16)
             partials = torch.empty(int(lib.nrc_gs_pose_partials_floats(P)), dtype=f32, device=dev)
@@ -503,10 +538,13 @@ class _RasterizeGaussians(torch.autograd.Function):
         if not capturing and P > 0:   # (P == 0: the library returned before touching the uninitialised buffer -- it is NOT known to be zero)
             _GRAD_RECORDS[rec_key] = (n1, grad_records)   # only after a call that went through: a failed one leaves the entry popped (contents unknown)
         cut = (lambda t: t) if P == n1 else (lambda t: t[:P])     # (whole buffers when nothing is cut: a gradient that is not a view can be adopted as .grad without a copy)
-        return (cut(dmean3D), cut(dmean2D), cut(dsh) if has_sh else None, cut(dcolor) if has_col else None,
-                cut(dopacity).reshape(ctx.opacity_shape), cut(dscale) if has_sr else None, cut(drot) if has_sr else None,
-                cut(dcov3D) if has_cov else None, None, cut(dsh_rest) if dsh_rest is not None else None, None, None, None, None) + _camera_grads(ctx.camera, dcam, feat is not None) \
+        grads = (cut(dmean3D), cut(dmean2D), cut(dsh) if has_sh else None, cut(dcolor) if has_col else None,
+                 cut(dopacity).reshape(ctx.opacity_shape), cut(dscale) if has_sr else None, cut(drot) if has_sr else None,
+                 cut(dcov3D) if has_cov else None, None, cut(dsh_rest) if dsh_rest is not None else None, None, None, None, None) + _camera_grads(ctx.camera, dcam, feat is not None) \
             + (() if feat is None else (cut(dfeat) if dfeat is not None else None,))
+        if ctx.absgrad is not None:   # the call passed every input up to the flag: their positions are filled
+            grads += (None,) * (19 - len(grads))
+        return grads
 
 
 def _check_features(features, P: int, dev) -> torch.Tensor:
@@ -535,11 +573,25 @@ def _camera_grads(camera, dcam, placeholders=False):
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, sh_rest=None, raw=False, rest_step=None, tile_rows=None,
-                        return_depth_alpha=False, camera_grad=False, features=None):
+                        return_depth_alpha=False, camera_grad=False, features=None, absgrad=False):
     """`tile_rows` = (begin, n): render and differentiate the band of 16-pixel tile rows [begin, begin + n) only (see GaussianRasterizer.forward); None: the frame.
     `return_depth_alpha`: (image, radii, depth, alpha) instead of (image, radii) -- see GaussianRasterizer.forward.
     `camera_grad`: gradients to raster_settings.viewmatrix / projmatrix / campos, for those that require grad -- see GaussianRasterizer.forward.
-    `features`: a (P, C) tensor blended by the colour's weights; appends feature_map (C, H, W) to the outputs -- see GaussianRasterizer.forward."""
+    `features`: a (P, C) tensor blended by the colour's weights; appends feature_map (C, H, W) to the outputs -- see GaussianRasterizer.forward.
+    `absgrad`: the backward also leaves sum_pixels |dL_pixel/dmean2D| as means2D.absgrad -- see GaussianRasterizer.forward."""
+    if absgrad:
+        if rest_step is not None:
+            raise RuntimeError('absgrad together with rest_step: the backward pass that steps the `rest` SH tensor (nrc_gs_backward_rest_step) takes the '
+                               'colour gradient only -- there is no absgrad form of it; render without rest_step and let the optimizer take that step')
+        if features is not None:
+            raise RuntimeError('absgrad together with features: the feature backward (nrc_gs_backward_features_band) forms its share of dL/dalpha in another kernel, '
+                               'and |a + b| per pixel cannot be assembled from two kernels\' sums -- there is no absgrad form of it; render the features in a call of their own')
+        rs = raster_settings
+        pose = (None, None, None)
+        if camera_grad and torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in (rs.viewmatrix, rs.projmatrix, rs.campos)):
+            pose = (rs.viewmatrix, rs.projmatrix, rs.campos)
+        return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, sh_rest, raw, None,
+                                         None if tile_rows is None else tuple(int(v) for v in tile_rows), bool(return_depth_alpha), *pose, None, True)
     if features is not None:
         if rest_step is not None:
             raise RuntimeError('features together with rest_step: the backward pass that steps the `rest` SH tensor (nrc_gs_backward_rest_step) takes the '
@@ -644,7 +696,7 @@ class GaussianRasterizer(torch.nn.Module):
             return z > 0.2
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, shs_rest=None,
-                raw_parameters=False, rest_step=None, tile_rows=None, return_depth_alpha=False, camera_grad=False, features=None):
+                raw_parameters=False, rest_step=None, tile_rows=None, return_depth_alpha=False, camera_grad=False, features=None, absgrad=False):
         """The reference's call (Renderer.py:75-81) plus two keyword extensions for callers that own the model tensors: `shs_rest` -- `shs` is then
         (`rest_step`, round 6: an object whose take() returns (parameter, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, bc1, bc2) -- the backward pass then applies
         the optimizer's Adam step to shs_rest itself and returns no gradient for it: nerficg_amd.gaussian_splatting.RestStep)
@@ -674,7 +726,15 @@ class GaussianRasterizer(torch.nn.Module):
         backward launch is skipped, `features.grad` is exact zeros).  The pass is one extra launch on the state the colour pass left (no second preprocess, sort
         or binning) and one more in the backward; image, radii and everything the backward saves are bit for bit those of the call without `features`.  Works with
         every parameter form above, with `tile_rows` (the band's rows and the band's share), `return_depth_alpha`, `camera_grad` and inside fixed_capacity; not
-        together with `rest_step` (RuntimeError).  A wrong type, shape, dtype, device or C raises ValueError / RuntimeError naming `features`."""
+        together with `rest_step` (RuntimeError).  A wrong type, shape, dtype, device or C raises ValueError / RuntimeError naming `features`.
+        `absgrad=True`: after backward() the tensor object passed as `means2D` carries `means2D.absgrad`, a (P, 3) float32 tensor on its device: per Gaussian the
+        sum over the pixels that blended it of |dL_pixel/dmean2D| (x, y; column 2 zero) -- the addends of `means2D.grad[:, :2]` with the absolute value taken PER
+        PIXEL before any sum, in the units of `means2D.grad` (AbsGS; gsplat's absgrad).  The signed sum cancels where a large Gaussian blurs fine texture; this
+        one does not: it is the statistic to densify on, with a threshold of its own (it is never smaller than |grad|).  Exact zeros for culled Gaussians and
+        those no pixel blended.  Like `.grad` it ACCUMULATES: a backward that finds an `absgrad` of the right shape adds to it (the bands of a partition rendered
+        on one leaf sum to the frame's); delete or zero it between steps.  Outputs and every ordinary gradient are those of the call without the flag (same
+        per-Gaussian sums; float atomics in another order); without the flag nothing changes.  Works with every parameter form above, with `tile_rows`,
+        `return_depth_alpha`, `camera_grad` and inside fixed_capacity (no host read is added); not together with `rest_step` or `features` (RuntimeError)."""
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
         if ((scales is None or rotations is None) and cov3D_precomp is None) or ((scales is not None or rotations is not None) and cov3D_precomp is not None):
@@ -686,7 +746,7 @@ class GaussianRasterizer(torch.nn.Module):
         try:
             out = rasterize_gaussians(means3D, means2D, empty if shs is None else shs, empty if colors_precomp is None else colors_precomp, opacities,
                                       empty if scales is None else scales, empty if rotations is None else rotations,
-                                      empty if cov3D_precomp is None else cov3D_precomp, self.raster_settings, shs_rest, raw_parameters, rest_step, tile_rows, return_depth_alpha, camera_grad, features)
+                                      empty if cov3D_precomp is None else cov3D_precomp, self.raster_settings, shs_rest, raw_parameters, rest_step, tile_rows, return_depth_alpha, camera_grad, features, absgrad)
         finally:
             _FRAME_STATE_SINK[0] = previous
         self._frame_state = sink[-1] if sink else None   # what contributions() runs on: references to tensors the forward created anyway

@@ -450,10 +450,19 @@ class Gaussians(torch.nn.Module):
         return {'pruned': n_pruned, 'kept': P - n_pruned}
 
     @torch.no_grad()
-    def add_densification_stats(self, viewspace_point_tensor: torch.Tensor, visibility: torch.Tensor) -> None:
-        """Model.py:243-246.  `visibility`: the rasterizer's int32 radii (used as they are) or the boolean mask radii > 0."""
+    def add_densification_stats(self, viewspace_point_tensor: torch.Tensor, visibility: torch.Tensor, use_absgrad: bool = False) -> None:
+        """Model.py:243-246.  `visibility`: the rasterizer's int32 radii (used as they are) or the boolean mask radii > 0.
+        use_absgrad: accumulate the row norms of `viewspace_point_tensor.absgrad` (a frame rendered with absgrad=True, after backward()) instead of those of
+        `.grad`: sum_pixels |dL_pixel/dmean2D| does not cancel where a large Gaussian blurs fine texture (AbsGS).  The statistic is larger than the signed one,
+        so densify_and_prune wants a larger grad_threshold with it: the threshold stays the caller's."""
         from . import _lib
-        grad = viewspace_point_tensor.grad if viewspace_point_tensor.grad is not None else viewspace_point_tensor
+        if use_absgrad:
+            grad = getattr(viewspace_point_tensor, 'absgrad', None)
+            if not torch.is_tensor(grad):
+                raise RuntimeError('add_densification_stats: use_absgrad=True, but the viewspace tensor carries no .absgrad -- render the frame with absgrad=True '
+                                   '(render_image_training(..., absgrad=True)) and call backward() first')
+        else:
+            grad = viewspace_point_tensor.grad if viewspace_point_tensor.grad is not None else viewspace_point_tensor
         radii = visibility if visibility.dtype == torch.int32 else visibility.to(torch.int32)
         _lib.check_input(grad, 'viewspace gradient', torch.float32)
         _lib.check_input(radii, 'radii', torch.int32)
@@ -687,8 +696,10 @@ class RestStep:
 
 def render_image_training(gaussians: Gaussians, cam: PerspectiveCamera, c2w: np.ndarray, fuse_rest_step: bool | None = None,
                           band: tuple[int, int] | None = None, depth_alpha: bool = False, camera_grad: bool | None = None,
-                          features: torch.Tensor | None = None) -> dict[str, torch.Tensor]:
-    """GaussianSplatting/Renderer.py:51-86.  features: a (P, C) float32 tensor of the caller's (it is NOT carried through densification: the caller owns it); the
+                          features: torch.Tensor | None = None, absgrad: bool = False) -> dict[str, torch.Tensor]:
+    """GaussianSplatting/Renderer.py:51-86.  absgrad: after backward() outputs['viewspace_points'].absgrad holds sum_pixels |dL_pixel/dmean2D| per Gaussian, (P, 3)
+    with column 2 zero (the rasterizer's `absgrad`; Gaussians.add_densification_stats(..., use_absgrad=True) reads it).  The backward that steps f_rest has no
+    absgrad form: fuse_rest_step=None then resolves to "not fused", an explicit fuse_rest_step=True raises (RuntimeError).  features: a (P, C) float32 tensor of the caller's (it is NOT carried through densification: the caller owns it); the
     outputs gain 'features', (C, H, W), blended with the colour's weights and differentiable to the tensor and the geometry (the rasterizer's `features`) -- refused
     together with the fused f_rest step (RuntimeError), like depth_alpha.  camera_grad (default None: on exactly when `c2w` is a tensor that requires grad): the loss is differentiated with
     respect to the pose as well (the rasterizer's `camera_grad`; pose refinement, tracking against a frozen model) -- refused together with the fused f_rest step
@@ -704,6 +715,12 @@ def render_image_training(gaussians: Gaussians, cam: PerspectiveCamera, c2w: np.
     positions = gaussians.get_positions
     band = check_tile_rows(band, cam.height)
     fuse = getattr(gaussians, 'fuse_rest_step', False) if fuse_rest_step is None else bool(fuse_rest_step)
+    absgrad = bool(absgrad)
+    if absgrad:
+        if fuse_rest_step is not None and fuse:
+            raise RuntimeError('render_image_training: absgrad= together with the fused f_rest step -- the backward pass that steps f_rest takes the colour '
+                               'gradient only (the rasterizer refuses absgrad with rest_step); leave fuse_rest_step off for frames that collect the abs-gradient')
+        fuse = False
     if band is not None and fuse:
         raise RuntimeError('render_image_training: band= together with the fused f_rest step -- the backward pass of a band holds that band\'s share of the '
                            'gradient only, and Adam applied to a partial gradient is not the optimizer\'s step; sum the shares over the bands and step then')
@@ -724,12 +741,12 @@ def render_image_training(gaussians: Gaussians, cam: PerspectiveCamera, c2w: np.
     if gaussians.baked:  # a baked model holds activated values
         image, radii, *aux = rasterizer(means3D=positions, means2D=viewspace_points, shs=gaussians.get_features_dc, shs_rest=gaussians.get_features_rest,
                                         opacities=gaussians.get_opacities, scales=gaussians.get_scales, rotations=gaussians.get_rotations, tile_rows=band,
-                                        return_depth_alpha=depth_alpha, camera_grad=camera_grad, features=features)
+                                        return_depth_alpha=depth_alpha, camera_grad=camera_grad, features=features, absgrad=absgrad)
     else:  # raw parameters straight into the kernels: no get_features concatenation, no separate exp / sigmoid / normalize passes (a25)
         rest_step = RestStep(gaussians) if fuse and not getattr(gaussians.optimizer, 'capturable', False) and not torch.cuda.is_current_stream_capturing() and torch.is_grad_enabled() and gaussians._features_rest.requires_grad and gaussians._features_rest.shape[1] > 0 and torch.is_tensor(c2w) else None
         image, radii, *aux = rasterizer(means3D=positions, means2D=viewspace_points, shs=gaussians._features_dc, shs_rest=gaussians._features_rest,
                                         opacities=gaussians._opacities, scales=gaussians._scales, rotations=gaussians._rotations, raw_parameters=True, rest_step=rest_step,
-                                        tile_rows=band, return_depth_alpha=depth_alpha, camera_grad=camera_grad, features=features)
+                                        tile_rows=band, return_depth_alpha=depth_alpha, camera_grad=camera_grad, features=features, absgrad=absgrad)
     outputs = _TrainingOutputs({'rgb': image, 'viewspace_points': viewspace_points, 'radii': radii})
     if depth_alpha:
         outputs.update(_depth_alpha_outputs(aux[0], aux[1], True))
