@@ -680,7 +680,8 @@ int nrc_ngp_encode_samples(const float* ts, const int32_t* row_tile, const float
 /* stage 3b on its own (the MFMA kernel; bench.py's second roofline object): features as written by nrc_ngp_encode_samples for the same
  * n_rows (<= 131072) rows -> packed (h0, r, g, b) fp16 of the FRAME (indexed by the frame's slots); ray_sh_workspace: n_ray_tiles * 2048 bytes,
  * filled by this call with the rays' SH coefficients; n_ray_tiles = 0: it holds them already (they belong to the image, a caller looping over
- * chunks fills it once) */
+ * chunks fills it once).  Only the records of SAMPLES are written: the record of a hole (t < 0) and the records of a finished tile's rows
+ * (row_tile = -1 - tile) keep what they held, as do the features of such rows in nrc_ngp_encode_samples (a hole's features are all zero) */
 int nrc_ngp_mlp_samples(const float* ts, const int32_t* row_tile, const float* ray_od, int64_t first_row, int64_t n_rows, int64_t n_ray_tiles,
                         const void* features_f16, const void* density_weights_f16, const void* color_weights_f16,
                         void* packed_f16, void* ray_sh_workspace, const int32_t* arena_tile_off, int32_t arena_rows, nrc_stream_t stream);

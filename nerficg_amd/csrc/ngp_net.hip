@@ -279,6 +279,13 @@ __device__ __forceinline__ int64_t ts_slot(const QueryIn& in, int64_t i, int32_t
 }
 // row_tile entry -> ray tile (finished tiles' rows hold -1 - tile)
 __device__ __forceinline__ int32_t tile_of(int32_t rt) { return rt < 0 ? -1 - rt : rt; }
+// (o + t d) - mn with one f32 rounding per operation.  Plain operators under `contract(off)`: __fadd_rn(o, __fmul_rn(t, d)) is `o + t * d` in this
+// toolchain's headers and, inlined into a unit compiled with the default contraction, became ONE v_fmac_f32 -- a single rounding, up to an ulp away
+// from the positions the op-by-op path and the training path feed the same table (tests/test_gpu_frame_stages.py found it on oblique rays)
+__device__ __forceinline__ float ray_point(float o, float t, float d, float mn) {
+#pragma clang fp contract(off)
+    return (o + t * d) - mn;
+}
 // 1: a sample; 0: a hole of the tiled layout (no sample in this slot); -1: a row of a finished tile (slab order): nothing of it is read or written
 template <int SRC, bool UNIFORM_ROW = true>
 __device__ __forceinline__ int fetch_pos(const QueryIn& in, int64_t i, float& px, float& py, float& pz) {
@@ -299,9 +306,9 @@ __device__ __forceinline__ int fetch_pos(const QueryIn& in, int64_t i, float& px
         if (t < 0.f) { px = py = pz = 0.f; return 0; }
         const float* od = in.ray_od + (int64_t)rt * 384 + (i & 63);  // per-tile SoA [6][64]
         // same roundings as the op-by-op path: xyz = o + t*d (mul, add: raymarching.cu:368), then (xyz - min) / size in torch
-        px = __fsub_rn(__fadd_rn(od[0], __fmul_rn(t, od[192])), in.mn[0]);
-        py = __fsub_rn(__fadd_rn(od[64], __fmul_rn(t, od[256])), in.mn[1]);
-        pz = __fsub_rn(__fadd_rn(od[128], __fmul_rn(t, od[320])), in.mn[2]);
+        px = ray_point(od[0], t, od[192], in.mn[0]);
+        py = ray_point(od[64], t, od[256], in.mn[1]);
+        pz = ray_point(od[128], t, od[320], in.mn[2]);
         if (in.sz[0] != 1.0f || in.sz[1] != 1.0f || in.sz[2] != 1.0f) {  // x / 1.0f == x exactly: skip the IEEE division for the unit box
             px = __fdiv_rn(px, in.sz[0]); py = __fdiv_rn(py, in.sz[1]); pz = __fdiv_rn(pz, in.sz[2]);
         }
@@ -741,10 +748,12 @@ __global__ void __launch_bounds__(256, NRC_MLP_WAVES) k_ngp_mlp(QueryIn in, int6
         ti.b1 = fp[((2 + hh + rot) & 3) * 32];
         ti.alive = 1u;
         if constexpr (SRC == SRC_TILED) {
-            // (no look at the sample's t: a hole of the layout -- 4 % of the slots -- carries the encoder's all-zero features, runs through the
-            // networks like any other slot and its output is never read (the compositor walks a ray's k < ray_cnt rows only); the 4-byte load per
-            // slot and, on arena frames, the scalar load of tile_off in front of it cost more than the holes' arithmetic)
-            ti.t = 0.f;
+            // the sample's t decides whether the slot's record is STORED: a hole of the layout (t < 0, 4 % of the slots) carries the encoder's all-zero
+            // features and runs through the networks like any other slot, but its record belongs to the caller and stays as it was (the contract of
+            // nrc_ngp_mlp_samples / nrc_ngp_query_samples; tests/test_gpu_frame_stages.py).  Dropping this load -- 4 B per slot and, on arena frames,
+            // the scalar load of tile_off in front of it -- had measured 0.181-0.186 -> 0.172-0.179 ms per launch and wrote a record into every hole.
+            // k_ngp_mlp_composite, the kernel of the single-pass frame, stores no records and never read t here.
+            ti.t = in.ts[ts_slot(in, i, rt)];   // (rt is wave-uniform here: tile_off[rt] is one scalar load)
             // (contiguous rows per wave: the next row mostly belongs to the same ray tile -- its SH fragment is in registers already)
             if (same_ray_tile) ti.sh = same_ray_tile->sh;
             else ti.sh = ray_sh[((int64_t)rt * 2 + hh) * 64 + (i & 63)];

@@ -1,6 +1,6 @@
 """A float64 restatement, an exactness proof and a per-element error budget for the fully fused MLP (nerficg_amd/csrc/ngp_net.hip: k_nwie_fwd, k_nwie_bwd;
 C ABI nrc_nwie_forward / nrc_nwie_backward, include/nerficg_hip.h).  Plain module: no test functions.  Used by tests/test_mlp_ref_cpu.py and
-tests/test_gpu_mlp_grad.py.
+tests/test_gpu_mlp_grad.py; tests/frame_stage_ref.py takes the forward half (`forward_budget`) for the image frame's two networks.
 
 The restatement
 ---------------
@@ -281,10 +281,10 @@ def _dw_bound(dZ, EdZ, P, EP, old, ls):
     return (cross + gamma32(n + 2) * (a.T @ b)) / ls + gamma32(n + 2) * np.abs(old)
 
 
-def budget(X, W, g, y, loss_scale, n_hidden, out_act, n_out_rows=16, old=None, E_X=None):
-    """Per-element bounds of the module docstring.  y: the `out` the backward call is GIVEN (an input of the call: no bound of its own).
-    Returns dict(out=(lo, hi) fp16 interval per output, dW=flat bound, d_in=(M,32) bound, fw=..., dW_ref=..., d_in_ref=...)."""
-    ls = float(loss_scale)
+def forward_budget(X, W, n_hidden, out_act, n_out_rows=16, E_X=None):
+    """The forward half of `budget`: the restated forward pass and, layer by layer, the bound E on |device - restated| of every activation, from the bound
+    E_X (M,32) on the inputs (None: exact inputs).  Returns dict(fw=..., Hs=[X, H_0, ...], Es=[E_X, E_0, ...], flips=[units whose ReLU mask the device may
+    see either way, per layer], e_out=bound on Z_out in front of the conversion, out=(lo, hi) fp16 interval per output, out_ref=the restated output)."""
     Ws, Wo = layers(W, n_hidden, n_out_rows)
     fw = forward(X, W, n_hidden, out_act, n_out_rows)
     E = np.zeros_like(fw['X']) if E_X is None else np.asarray(E_X, np.float64)
@@ -299,6 +299,16 @@ def budget(X, W, g, y, loss_scale, n_hidden, out_act, n_out_rows=16, old=None, E
             out_iv = (h16_down(1.0 / (1.0 + np.exp(-(fw['Zout'] - eo)))), h16_up(1.0 / (1.0 + np.exp(-(fw['Zout'] + eo)))))
     else:
         out_iv = (h16(fw['Zout'] - eo), h16(fw['Zout'] + eo))
+    return dict(fw=fw, Hs=Hs, Es=Es, flips=flips, e_out=eo, out=out_iv, out_ref=fw['out'])
+
+
+def budget(X, W, g, y, loss_scale, n_hidden, out_act, n_out_rows=16, old=None, E_X=None):
+    """Per-element bounds of the module docstring.  y: the `out` the backward call is GIVEN (an input of the call: no bound of its own).
+    Returns dict(out=(lo, hi) fp16 interval per output, dW=flat bound, d_in=(M,32) bound, fw=..., dW_ref=..., d_in_ref=...)."""
+    ls = float(loss_scale)
+    Ws, Wo = layers(W, n_hidden, n_out_rows)
+    fb = forward_budget(X, W, n_hidden, out_act, n_out_rows, E_X)
+    fw, Hs, Es, flips, out_iv = fb['fw'], fb['Hs'], fb['Es'], fb['flips'], fb['out']
     # backward
     oldf = np.zeros(n_weights(n_hidden)) if old is None else np.asarray(old, np.float64).reshape(-1)
     offs = np.cumsum([0] + [w.size for w in Ws])
