@@ -56,7 +56,8 @@ enum {
  * 21 = group 22 (nrc_gs_contributions_band: per-Gaussian contribution statistics of a rendered view) is new, every earlier signature is unchanged;
  * 22 = nrc_ngp_set_encoder_vertex_levels / _vertex_view, nrc_ngp_vertex_view_bytes, nrc_ngp_build_vertex_view (group 6: the vertex view of the leading
  * hashed levels) are new, every earlier signature is unchanged.  Added under 22 without a bump (additive: no earlier signature, record slot or default
- * launch changes): group 23, nrc_gs_backward_absgrad_band -- slots [10], [11] of a gradient record carry sum_pixels |dL_pixel/dmean2D| in that call only. */
+ * launch changes): group 23, nrc_gs_backward_absgrad_band -- slots [10], [11] of a gradient record carry sum_pixels |dL_pixel/dmean2D| in that call only;
+ * group 24, nrc_adam_step_rows_multi -- the visibility-masked Adam step, a new entry in a translation unit of its own. */
 #define NRC_ABI_VERSION 22
 /* library identification; also used by the loader's symbol check */
 int nrc_abi_version(void);
@@ -1335,6 +1336,28 @@ int nrc_gs_backward_absgrad_band(int32_t P, int32_t D, int32_t M, int32_t W, int
                     float* dL_dcov3D, float* dL_dsh, float* dL_dsh_rest, float* dL_dscale, float* dL_drot, float* grad_records,
                     int32_t records_clear, int32_t tile_row_begin, int32_t n_tile_rows, const float* dL_ddepth_alpha, float* pose_partials,
                     float* dL_dcamera, float* dL_dmean2D_abs, nrc_stream_t stream);
+
+/* =====================================================================================================
+ * Group 24 -- the visibility-masked Adam step (csrc/adam_rows.hip: k_adam_rows).  The sparse step of Taming-3DGS, of 3DGS `--optimizer_type sparse_adam`
+ *            (SparseGaussianAdam.step(visibility, N)) and of gsplat's SelectiveAdam: a Gaussian that the frame did not see keeps its parameters and both
+ *            moments, every other row gets the ordinary update.  Added under ABI version 22 without a bump (additive, like group 23).
+ *
+ *   nrc_adam_step_rows_multi : up to 12 tensors in ONE launch, tensor k contiguous f32 of shape (n_rows, row_widths[k]), all sharing the row mask `visible`.
+ *            The calling convention of nrc_adam_step_multi (group 8): params / grads / exp_avg / exp_avg_sq are HOST arrays of n_tensors device pointers;
+ *            row_widths / lrs / bc1 / bc2 are HOST arrays (bc = the bias corrections 1 - beta^t, or 1).  visible is a DEVICE array of n_rows entries:
+ *            visible_kind 0 = uint8 / bool, non-zero = visible; 1 = int32 radii as the rasterizer returns them, > 0 = visible.
+ *            Row r visible: every element of row r of every tensor gets nrc_adam_update of csrc/adam_math.h (no L2 slice, inv_scale = 1) -- bit for bit what
+ *            nrc_adam_step_multi does to it; weight decay (either mode) therefore acts on visible rows only.
+ *            Row r invisible: its parameters, exp_avg and exp_avg_sq keep their bits, whatever its gradient holds (NaN and inf included).
+ *            The work item is four consecutive floats; one none of whose elements is visible issues no load and no store of the four streams; inside a
+ *            touched one the elements of invisible rows are written back as read.  16-byte accesses where all four pointers of a tensor are 16-byte
+ *            aligned, single floats otherwise.  Element indices are 64-bit: n_rows * width may pass 2^31.  Nothing else may write the tensors meanwhile.
+ *   NRC_ERR_INVALID before any HIP call: a null array or a null `visible`; n_tensors outside 1..12; a width <= 0; n_rows < 0; a visible_kind other than
+ *            0 / 1; a bias correction <= 0; with n_rows > 0 a null tensor pointer.  n_rows == 0: NRC_OK, nothing is launched.
+ * ===================================================================================================== */
+int nrc_adam_step_rows_multi(int32_t n_tensors, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                             const int32_t* row_widths, int64_t n_rows, const void* visible, int32_t visible_kind, const float* lrs, const float* bc1,
+                             const float* bc2, float beta1, float beta2, float eps, float weight_decay, int32_t adam_w_mode, nrc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,9 @@ betas, adam_w_mode, weight_decay, bias_correction).
   read from a device scalar per group, so a step recorded in a HIP graph (nerficg_amd.graphs) keeps counting on replay; after changing
   group['lr'] (a scheduler) call `sync_hyperparameters()` between replays;
 * a parameter that belongs to a nerficg_amd.tinycudann module gets its fp16 compute copy rewritten by the same kernel and its version
-  counter bumped, so the next forward can neither see stale weights nor pay a separate conversion pass.
+  counter bumped, so the next forward can neither see stale weights nor pay a separate conversion pass;
+* `step(visibility=mask)` (not in apex; 3DGS `sparse_adam`, gsplat `SelectiveAdam`): rows that the (P,) mask calls invisible keep their values and
+  both moments, the other rows get the same update as in the dense step (nerficg_amd/csrc/adam_rows.hip, group 24).
 Kernel: nerficg_amd/csrc/adam.hip through the C ABI (include/nerficg_hip.h group 8).
 """
 from __future__ import annotations
@@ -281,15 +283,100 @@ class FusedAdam(torch.optim.Optimizer):
             torch.autograd.graph.increment_version(r[0])
         return True
 
+    def _step_rows(self, visibility) -> None:
+        """step(visibility=...): the visibility-masked step (nrc_adam_step_rows_multi, include/nerficg_hip.h group 24).  Every check runs before any state is
+        created, any counter advanced or any launch made; the counters and bias corrections are those of _step_multi (one per group, global count)."""
+        todo = [(group, p) for group in self.param_groups for p in group['params'] if p.grad is not None]
+        if not todo:       # e.g. right after densify_and_prune: fresh parameters, and a mask of the old length -- skipped silently like the dense step
+            return
+        if not torch.is_tensor(visibility):
+            raise ValueError(f'FusedAdam.step: visibility must be a tensor of shape (P,), got {type(visibility).__name__}')
+        if visibility.dtype not in (torch.bool, torch.uint8, torch.int32):
+            raise ValueError(f'FusedAdam.step: visibility must have dtype torch.bool, torch.uint8 or torch.int32 (the rasterizer\'s radii), got {visibility.dtype}')
+        if visibility.dim() != 1 or not visibility.is_contiguous():
+            raise ValueError(f'FusedAdam.step: visibility must be a contiguous tensor of shape (P,), got shape {tuple(visibility.shape)}')
+        if self.capturable:
+            raise RuntimeError('FusedAdam.step: visibility= is not implemented for a capturable optimizer (the masked step takes host step counts)')
+        if getattr(self, 'grad_scale', None) is not None or getattr(self, 'found_inf', None) is not None:
+            raise RuntimeError('FusedAdam.step: visibility= together with a GradScaler (grad_scale / found_inf are set) is not implemented')
+        P = visibility.shape[0]
+        names = {id(p): f"parameter {k} of group {gi} ({group.get('name', 'unnamed')})"
+                 for gi, group in enumerate(self.param_groups) for k, p in enumerate(group['params'])}
+        for group, p in todo:
+            who = names[id(p)]
+            if not p.is_cuda or p.device != visibility.device:
+                raise RuntimeError(f'FusedAdam.step(visibility=): {who} must be a CUDA tensor on the device of visibility ({p.device} / {visibility.device})')
+            if p.grad.is_sparse or p.grad.layout != torch.strided:
+                raise RuntimeError(f'FusedAdam.step(visibility=): {who} has a sparse gradient; a dense float32 gradient is needed')
+            if p.dtype != torch.float32 or p.grad.dtype != torch.float32:
+                raise RuntimeError(f'FusedAdam.step(visibility=): {who} and its gradient must be float32, got {p.dtype} / {p.grad.dtype}')
+            if not p.is_contiguous() or not p.grad.is_contiguous():
+                raise RuntimeError(f'FusedAdam.step(visibility=): {who} and its gradient must be contiguous')
+            if p.dim() < 1 or p.shape[0] != P:
+                raise ValueError(f'FusedAdam.step(visibility=): {who} has shape {tuple(p.shape)}, visibility has {P} rows')
+            if getattr(p, '_nrc_half_owner', None) is not None:
+                raise RuntimeError(f'FusedAdam.step(visibility=): {who} has an fp16 compute copy, which the masked step does not write')
+            if self._l2_slice_of(p)[0]:
+                raise RuntimeError(f'FusedAdam.step(visibility=): {who} has an L2 slice, which the masked step does not carry')
+            state = self.state.get(p)
+            if state:
+                for name in ('exp_avg', 'exp_avg_sq'):
+                    t = state.get(name)
+                    if (not torch.is_tensor(t) or t.dtype != torch.float32 or t.device != p.device or not t.is_contiguous() or t.shape != p.shape):
+                        raise RuntimeError(f'FusedAdam.step(visibility=): {name} of {who} must be a contiguous float32 tensor of the parameter\'s shape and device')
+        lib = _lib.load()
+        stepped = set()
+        batches: dict = {}       # (betas, eps, weight_decay) -> rows, in the order of first appearance
+        for group, p in todo:
+            if id(group) not in stepped:       # like apex: one step counter per group, advanced whenever the group has gradients
+                if torch.is_tensor(group.get('step')):   # the group was stepped in capturable mode before
+                    group['step'] = int(group['step'].item())
+                group['step'] = group.get('step', 0) + 1
+                stepped.add(id(group))
+            state = self.state[p]
+            if len(state) == 0:
+                state['exp_avg'] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+                state['exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            beta1, beta2 = group['betas']
+            bc = (1.0 - beta1 ** group['step'], 1.0 - beta2 ** group['step']) if group['bias_correction'] else (1.0, 1.0)
+            key = (float(beta1), float(beta2), float(group['eps']), float(group['weight_decay']))
+            if p.numel() > 0:
+                batches.setdefault(key, []).append((p, p.grad, state['exp_avg'], state['exp_avg_sq'], float(group['lr']), bc))
+        kind = 1 if visibility.dtype == torch.int32 else 0
+        cast = lambda a: ctypes.cast(a, ctypes.c_void_p)
+        for (beta1, beta2, eps, weight_decay), all_rows in batches.items():
+            for start in range(0, len(all_rows), 12):
+                rows = all_rows[start:start + 12]
+                n = len(rows)
+                ptrs = lambda k: cast((ctypes.c_void_p * n)(*[r[k].data_ptr() for r in rows]))
+                widths = (ctypes.c_int32 * n)(*[r[0].numel() // P for r in rows])
+                lrs = (ctypes.c_float * n)(*[r[4] for r in rows])
+                bc1 = (ctypes.c_float * n)(*[r[5][0] for r in rows])
+                bc2 = (ctypes.c_float * n)(*[r[5][1] for r in rows])
+                _lib.check(lib.nrc_adam_step_rows_multi(n, ptrs(0), ptrs(1), ptrs(2), ptrs(3), cast(widths), P, _lib.ptr(visibility), kind, cast(lrs), cast(bc1),
+                                                        cast(bc2), beta1, beta2, eps, weight_decay, self.adam_w_mode, _lib.stream_of(rows[0][0])),
+                           'adam_step_rows_multi')
+        for _, p in todo:
+            torch.autograd.graph.increment_version(p)
+
     def zero_grad(self, set_to_none: bool | None = None):
         super().zero_grad(set_to_none=self.set_grad_none if set_to_none is None else set_to_none)
 
     @torch.no_grad()
-    def step(self, closure=None):
+    def step(self, closure=None, *, visibility=None):
+        """visibility (keyword only, default None: the dense step): a (P,) tensor on the parameters' device, torch.bool / torch.uint8 (non-zero = visible) or
+        torch.int32 (the rasterizer's radii as they are, > 0 = visible).  Rows of every parameter (all of shape (P, ...)) that the mask calls invisible keep
+        their values and both moments bit for bit, whatever their gradient holds; every other row gets the ordinary update, weight decay included.  The step
+        counters and bias corrections stay global (one per group, as in the dense step): no per-row step count is kept.  Not with `capturable`, a GradScaler,
+        an fp16 compute copy or an L2 slice; every parameter with a gradient must be contiguous float32 on the device (RuntimeError / ValueError before
+        anything is modified).  A call in which no parameter has a gradient returns at once, whatever the mask."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        if visibility is not None:
+            self._step_rows(visibility)
+            return loss
         lib = _lib.load()
         grad_scale = getattr(self, 'grad_scale', None)
         found_inf = getattr(self, 'found_inf', None)

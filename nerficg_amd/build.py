@@ -32,6 +32,7 @@ GS_BLEND_FLAGS = ['-ffp-contract=off', '-fno-slp-vectorize', '-mllvm', '-amdgpu-
 PER_FILE_FLAGS = {
     'ngp_march.hip': ['-ffp-contract=off'],
     'adam.hip': ['-ffp-contract=off'],
+    'adam_rows.hip': ['-ffp-contract=off'],    # the masked step includes adam_math.h: the same bits as adam.hip's dense step on every visible row
     'knn.hip': ['-ffp-contract=off'],
     'gs_densify.hip': ['-ffp-contract=off'],   # thresholds decide the row list: same f32 sequence as oracle/gs_densify.py   # squared distances decide the neighbour set: same f32 sequence as oracle/knn_oracle.c
   # HBM-bound anyway; keeps the update bit-identical to oracle/adam_oracle.c

@@ -359,9 +359,17 @@ class Gaussians(torch.nn.Module):
     def training_setup(self, LEARNING_RATE_POSITION_INIT: float = 0.00016, LEARNING_RATE_POSITION_FINAL: float = 0.0000016,
                        LEARNING_RATE_POSITION_MAX_STEPS: int = 30000, LEARNING_RATE_FEATURE: float = 0.0025, LEARNING_RATE_OPACITY: float = 0.05,
                        LEARNING_RATE_SCALING: float = 0.005, LEARNING_RATE_ROTATION: float = 0.001, PERCENT_DENSE: float = 0.01,
-                       training_cameras_extent: float | None = None, optimizer_class=None, capturable: bool = False) -> None:
+                       training_cameras_extent: float | None = None, optimizer_class=None, capturable: bool = False, sparse_adam: bool = False,
+                       bias_correction: bool = True) -> None:
         """Six single-tensor groups in the reference's order and names; FusedAdam(lr=0, eps=1e-15, adam_w_mode=False) over the HIP step.
-        capturable: step counters and learning rates on the device, for steps recorded in a HIP graph (nerficg_amd.graphs)."""
+        capturable: step counters and learning rates on the device, for steps recorded in a HIP graph (nerficg_amd.graphs).
+        sparse_adam (default False: the dense step, nothing changes): `optimizer_step(radii)` updates only the Gaussians the frame saw (radii > 0); the others
+        keep their parameters and both moments untouched instead of decaying them -- Taming-3DGS, 3DGS `--optimizer_type sparse_adam`, gsplat `SelectiveAdam`.
+        Another optimisation trajectory than the dense step, hence opt-in; it needs the library's FusedAdam (RuntimeError with `optimizer_class`) and excludes
+        the in-backward f_rest step, which is dense over all rows (render_image_training).
+        bias_correction (passed to FusedAdam; default True, as before): the published sparse kernels apply no bias correction; False selects that formula in
+        this project's own operation order (csrc/adam_math.h with bc = 1).  The result equals the published kernels' within rounding, not bit for bit: they
+        round (-lr m) / (sqrt(v) + eps), this step rounds lr (m / (sqrt(v) + eps)).  Ignored with `optimizer_class`."""
         from .lr_utils import LRDecayPolicy
         if training_cameras_extent is not None:
             self.training_cameras_extent = training_cameras_extent
@@ -371,13 +379,28 @@ class Gaussians(torch.nn.Module):
                  'opacities': LEARNING_RATE_OPACITY, 'scales': LEARNING_RATE_SCALING, 'rotations': LEARNING_RATE_ROTATION}
         # one single-tensor group per attribute, in the order and under the names the reference's optimizer-state surgery looks up (Model.py:121-130)
         param_groups = [{'name': name, 'lr': rates[name], 'params': [getattr(self, attr)]} for name, attr in self._GROUP_OF.items()]
+        if sparse_adam and optimizer_class is not None:
+            raise RuntimeError('training_setup: sparse_adam=True needs the library\'s FusedAdam (its step(visibility=...)); leave optimizer_class unset')
+        self.sparse_adam = bool(sparse_adam)
         if optimizer_class is None:
             from .apex_optimizers import FusedAdam
-            self.optimizer = FusedAdam(param_groups, lr=0.0, eps=1e-15, adam_w_mode=False, capturable=capturable)
+            self.optimizer = FusedAdam(param_groups, lr=0.0, eps=1e-15, adam_w_mode=False, capturable=capturable, bias_correction=bias_correction)
         else:
             self.optimizer = optimizer_class(param_groups, lr=0.0, eps=1e-15)
         self.position_lr_scheduler = LRDecayPolicy(lr_init=LEARNING_RATE_POSITION_INIT * ext, lr_final=LEARNING_RATE_POSITION_FINAL * ext,
                                                    max_steps=LEARNING_RATE_POSITION_MAX_STEPS)
+
+    def optimizer_step(self, radii: torch.Tensor | None = None) -> None:
+        """The optimizer's step of one iteration.  With training_setup(sparse_adam=True): `radii` is the frame's out['radii'] (or any (P,) bool / uint8 / int32
+        mask; a band or data-parallel caller passes the mask that covers every contribution to the summed gradient, e.g. the union of the band_masks) and only
+        its visible rows are stepped; leaving it out raises -- a silent dense step would be a different optimizer.  Otherwise the dense step."""
+        if getattr(self, 'sparse_adam', False):
+            if radii is None:
+                raise RuntimeError('optimizer_step: this model was set up with sparse_adam=True -- pass the frame\'s radii (out[\'radii\']); a dense step here would '
+                                   'be a different optimizer')
+            self.optimizer.step(visibility=radii)
+        else:
+            self.optimizer.step()
 
     def update_learning_rate(self, iteration: int) -> None:
         rate = self.position_lr_scheduler(iteration)
@@ -699,7 +722,8 @@ def render_image_training(gaussians: Gaussians, cam: PerspectiveCamera, c2w: np.
                           features: torch.Tensor | None = None, absgrad: bool = False) -> dict[str, torch.Tensor]:
     """GaussianSplatting/Renderer.py:51-86.  absgrad: after backward() outputs['viewspace_points'].absgrad holds sum_pixels |dL_pixel/dmean2D| per Gaussian, (P, 3)
     with column 2 zero (the rasterizer's `absgrad`; Gaussians.add_densification_stats(..., use_absgrad=True) reads it).  The backward that steps f_rest has no
-    absgrad form: fuse_rest_step=None then resolves to "not fused", an explicit fuse_rest_step=True raises (RuntimeError).  features: a (P, C) float32 tensor of the caller's (it is NOT carried through densification: the caller owns it); the
+    absgrad form: fuse_rest_step=None then resolves to "not fused", an explicit fuse_rest_step=True raises (RuntimeError).  The same holds for a model set up with
+    training_setup(sparse_adam=True): the in-backward f_rest step is dense over all rows, the masked step is Gaussians.optimizer_step(radii).  features: a (P, C) float32 tensor of the caller's (it is NOT carried through densification: the caller owns it); the
     outputs gain 'features', (C, H, W), blended with the colour's weights and differentiable to the tensor and the geometry (the rasterizer's `features`) -- refused
     together with the fused f_rest step (RuntimeError), like depth_alpha.  camera_grad (default None: on exactly when `c2w` is a tensor that requires grad): the loss is differentiated with
     respect to the pose as well (the rasterizer's `camera_grad`; pose refinement, tracking against a frozen model) -- refused together with the fused f_rest step
@@ -715,6 +739,11 @@ def render_image_training(gaussians: Gaussians, cam: PerspectiveCamera, c2w: np.
     positions = gaussians.get_positions
     band = check_tile_rows(band, cam.height)
     fuse = getattr(gaussians, 'fuse_rest_step', False) if fuse_rest_step is None else bool(fuse_rest_step)
+    if getattr(gaussians, 'sparse_adam', False):
+        if fuse_rest_step is not None and fuse:
+            raise RuntimeError('render_image_training: fuse_rest_step=True on a model set up with sparse_adam -- the backward pass that steps f_rest steps every row, '
+                               'invisible ones included (a zero gradient still decays their moments); the masked step is optimizer_step(radii), leave fuse_rest_step off')
+        fuse = False
     absgrad = bool(absgrad)
     if absgrad:
         if fuse_rest_step is not None and fuse:

@@ -66,6 +66,9 @@ if gcstats:
 nistats = sorted(glob.glob(str(RAW / 'nerf_input_grad_stats' / '*' / '*kernel_stats.csv')), key=os.path.getmtime)   # tools/bench_nerf_input_grad.py: a pose-refinement iteration
 if nistats:
     shutil.copy(nistats[-1], OUT / f'{ROUND}_nerf_input_grad_kernel_stats.csv')
+sastats = sorted(glob.glob(str(RAW / 'sparse_adam_stats' / '*' / '*kernel_stats.csv')), key=os.path.getmtime)   # tools/bench_sparse_adam.py --profile: the masked Adam launch, one known mask
+if sastats:
+    shutil.copy(sastats[-1], OUT / f'{ROUND}_sparse_adam_kernel_stats.csv')
 # one accumulator per collection run: pmc_* = tools/bench_query.py (InstantNGP image pipeline), pmcgs_* = tools/bench_gs.py (3DGS frame),
 # pmctr_* = tools/bench_train.py (InstantNGP training iteration).  A kernel that appears in several of them (k_grid_encode runs in the image
 # pipeline with 8 Mi-slot launches and in training with 264 K samples) is reported from the run that is about it.
