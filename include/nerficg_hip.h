@@ -57,7 +57,9 @@ enum {
  * 22 = nrc_ngp_set_encoder_vertex_levels / _vertex_view, nrc_ngp_vertex_view_bytes, nrc_ngp_build_vertex_view (group 6: the vertex view of the leading
  * hashed levels) are new, every earlier signature is unchanged.  Added under 22 without a bump (additive: no earlier signature, record slot or default
  * launch changes): group 23, nrc_gs_backward_absgrad_band -- slots [10], [11] of a gradient record carry sum_pixels |dL_pixel/dmean2D| in that call only;
- * group 24, nrc_adam_step_rows_multi -- the visibility-masked Adam step, a new entry in a translation unit of its own. */
+ * group 24, nrc_adam_step_rows_multi -- the visibility-masked Adam step, a new entry in a translation unit of its own; group 25,
+ * nrc_ngp_set_encoder_ypair_levels / _ypair_view, nrc_ngp_ypair_view_bytes, nrc_ngp_build_ypair_view -- the y-pair view of the leading hashed levels, read
+ * only by a call that was handed one. */
 #define NRC_ABI_VERSION 22
 /* library identification; also used by the loader's symbol check */
 int nrc_abi_version(void);
@@ -674,6 +676,28 @@ int nrc_ngp_build_vertex_view(const void* table_f16, int32_t n_levels, int32_t l
                               void* view, nrc_stream_t stream);
 int nrc_ngp_set_encoder_vertex_view(const void* view);
 int nrc_ngp_set_encoder_vertex_levels(int32_t levels);
+/* Group 25 -- y-pair view of the hashed levels that follow the block view's levels (at most 6 consecutive hashed levels, as long as the view stays below
+ * 1 GiB, and no more than the library reads by default, 5; the shipped grid: level 5 4.6 MB, 6 11.9, 7 30.4, 8 79.5, 9 209.6 = 335.9 MB): level by level a
+ * dense array of 8-byte records, record (x, y, z) in [0, R)^3 at index x + R * (y + R * z), R = res + 2, holding the table entries the spatial hash
+ * names for vertex (x, y, z) and for vertex (x, y + 1, z); the records of the row y = res + 1 are never read and hold zeros.  One 16-byte load at the
+ * record of a sample's cell returns the four corners of a z-plane, so the image encoder reads a level as two loads of one address instead of the vertex
+ * view's four or the table's four, a predicated round of four more and the hash.  The features are identical with and without the view for every
+ * sample inside the model box; a position outside it gets meaningless features either way, and not the same ones (the view clamps the cell
+ * coordinates to res).  A buffer of its own: the block view and the vertex view, their sizes and their functions are what they were.  A level that a
+ * call reads through the y-pair view is not read through the vertex view, so a caller whose y-pair view holds the vertex view's levels needs no
+ * vertex view.
+ *   nrc_ngp_ypair_view_bytes  : size of the view of a grid (0: no level qualifies; < 0: an error code)
+ *   nrc_ngp_build_ypair_view  : fills `view` from table_f16 -- again whenever the table's VALUES change (one gather pass over the view)
+ *   nrc_ngp_set_encoder_ypair_view : as nrc_ngp_set_encoder_block_view -- for the NEXT call of the four entry points on the calling host thread, taken
+ *       by that call whichever way it ends, never checked, NULL or no call = the vertex view or the table.
+ *   nrc_ngp_set_encoder_ypair_levels : how many of the view's levels the encoder reads through it (0 .. 6; the levels a view does not hold are read
+ *       from the vertex view or the table whatever is asked for), -1: the library's default, the measured best.  A setting of the CALLING HOST
+ *       THREAD; it exists for tests and measurements, the renderer does not call it. */
+int64_t nrc_ngp_ypair_view_bytes(int32_t n_levels, int32_t log2_hashmap_size, int32_t base_resolution, float per_level_scale);
+int nrc_ngp_build_ypair_view(const void* table_f16, int32_t n_levels, int32_t log2_hashmap_size, int32_t base_resolution, float per_level_scale,
+                             void* view, nrc_stream_t stream);
+int nrc_ngp_set_encoder_ypair_view(const void* view);
+int nrc_ngp_set_encoder_ypair_levels(int32_t levels);
 int nrc_ngp_encode_samples(const float* ts, const int32_t* row_tile, const float* ray_od, int64_t first_row, int64_t n_rows, const float* xyz_min3,
                            const float* xyz_size3, const void* table_f16, int32_t n_levels, int32_t log2_hashmap_size,
                            int32_t base_resolution, float per_level_scale, void* features_f16, const int32_t* arena_tile_off,

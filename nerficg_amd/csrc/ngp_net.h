@@ -59,6 +59,23 @@ struct VertexView {
     uint32_t R[NRC_ENC_VERTEX_MAX];          // vertices per axis
 };
 
+// Y-pair view of the hashed levels that follow the block view's levels (image encoder only): level begin + i, i < levels, as a dense array of 8-byte
+// records, record (x, y, z) in [0, R)^3 at index x + R * (y + R * z) behind byte first[i] of the view, R = res + 2, holding {fp16 pair of vertex (x, y, z),
+// fp16 pair of vertex (x, y + 1, z)}.  A vertex array cannot go below four lookups per level (the y-neighbour sits a row away); here ONE 16-byte load at
+// record (gx, gy, gz) returns the four corners of a z-plane -- (x, y), (x, y + 1), (x + 1, y), (x + 1, y + 1) -- so a level costs two lookups, the block
+// view's count, at 8 bytes per vertex instead of 32 per cell (grid_level_features_ypair).  The records of the row y = res + 1 are never read (a cell
+// coordinate is clamped to res) and hold zeros.  A separate buffer and kernel argument: the two other views are what they were.  Built by
+// k_build_ypair_view whenever the table is refreshed.
+#define NRC_ENC_YPAIR_MAX 6                    // levels a view holds at most: levels 5-10 of the shipped grid (res 81 .. 407) are 883.2 MB
+#define NRC_ENC_YPAIR_MAX_BYTES (1u << 30)     // ... and the view of any other grid stops in front of the level that would pass this (offsets stay in 32 bits)
+struct YPairView {
+    const void* ptr;                        // nullptr: no view
+    uint32_t bytes;
+    int32_t begin, levels;                  // levels begin <= l < begin + levels read the view
+    uint32_t first[NRC_ENC_YPAIR_MAX + 1];  // byte offset of the level's first record; [levels] = bytes
+    uint32_t R[NRC_ENC_YPAIR_MAX];          // records per axis
+};
+
 __device__ __forceinline__ f16v zero16() {
     f16v z;
 #pragma unroll
@@ -377,6 +394,25 @@ __device__ __forceinline__ void grid_level_features_vertex(__amdgpu_buffer_rsrc_
     const auto c = __builtin_amdgcn_raw_buffer_load_b64(view, vtx << 2, first_byte + plane, 0);
     const auto d = __builtin_amdgcn_raw_buffer_load_b64(view, vtx << 2, first_byte + plane + row, 0);
     const uint32_t v[8] = {a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
+    f0 = 0.f; f1 = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; k++) fma_half2(w[k], v[k], f0, f1);
+}
+
+// hashed levels through the y-pair view (YPairView): ONE record address from the cell (the vertex form's three v_min and two multiply-adds) and TWO
+// 16-byte loads, one per z-plane; the level's first byte and the plane stride 8 R^2 ride in the loads' scalar offsets.  A load at record (gx, gy, gz)
+// returns records gx and gx + 1 of the row: {(x, y), (x, y + 1)}, {(x + 1, y), (x + 1, y + 1)} = corners k0, k2, k1, k3 of Corner8 (k4, k6, k5, k7 in
+// the next plane).  Same fp16 values, same weights, same FMA order k = 0 .. 7 as grid_level_features_hashed: identical features for every position
+// whose cell lies in [0, res]^3; outside the box the cell is clamped, as for the two other views.  The loads are 8-byte aligned (16-byte only for even
+// gx); buffer loads of a dword or more ask for dword alignment only.  gx <= res, so record gx + 1 <= res + 1 = R - 1 stays in the row, and gy <= res
+// never reaches the zero row y = res + 1.
+__device__ __forceinline__ void grid_level_features_ypair(__amdgpu_buffer_rsrc_t view, uint32_t first_byte, uint32_t gx, uint32_t gy, uint32_t gz,
+                                                          uint32_t res, uint32_t R, const float (&w)[8], float& f0, float& f1) {
+    const uint32_t rec = __umul24(__umul24(min(gz, res), R) + min(gy, res), R) + min(gx, res);
+    const uint32_t plane = __umul24(R, R) << 3;   // (scalar)
+    const auto lo = __builtin_amdgcn_raw_buffer_load_b128(view, rec << 3, first_byte, 0);
+    const auto hi = __builtin_amdgcn_raw_buffer_load_b128(view, rec << 3, first_byte + plane, 0);
+    const uint32_t v[8] = {lo[0], lo[2], lo[1], lo[3], hi[0], hi[2], hi[1], hi[3]};
     f0 = 0.f; f1 = 0.f;
 #pragma unroll
     for (int k = 0; k < 8; k++) fma_half2(w[k], v[k], f0, f1);

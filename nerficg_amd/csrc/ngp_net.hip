@@ -335,7 +335,7 @@ __device__ __forceinline__ void fetch_dir(const QueryIn& in, int64_t i, float& d
 template <int SRC>
 __global__ void __launch_bounds__(256) k_grid_encode(QueryIn in, int64_t base, int64_t n, const __half2* __restrict__ table, GridCfg g,
                                                          uint4* __restrict__ feat, int narrow_levels, int lvl_range, int lane_shape = 0, int xcd_run = 0,
-                                                         BlockView bv = BlockView{}, VertexView vv = VertexView{}) {
+                                                         BlockView bv = BlockView{}, VertexView vv = VertexView{}, YPairView yv = YPairView{}) {
     int64_t bid = blockIdx.x;
     if constexpr (SRC == SRC_TILED) {
         // workgroups are dealt round-robin over the 8 XCDs; each XCD takes a CONTIGUOUS eighth of a range of slots instead of every eighth
@@ -394,6 +394,7 @@ __global__ void __launch_bounds__(256) k_grid_encode(QueryIn in, int64_t base, i
     const __amdgpu_buffer_rsrc_t trs = make_table_rsrc(table, g.total_entries * 4u);
     const __amdgpu_buffer_rsrc_t vrs = make_table_rsrc(bv.ptr, bv.bytes);   // (SRC_TILED: the cell-block view of levels < bv.levels, see BlockView)
     const __amdgpu_buffer_rsrc_t xrs = make_table_rsrc(vv.ptr, vv.bytes);   // (SRC_TILED: the vertex view of levels vv.begin .. + vv.levels, see VertexView)
+    const __amdgpu_buffer_rsrc_t yrs = make_table_rsrc(yv.ptr, yv.bytes);   // (SRC_TILED: the y-pair view of levels yv.begin .. + yv.levels, see YPairView)
     uint4* out = feat + ((j >> 5) * 4) * 32 + (j & 31);
     const int rot = (int)((j >> 5) & 3);
     const int lvl_lo = lvl_range & 0xff, lvl_hi = (lvl_range >> 8) & 0xff;   // NRC_ENC_LEVELS (measurement only; 0 .. 16 normally)
@@ -414,6 +415,10 @@ __global__ void __launch_bounds__(256) k_grid_encode(QueryIn in, int64_t base, i
                     uint32_t gx, gy, gz;
                     grid_cell(px, py, pz, g.scale[level], gx, gy, gz, c.w);
                     grid_level_features_block(vrs, bv.first[level], gx, gy, gz, g.res[level], c.w, f0, f1);
+                } else if (SRC == SRC_TILED && level >= yv.begin && level < yv.begin + yv.levels) {   // (hashed levels behind the block view's: ypair_view_cfg)
+                    uint32_t gx, gy, gz;
+                    grid_cell(px, py, pz, g.scale[level], gx, gy, gz, c.w);
+                    grid_level_features_ypair(yrs, yv.first[level - yv.begin], gx, gy, gz, g.res[level], yv.R[level - yv.begin], c.w, f0, f1);
                 } else if (SRC == SRC_TILED && level >= vv.begin && level < vv.begin + vv.levels) {   // (hashed levels behind the block view's: vertex_view_cfg)
                     uint32_t gx, gy, gz;
                     grid_cell(px, py, pz, g.scale[level], gx, gy, gz, c.w);
@@ -507,6 +512,23 @@ __global__ void __launch_bounds__(256) k_build_vertex_view(const uint32_t* __res
     Corner8 c;
     grid_corners_u<true>((float)x / scale, (float)y / scale, (float)z / scale, scale, g.res[level], g.size[level], g.offset[level], c);
     view[v] = table[c.e[0]];
+}
+
+// Fills the y-pair view (YPairView) from the fp16 table: one thread per record.  The entries are corners 0 and 2 -- (x, y, z) and (x, y + 1, z) -- of the
+// cell grid_corners_u<true> finds for a position on the vertex: the hash is the encoder's own, stated nowhere else.  The row y = R - 1 is zero.
+__global__ void __launch_bounds__(256) k_build_ypair_view(const uint32_t* __restrict__ table, GridCfg g, YPairView yv, uint2* __restrict__ view) {
+    const uint32_t rec = blockIdx.x * 256u + threadIdx.x;
+    if (rec >= yv.bytes / 8u) return;
+    int i = 0;
+    while (i + 1 < yv.levels && rec >= yv.first[i + 1] / 8u) i++;
+    const int level = yv.begin + i;
+    const uint32_t r = rec - yv.first[i] / 8u, R = yv.R[i];
+    const uint32_t x = r % R, y = r / R % R, z = r / (R * R);
+    if (y == R - 1u) { view[rec] = make_uint2(0u, 0u); return; }
+    const float scale = g.scale[level];   // >= 1 (ypair_view_cfg): fmaf(scale, x / scale, 0.5f) lies within a rounding of x + 0.5
+    Corner8 c;
+    grid_corners_u<true>((float)x / scale, (float)y / scale, (float)z / scale, scale, g.res[level], g.size[level], g.offset[level], c);
+    view[rec] = make_uint2(table[c.e[0]], table[c.e[2]]);
 }
 
 // SH degree 4 of the ray direction as the colour net's k-step-0 B fragments, once per RAY of the tiled layout:
@@ -1087,6 +1109,32 @@ void vertex_view_cfg(const GridCfg& g, int n_levels, VertexView& vv) {
     for (int k = i; k <= NRC_ENC_VERTEX_MAX; k++) vv.first[k] = (uint32_t)bytes;
 }
 
+// The levels a y-pair view of this grid holds, and where: the consecutive hashed levels that follow the block view's levels, at most NRC_ENC_YPAIR_LEVELS
+// of them -- the measured default: a level the encoder would not read is not held, so its memory is not paid -- while the view stays below
+// NRC_ENC_YPAIR_MAX_BYTES.  (scale >= 1: the builder places its position by a division by the scale.)  yv.ptr stays null.
+#ifndef NRC_ENC_YPAIR_LEVELS
+#define NRC_ENC_YPAIR_LEVELS 5   // 0 .. NRC_ENC_YPAIR_MAX; measured: 0, 4, 5, 6 -- LABBOOK R30
+#endif
+static_assert(NRC_ENC_YPAIR_LEVELS >= 0 && NRC_ENC_YPAIR_LEVELS <= NRC_ENC_YPAIR_MAX, "NRC_ENC_YPAIR_LEVELS");
+void ypair_view_cfg(const GridCfg& g, int n_levels, YPairView& yv) {
+    BlockView bv;
+    block_view_cfg(g, n_levels, bv);
+    yv = YPairView{};
+    yv.begin = bv.levels;
+    uint64_t bytes = 0;
+    int i = 0;
+    for (; i < NRC_ENC_YPAIR_LEVELS && yv.begin + i < n_levels && g.hashed[yv.begin + i] && g.scale[yv.begin + i] >= 1.f; i++) {
+        const uint64_t R = (uint64_t)g.res[yv.begin + i] + 2u, level_bytes = R * R * R * 8u;
+        if (bytes + level_bytes > NRC_ENC_YPAIR_MAX_BYTES) break;
+        yv.first[i] = (uint32_t)bytes;
+        yv.R[i] = (uint32_t)R;
+        bytes += level_bytes;
+    }
+    yv.levels = i;
+    yv.bytes = (uint32_t)bytes;
+    for (int k = i; k <= NRC_ENC_YPAIR_MAX; k++) yv.first[k] = (uint32_t)bytes;
+}
+
 int pick_blocks(int64_t M) {
     // every workgroup stages the network's weight fragments in LDS (24 KB) before its first tile: few workgroups with several tiles per wave beat
     // one tile per wave (cap on the number of workgroups: 512 below 1 Mi samples, 2 048 above)
@@ -1163,9 +1211,28 @@ static VertexView vertex_view_of(const void* view, const GridCfg& g, int n_level
     if (!vv.ptr || vv.levels <= 0) { vv.ptr = nullptr; vv.levels = 0; }
     return vv;
 }
+// The y-pair view of the table (YPairView), handed over and taken like the two other views: nrc_ngp_set_encoder_ypair_view for the calling thread's NEXT
+// frame entry point, gone whichever way that call ends.  nrc_ngp_set_encoder_ypair_levels: how many of the view's levels are read there,
+// -1 = NRC_ENC_YPAIR_LEVELS; per host thread.  A level the y-pair view serves is not read through the vertex view.
+static thread_local const void* g_enc_ypair_view = nullptr;
+static thread_local int g_enc_ypair_levels_override = -1;
+static const void* take_ypair_view() {
+    const void* view = g_enc_ypair_view;
+    g_enc_ypair_view = nullptr;
+    return view;
+}
+static YPairView ypair_view_of(const void* view, const GridCfg& g, int n_levels) {
+    YPairView yv;
+    ypair_view_cfg(g, n_levels, yv);
+    const int want = g_enc_ypair_levels_override >= 0 ? g_enc_ypair_levels_override : NRC_ENC_YPAIR_LEVELS;
+    yv.ptr = view;
+    if (want < yv.levels) yv.levels = want;   // (the levels behind it stay in the view, unread)
+    if (!yv.ptr || yv.levels <= 0) { yv.ptr = nullptr; yv.levels = 0; }
+    return yv;
+}
 template <int SRC>
 static void launch_encode(const QueryIn& in, int64_t base, int64_t n, const void* table, const GridCfg& g, uint4* feat, hipStream_t s,
-                          const BlockView& bv = BlockView{}, const VertexView& vv = VertexView{}) {
+                          const BlockView& bv = BlockView{}, const VertexView& vv = VertexView{}, const YPairView& yv = YPairView{}) {
     // levels whose cells are larger than a wave's footprint: narrow gathers (see grid_level_features_narrow)
     int narrow = 0;
     while (narrow < NRC_MAX_LEVELS && !g.hashed[narrow] && g.size[narrow] > 8) narrow++;
@@ -1192,7 +1259,7 @@ static void launch_encode(const QueryIn& in, int64_t base, int64_t n, const void
     const int lane_shape = (3 << 4) | 1;
     const int lanes = (SRC == SRC_TILED && (base & 1023) == 0) ? (g_enc_shape_override ? g_enc_shape_override : lane_shape) : 0;
     hipLaunchKernelGGL(k_grid_encode<SRC>, dim3((unsigned)(lanes ? 4 * nrc_cdiv(n, 1024) : nrc_cdiv(n, 256)), rows), dim3(256), 0, s, in, base, n, (const __half2*)table, g, feat,
-                       narrow, lvl_range, lanes, g_enc_xcd_run_override ? g_enc_xcd_run_override : NRC_ENC_XCD_RUN, bv, vv);
+                       narrow, lvl_range, lanes, g_enc_xcd_run_override ? g_enc_xcd_run_override : NRC_ENC_XCD_RUN, bv, vv, yv);
 }
 
 template <int SRC>
@@ -1207,7 +1274,7 @@ static void launch_mlp(const QueryIn& in, int64_t base, int64_t n, const void* f
 template <int SRC>
 static int run_query(const QueryIn& in, int64_t M, int64_t n_ray_tiles, const void* wd, const void* wc, const void* table, const GridCfg& g,
                      float* sigmas, float* rgbs, void* packed, void* workspace, hipStream_t s, const BlockView& bv = BlockView{},
-                     const VertexView& vv = VertexView{}) {
+                     const VertexView& vv = VertexView{}, const YPairView& yv = YPairView{}) {
     uint4* feat = (uint4*)workspace;
     h8* ray_sh = (h8*)((char*)workspace + query_feat_bytes(M));
     if constexpr (SRC == SRC_TILED)
@@ -1216,7 +1283,7 @@ static int run_query(const QueryIn& in, int64_t M, int64_t n_ray_tiles, const vo
     NRC_STAGE(s, nullptr);      // (armed stage timer: the two kernels of every chunk IN the frame's own sequence -- bench.py's in-frame ruler)
     for (int64_t base = 0; base < M; base += NRC_QUERY_CHUNK) {
         const int64_t n = (M - base) < NRC_QUERY_CHUNK ? (M - base) : NRC_QUERY_CHUNK;
-        launch_encode<SRC>(in, base, n, table, g, feat, s, bv, vv);
+        launch_encode<SRC>(in, base, n, table, g, feat, s, bv, vv, yv);
         NRC_STAGE(s, "k_grid_encode");
         launch_mlp<SRC>(in, base, n, feat, ray_sh, wd, wc, sigmas, rgbs, packed, s);
         NRC_STAGE(s, "k_ngp_mlp");
@@ -1406,6 +1473,38 @@ int nrc_ngp_build_vertex_view(const void* table_f16, int32_t n_levels, int32_t l
     NRC_LAUNCH_CHECK();
     return NRC_OK;
 }
+int nrc_ngp_set_encoder_ypair_levels(int32_t levels) {
+    if (levels < -1 || levels > NRC_ENC_YPAIR_MAX) return NRC_ERR_INVALID;
+    g_enc_ypair_levels_override = levels;
+    return NRC_OK;
+}
+int nrc_ngp_set_encoder_ypair_view(const void* view) {
+    g_enc_ypair_view = view;
+    return NRC_OK;
+}
+int64_t nrc_ngp_ypair_view_bytes(int32_t n_levels, int32_t log2_hashmap_size, int32_t base_resolution, float per_level_scale) {
+    GridCfg g;
+    const int rc = make_grid_cfg(n_levels, log2_hashmap_size, base_resolution, per_level_scale, g, nullptr);
+    if (rc != NRC_OK) return rc;
+    YPairView yv;
+    ypair_view_cfg(g, n_levels, yv);
+    return (int64_t)yv.bytes;
+}
+int nrc_ngp_build_ypair_view(const void* table_f16, int32_t n_levels, int32_t log2_hashmap_size, int32_t base_resolution, float per_level_scale,
+                             void* view, nrc_stream_t stream) {
+    NRC_ENTER();
+    GridCfg g;
+    const int rc = make_grid_cfg(n_levels, log2_hashmap_size, base_resolution, per_level_scale, g, nullptr);
+    if (rc != NRC_OK) return rc;
+    YPairView yv;
+    ypair_view_cfg(g, n_levels, yv);
+    if (yv.bytes == 0) return NRC_OK;
+    if (!table_f16 || !view) return NRC_ERR_INVALID;
+    hipLaunchKernelGGL(k_build_ypair_view, dim3((unsigned)nrc_cdiv((int64_t)(yv.bytes / 8u), 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const uint32_t*)table_f16, g, yv, (uint2*)view);
+    NRC_LAUNCH_CHECK();
+    return NRC_OK;
+}
 int nrc_ngp_encode_samples(const float* ts, const int32_t* row_tile, const float* ray_od, int64_t first_row, int64_t n_rows, const float* xyz_min3,
                            const float* xyz_size3, const void* table_f16, int32_t n_levels, int32_t log2_hashmap_size,
                            int32_t base_resolution, float per_level_scale, void* features_f16, const int32_t* arena_tile_off, int32_t arena_rows,
@@ -1413,6 +1512,7 @@ int nrc_ngp_encode_samples(const float* ts, const int32_t* row_tile, const float
     NRC_ENTER();
     const void* view = take_block_view();
     const void* vview = take_vertex_view();
+    const void* yview = take_ypair_view();
     const int64_t n = n_rows * 64;
     if (n_rows < 0 || first_row < 0 || n > NRC_QUERY_CHUNK || !table_f16 || !xyz_min3 || !xyz_size3) return NRC_ERR_INVALID;
     if ((arena_tile_off != nullptr) != (arena_rows > 0) || arena_rows < 0) return NRC_ERR_INVALID;
@@ -1426,7 +1526,7 @@ int nrc_ngp_encode_samples(const float* ts, const int32_t* row_tile, const float
     in.ts = ts; in.row_tile = row_tile; in.ray_od = ray_od; in.tile_off = arena_tile_off; in.arena_rows = arena_rows;
     for (int k = 0; k < 3; k++) { in.mn[k] = xyz_min3[k]; in.sz[k] = xyz_size3[k]; }
     launch_encode<SRC_TILED>(in, first_row * 64, n, table_f16, g, (uint4*)features_f16, (hipStream_t)stream, block_view_of(view, g, n_levels),
-                             vertex_view_of(vview, g, n_levels));
+                             vertex_view_of(vview, g, n_levels), ypair_view_of(yview, g, n_levels));
     NRC_LAUNCH_CHECK();
     return NRC_OK;
 }
@@ -1458,6 +1558,7 @@ int nrc_ngp_query_samples(const float* ts, int32_t* row_tile, const float* ray_o
     NRC_ENTER();
     const void* view = take_block_view();
     const void* vview = take_vertex_view();
+    const void* yview = take_ypair_view();
     const int64_t M = n_rows * 64;
     if ((arena_tile_off != nullptr) != (arena_rows > 0) || arena_rows < 0) return NRC_ERR_INVALID;
     if (n_rows < 0 || n_ray_tiles < 0 || !density_weights_f16 || !color_weights_f16 || !table_f16 || !xyz_min3 || !xyz_size3) return NRC_ERR_INVALID;
@@ -1472,7 +1573,7 @@ int nrc_ngp_query_samples(const float* ts, int32_t* row_tile, const float* ray_o
     in.tile_off = arena_tile_off; in.arena_rows = arena_rows;
     for (int k = 0; k < 3; k++) { in.mn[k] = xyz_min3[k]; in.sz[k] = xyz_size3[k]; }
     run_query<SRC_TILED>(in, M, n_ray_tiles, density_weights_f16, color_weights_f16, table_f16, g, nullptr, nullptr, packed_f16, workspace, (hipStream_t)stream,
-                         block_view_of(view, g, n_levels), vertex_view_of(vview, g, n_levels));
+                         block_view_of(view, g, n_levels), vertex_view_of(vview, g, n_levels), ypair_view_of(yview, g, n_levels));
     NRC_LAUNCH_CHECK();
     return NRC_OK;
 }
@@ -1497,6 +1598,7 @@ int nrc_ngp_render_layers(const float* ts, int32_t* row_tile, const float* ray_o
     NRC_ENTER();
     const void* view = take_block_view();
     const void* vview = take_vertex_view();
+    const void* yview = take_ypair_view();
     const int64_t M = n_rows * 64;
     if ((arena_row_k != nullptr) != (arena_rows > 0) || arena_rows < 0) return NRC_ERR_INVALID;
     if (n_rows < 0 || n_ray_tiles < 1 || !density_weights_f16 || !color_weights_f16 || !table_f16 || !xyz_min3 || !xyz_size3 || !bg3_host ||
@@ -1524,6 +1626,7 @@ int nrc_ngp_render_layers(const float* ts, int32_t* row_tile, const float* ray_o
     for (int k = 0; k < 3; k++) { in.mn[k] = xyz_min3[k]; in.sz[k] = xyz_size3[k]; }
     const BlockView bv = block_view_of(view, g, n_levels);
     const VertexView vv = vertex_view_of(vview, g, n_levels);
+    const YPairView yv = ypair_view_of(yview, g, n_levels);
     nrc_launch_layers_init(n_ray_tiles, ray_cnt, state, ray_alive, next_k, tile_alive, skipped_rows, s);
     hipLaunchKernelGGL(k_ray_sh, dim3((unsigned)nrc_cdiv(n_ray_tiles * 64, 256)), dim3(256), 0, s, ray_od, n_ray_tiles, ray_sh);
     // front to back: encode + MLP on a slab of rows, composite it, finished tiles drop out of the following slabs.  No host
@@ -1532,7 +1635,7 @@ int nrc_ngp_render_layers(const float* ts, int32_t* row_tile, const float* ray_o
     do {
         const int64_t cn = (M - base) < NRC_QUERY_CHUNK ? (M - base) : NRC_QUERY_CHUNK;
         if (cn > 0) {
-            launch_encode<SRC_TILED>(in, base, cn, table_f16, g, feat, s, bv, vv);
+            launch_encode<SRC_TILED>(in, base, cn, table_f16, g, feat, s, bv, vv, yv);
             launch_mlp<SRC_TILED>(in, base, cn, feat, ray_sh, density_weights_f16, color_weights_f16, nullptr, nullptr, packed_f16, s);
         }
         nrc_launch_composite_layers(packed_f16, ts, ray_cnt, tile_rows, tile_off, row_of, row_tile, (base + cn) / 64, width, height, tile_begin, n_ray_tiles, cascades,
@@ -1571,6 +1674,7 @@ int nrc_ngp_render_frame(const float* ts_arena, int32_t* row_tile, const float* 
     NRC_ENTER();
     const void* view = take_block_view();
     const void* vview = take_vertex_view();
+    const void* yview = take_ypair_view();
     const int64_t budget = frame_budget(row_budget);
     if (n_rows < 0 || n_ray_tiles < 1 || width < 1 || height < 1 || tile_begin < 0 || cascades < 1 || grid_size < 1 || max_samples < 1 ||
         budget < 2 * (int64_t)max_samples || !density_weights_f16 || !color_weights_f16 || !table_f16 || !xyz_min3 || !xyz_size3 || !bg3_host)
@@ -1607,6 +1711,7 @@ int nrc_ngp_render_frame(const float* ts_arena, int32_t* row_tile, const float* 
     const int64_t resident = (int64_t)(n_cu > 0 ? n_cu : 256) * NRC_MLP_WAVES, mlp_blocks = nrc_cdiv(n_ray_tiles, 4) < resident ? nrc_cdiv(n_ray_tiles, 4) : resident;
     const BlockView bv = block_view_of(view, g, n_levels);
     const VertexView vv = vertex_view_of(vview, g, n_levels);
+    const YPairView yv = ypair_view_of(yview, g, n_levels);
     NRC_STAGE(s, nullptr);
     // SH of every ray + the ray tile of every row (for the encoder)
     hipLaunchKernelGGL(k_ray_sh, dim3((unsigned)nrc_cdiv(n_ray_tiles * 64, 256)), dim3(256), 0, s, ray_od, n_ray_tiles, ray_sh, tile_off, row_tile, n_rows);
@@ -1617,7 +1722,7 @@ int nrc_ngp_render_frame(const float* ts_arena, int32_t* row_tile, const float* 
     for (int64_t c = 0; c < chunks; c++) {
         if (n_rows > 0) {
             in.chunk_rows = chunk_tab + 4 * c + 2;
-            launch_encode<SRC_TILED>(in, 0, feat_rows * 64, table_f16, g, feat, s, bv, vv);
+            launch_encode<SRC_TILED>(in, 0, feat_rows * 64, table_f16, g, feat, s, bv, vv, yv);
             NRC_STAGE(s, "k_grid_encode");
         }
         hipLaunchKernelGGL(k_ngp_mlp_composite, dim3((unsigned)mlp_blocks), dim3(256), 0, s, feat, ray_sh, (const __half*)density_weights_f16,

@@ -416,24 +416,30 @@ class InstantNGPRenderer:
     def _block_view_ptr(self):
         """The cell-block view of the grid's dense levels for the image encoder (tinycudann._block_view: built here if the fp16 table changed, valid
         from frame to frame otherwise) and the vertex view of the hashed levels behind them (tinycudann._vertex_view), as a pair.  Taken where a
-        frame's arguments are marshalled -- ahead of the wait for the row count."""
+        frame's arguments are marshalled -- ahead of the wait for the row count.  Third, the y-pair view of those hashed levels and further ones
+        (tinycudann._ypair_view): where it holds every level the vertex view would serve, the encoder reads none through the vertex view, and that one
+        is not allocated here."""
         enc = self.model.encoding_xyz
-        return _lib.ptr(enc._block_view()), _lib.ptr(enc._vertex_view())
+        block, ypair = enc._block_view(), enc._ypair_view()
+        vertex = None if enc._ypair_covers_vertex_view() else enc._vertex_view()
+        return _lib.ptr(block), _lib.ptr(vertex), _lib.ptr(ypair)
 
     @staticmethod
     def _frame_entry(fn, args, what: str, views) -> None:
-        """One of the library's frame entry points with the two views (_block_view_ptr) handed over in front of it (nrc_ngp_set_encoder_block_view /
-        _vertex_view: the call takes them).  Cleared behind the call as well: a call that never reached the library (an argument ctypes refuses) must
+        """One of the library's frame entry points with the three views (_block_view_ptr) handed over in front of it (nrc_ngp_set_encoder_block_view /
+        _vertex_view / _ypair_view: the call takes them).  Cleared behind the call as well: a call that never reached the library (an argument ctypes refuses) must
         not leave them to the next one."""
         lib = _lib.load()
-        block, vertex = views
+        block, vertex, ypair = views
         lib.nrc_ngp_set_encoder_block_view(block)
         lib.nrc_ngp_set_encoder_vertex_view(vertex)
+        lib.nrc_ngp_set_encoder_ypair_view(ypair)
         try:
             _lib.check(fn(*args), what)
         finally:
             lib.nrc_ngp_set_encoder_block_view(None)
             lib.nrc_ngp_set_encoder_vertex_view(None)
+            lib.nrc_ngp_set_encoder_ypair_view(None)
 
     def _fused_size_rows(self, ws: dict, rows: int, nt: int) -> None:
         if rows > ws['cap']:

@@ -23,6 +23,7 @@ from __future__ import annotations
 
 import ctypes
 import math
+import warnings
 import weakref
 
 import torch
@@ -227,6 +228,9 @@ class NetworkWithInputEncoding(torch.nn.Module):
         self._view_key = None
         self._vview = None      # _vertex_view
         self._vview_key = None
+        self._yview = None      # _ypair_view
+        self._yview_key = None
+        self._yview_refused = False   # the device had no room for the y-pair view once: not asked again
         self._half_captures = 0  # times the fp16 copy was handed to an optimizer step that a HIP graph was recording (_half_for_optimizer)
         # nerficg_amd.apex_optimizers.FusedAdam updates `params` through a raw pointer: it finds this module through the parameter and
         # has the step kernel rewrite the fp16 copy as well (_half_for_optimizer / _half_written_by_optimizer)
@@ -346,6 +350,51 @@ class NetworkWithInputEncoding(torch.nn.Module):
                 _lib.check(lib.nrc_ngp_build_vertex_view(_lib.ptr(self._table16()), *cfg, _lib.ptr(view), _lib.stream_of(view)), 'ngp_build_vertex_view')
             self._vview, self._vview_key = view, key
         return self._vview
+
+    def _ypair_view(self):
+        """Y-pair view of the hashed levels behind the block view's (include/nerficg_hip.h, nrc_ngp_build_ypair_view; levels 5-9 of the shipped grid: 336 MB),
+        owned like _vertex_view: allocated and built on first use, cached under the key of the fp16 copy, rebuilt (one gather pass over the view) when the
+        copy was, and None -- and freed -- where _block_view rebuilds for every frame or the frame is being recorded: those levels then read the vertex
+        view or the table.  A device without room for it is no error either: one warning, and the same fallback from then on.  None for a grid without
+        such levels."""
+        if self.encoding != 0 or not self.default_layout:
+            return None
+        if self._half_captures or torch.cuda.is_current_stream_capturing():
+            self._yview = self._yview_key = None
+            return None
+        self._refresh_half()
+        key = (self._half_key, self._half.data_ptr())
+        if self._yview_key != key:
+            lib, g = _lib.load(), self.grid_cfg
+            cfg = (g['n_levels'], g['log2_hashmap_size'], g['base_resolution'], float(g['per_level_scale']))
+            nbytes = int(lib.nrc_ngp_ypair_view_bytes(*cfg))
+            if nbytes < 0:
+                _lib.check(nbytes, 'ngp_ypair_view_bytes')
+            view = self._yview
+            if nbytes == 0 or self._yview_refused:
+                view = None
+            elif view is None or view.numel() != nbytes or view.device != self._half.device:
+                self._yview = view = None      # (the old one goes first: never two of them at a time)
+                try:
+                    view = torch.empty(nbytes, dtype=torch.uint8, device=self._half.device)
+                except torch.cuda.OutOfMemoryError:
+                    self._yview_refused = True
+                    warnings.warn(f'nerficg_amd.tinycudann: no room for the image encoder\'s y-pair view ({nbytes / 2 ** 20:.0f} MiB); '
+                                  'its levels are read through the vertex view or from the table', RuntimeWarning, stacklevel=2)
+            if view is not None:
+                _lib.check(lib.nrc_ngp_build_ypair_view(_lib.ptr(self._table16()), *cfg, _lib.ptr(view), _lib.stream_of(view)), 'ngp_build_ypair_view')
+            self._yview, self._yview_key = view, key
+        return self._yview
+
+    def _ypair_covers_vertex_view(self) -> bool:
+        """whether the y-pair view this module is holding serves every level its vertex view would serve.  Both begin at the first hashed level behind the
+        block view's and hold what the library reads by default, 8 and 4 bytes per vertex of the same levels: the one with at least as many levels is
+        the one with at least twice the bytes"""
+        if self._yview is None:
+            return False
+        lib, g = _lib.load(), self.grid_cfg
+        cfg = (g['n_levels'], g['log2_hashmap_size'], g['base_resolution'], float(g['per_level_scale']))
+        return self._yview.numel() >= 2 * int(lib.nrc_ngp_vertex_view_bytes(*cfg))
 
     @property
     def default_layout(self) -> bool:
