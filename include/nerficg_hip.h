@@ -59,7 +59,8 @@ enum {
  * launch changes): group 23, nrc_gs_backward_absgrad_band -- slots [10], [11] of a gradient record carry sum_pixels |dL_pixel/dmean2D| in that call only;
  * group 24, nrc_adam_step_rows_multi -- the visibility-masked Adam step, a new entry in a translation unit of its own; group 25,
  * nrc_ngp_set_encoder_ypair_levels / _ypair_view, nrc_ngp_ypair_view_bytes, nrc_ngp_build_ypair_view -- the y-pair view of the leading hashed levels, read
- * only by a call that was handed one. */
+ * only by a call that was handed one; group 26, nrc_ngp_set_frame_density_encoder -- the single-pass frame's kernel pair (the workspace of
+ * nrc_ngp_render_frame is what it was, the pictures are the same bits). */
 #define NRC_ABI_VERSION 22
 /* library identification; also used by the loader's symbol check */
 int nrc_abi_version(void);
@@ -721,7 +722,20 @@ int nrc_ngp_composite_image(const void* packed_f16, const float* ts, const int32
  * shard's pixels like nrc_ngp_composite_image.  Same pictures as steps 3 + 4, bit for bit (the per-sample step is shared).
  * The frame runs in chunks of WHOLE ray tiles of at most row_budget rows (<= 0: the library default, 2 Mi rows = one chunk for an 800x800
  * frame; otherwise >= 2 * max_samples); inside a chunk the tiles are processed longest first.  workspace:
- * nrc_ngp_render_frame_ws_bytes(n_rows, n_ray_tiles, max_samples, row_budget) bytes. */
+ * nrc_ngp_render_frame_ws_bytes(n_rows, n_ray_tiles, max_samples, row_budget) bytes.
+ * Group 26 -- which kernel pair the frame runs, nrc_ngp_set_frame_density_encoder(mode):
+ *   0: the 64-byte pair.  The encoder writes the 64 B of grid features of every slot (the records of nrc_ngp_encode_samples) and the MLP-composite
+ *      kernel runs the density net, its head and the colour net on them.
+ *   1: the density-encoder pair.  The encoder runs the density net on the samples it has just gathered for and writes the 16 fp16 density features,
+ *      32 B per slot: for the 32-sample tile T of a chunk (slots 32 T .. 32 T + 31) a 1 KB record, the 16-byte vector 64 T + 32 hh + r holding
+ *      features 8 hh .. 8 hh + 7 of slot 32 T + r; the MLP-composite kernel runs the colour net from there.  The records fill the first half of
+ *      the workspace's feature part.  Chunks of more than 2^24 rows run the 64-byte pair whatever is set.
+ *  -1: the library's default (a compile-time constant).
+ * The pictures are the same bit for bit: the same MFMAs on the same operands, only in another kernel.  A setting of the CALLING HOST THREAD, read by
+ * nrc_ngp_render_frame alone: nrc_ngp_render_frame_ws_bytes is what it was (64 B per slot), so a workspace serves either pair
+ * (InstantNGPRenderer sets the mode from FRAME_DENSITY_ENCODER in front of every frame).  No other entry point reads it: nrc_ngp_encode_samples /
+ * nrc_ngp_mlp_samples, the layered and the fixed-capacity frames and all training paths keep the 64-byte features. */
+int nrc_ngp_set_frame_density_encoder(int32_t mode);
 int64_t nrc_ngp_render_frame_ws_bytes(int64_t n_rows, int64_t n_ray_tiles, int32_t max_samples, int64_t row_budget);
 int nrc_ngp_render_frame(const float* ts_arena, int32_t* row_tile, const float* ray_od, int64_t n_rows, int64_t n_ray_tiles,
                          const float* xyz_min3, const float* xyz_size3, const void* density_weights_f16, const void* color_weights_f16,

@@ -332,10 +332,33 @@ __device__ __forceinline__ void fetch_dir(const QueryIn& in, int64_t i, float& d
 // per lane and needs no unpacking.  The group position inside a tile's 2 KB record rotates with the tile index: all waves
 // of the chip reach group g at about the same time, and un-rotated they would all write the same quarter of the memory
 // channels (measured: 0.262 ms vs 0.22 ms per 2 Mi samples).  One lane per sample, all 16 levels.
-template <int SRC>
-__global__ void __launch_bounds__(256) k_grid_encode(QueryIn in, int64_t base, int64_t n, const __half2* __restrict__ table, GridCfg g,
+//
+// DENS (the single-pass frame's density-encoder form, SRC_TILED): the wave keeps the four groups of its 64 samples in registers and runs the DENSITY
+// net on them itself (mlp_density_half, weights Wd staged in LDS: 6 KB per workgroup) as two 32-sample MFMA tiles, tile v = the samples on lanes
+// 32 v .. 32 v + 31 -- the columns of an MFMA are independent, so which sample sits in which column changes no bit.  What it stores is X1, the 16 fp16
+// density features, 32 B per sample instead of 64: the 16-byte vector
+//   feat[(j >> 5) * 64 + 32 hh + (j & 31)]   holds density features 8 hh .. 8 hh + 7 of slot j,
+// which is the 1 KB record of the 32-sample tile j >> 5 in the lane order of the MFMA wave that owns it (k_ngp_mlp_composite<true>: one coalesced
+// 16-byte load per lane and tile, no unpacking).  The records are not rotated over the memory channels.
+// MFMA and the lane swaps are wave-wide: no lane of such a wave leaves before the chain.  Slots behind n, holes and rows of finished tiles go through it
+// with all-zero features; what they are spared is the gathers and (slots behind n, finished rows) the stores.
+enum { MLP_F_D0 = 0, MLP_F_DO = 4, MLP_F_C0 = 8, MLP_F_C1 = 12, MLP_F_CO = 20, MLP_N_FRAG = 24 };
+__device__ __forceinline__ void mlp_stage_weights(h8 (*wlds)[64], const __half* __restrict__ Wd, const __half* __restrict__ Wc, int n_frag = MLP_N_FRAG);
+template <int NT>
+__device__ __forceinline__ void mlp_density_half(const h8 (*wlds)[64], const h8 (&B)[NT][2], h8 (&X1)[NT]);
+#ifndef NRC_ENC_DENS_WAVES
+#define NRC_ENC_DENS_WAVES 7   // waves per SIMD the density-encoder form's register budget is set for (workgroups per CU: a workgroup is one wave per SIMD).
+                               // 67 VGPRs, no scratch; without a budget the chain's accumulators go to AGPRs (68 + 32: 4 waves).  Measured, frame ms: 8 waves (64 VGPRs,
+                               // 20 B of scratch) 6.89, 7 waves 6.62, 7 waves' registers held to 6 / 5 waves by LDS padding 6.64 / 7.25 -- LABBOOK R31.2
+#endif
+template <int SRC, bool DENS = false>
+__global__ void __launch_bounds__(256, DENS ? NRC_ENC_DENS_WAVES : 0) k_grid_encode(QueryIn in, int64_t base, int64_t n, const __half2* __restrict__ table, GridCfg g,
                                                          uint4* __restrict__ feat, int narrow_levels, int lvl_range, int lane_shape = 0, int xcd_run = 0,
-                                                         BlockView bv = BlockView{}, VertexView vv = VertexView{}, YPairView yv = YPairView{}) {
+                                                         BlockView bv = BlockView{}, VertexView vv = VertexView{}, YPairView yv = YPairView{},
+                                                         const __half* __restrict__ Wd = nullptr) {
+    static_assert(!DENS || SRC == SRC_TILED, "the density-encoder form belongs to the tiled layout");
+    extern __shared__ h8 enc_wlds[][64];   // DENS: (MLP_F_DO + 2) * 1 KB of dynamic LDS, none otherwise
+    if constexpr (DENS) mlp_stage_weights(enc_wlds, Wd, nullptr, MLP_F_DO + 2);   // (read behind the barrier in front of the chain, not in front of the gathers)
     int64_t bid = blockIdx.x;
     if constexpr (SRC == SRC_TILED) {
         // workgroups are dealt round-robin over the 8 XCDs; each XCD takes a CONTIGUOUS eighth of a range of slots instead of every eighth
@@ -385,11 +408,17 @@ __global__ void __launch_bounds__(256) k_grid_encode(QueryIn in, int64_t base, i
             remapped = true;
         }
     }
-    if (j >= n || j < 0) return;
-    float px, py, pz;
+    const bool in_range = j < n && j >= 0;
+    if constexpr (!DENS) {
+        if (!in_range) return;
+    }
+    float px = 0.f, py = 0.f, pz = 0.f;
     if (blockIdx.y != 0) in.x01_out = nullptr;   // level groups split over workgroup rows: the first row writes the normalised positions
-    const int state = remapped ? fetch_pos<SRC, false>(in, base + j, px, py, pz) : fetch_pos<SRC>(in, base + j, px, py, pz);
-    if (state < 0) return;   // a row of a finished tile (slab order): the MLP kernel skips it too, nothing reads its features
+    int state = -1;
+    if (in_range) state = remapped ? fetch_pos<SRC, false>(in, base + j, px, py, pz) : fetch_pos<SRC>(in, base + j, px, py, pz);
+    if constexpr (!DENS) {
+        if (state < 0) return;   // a row of a finished tile (slab order): the MLP kernel skips it too, nothing reads its features
+    }
     const bool live = state > 0;
     const __amdgpu_buffer_rsrc_t trs = make_table_rsrc(table, g.total_entries * 4u);
     const __amdgpu_buffer_rsrc_t vrs = make_table_rsrc(bv.ptr, bv.bytes);   // (SRC_TILED: the cell-block view of levels < bv.levels, see BlockView)
@@ -401,6 +430,8 @@ __global__ void __launch_bounds__(256) k_grid_encode(QueryIn in, int64_t base, i
     // gridDim.y == 4: one group of four levels per workgroup row (small batches: four times the waves, a quarter of the dependent gathers each --
     // a 264 K-sample training batch is ~4 waves per SIMD in all and runs at the latency of ONE wave's sixteen gather rounds otherwise)
     const int grp_begin = gridDim.y == 4 ? (int)blockIdx.y : 0, grp_end = gridDim.y == 4 ? grp_begin + 1 : 4;
+    uint4 F[4] = {};   // DENS: the groups of this lane's sample, F[g] = group g behind the loop (each round shifts them down one place: the loop stays rolled
+                       // and no register is indexed by a loop variable)
 #pragma unroll 1
     for (int grp = grp_begin; grp < grp_end; grp++) {
         uint32_t v[4] = {0u, 0u, 0u, 0u};
@@ -441,7 +472,41 @@ __global__ void __launch_bounds__(256) k_grid_encode(QueryIn in, int64_t base, i
         }
         // (cache-policy variants of this store -- sc1, sc0 sc1, nt, so that the 64 B of features per sample would not take L2 lines from the hash
         // table -- measured 0.630-0.640 ms against 0.640: no effect, removed)
-        out[((grp + rot) & 3) * 32] = make_uint4(v[0], v[1], v[2], v[3]);
+        if constexpr (DENS) {
+            F[0] = F[1]; F[1] = F[2]; F[2] = F[3]; F[3] = make_uint4(v[0], v[1], v[2], v[3]);
+        } else {
+            out[((grp + rot) & 3) * 32] = make_uint4(v[0], v[1], v[2], v[3]);
+        }
+    }
+    if constexpr (DENS) {
+        const int lane = threadIdx.x & 63;
+        // B fragment of tile v, k-step s, lane half hh = group 2 s + hh of the sample on lane 32 v + (lane & 31): one v_permlane32_swap per dword trades
+        // the lower lanes' groups 1 and 3 for the upper lanes' groups 0 and 2.  swap(X, Y) = {[X lower | Y lower], [X upper | Y upper]}
+        h8 B[2][1][2];
+#pragma unroll
+        for (int s = 0; s < 2; s++) {
+            const uint4 x = F[2 * s], y = F[2 * s + 1];
+            const auto s0 = __builtin_amdgcn_permlane32_swap(x.x, y.x, false, false);
+            const auto s1 = __builtin_amdgcn_permlane32_swap(x.y, y.y, false, false);
+            const auto s2 = __builtin_amdgcn_permlane32_swap(x.z, y.z, false, false);
+            const auto s3 = __builtin_amdgcn_permlane32_swap(x.w, y.w, false, false);
+            const uint4 a = make_uint4(s0[0], s1[0], s2[0], s3[0]), b = make_uint4(s0[1], s1[1], s2[1], s3[1]);
+            B[0][0][s] = *reinterpret_cast<const h8*>(&a);
+            B[1][0][s] = *reinterpret_cast<const h8*>(&b);
+        }
+        // where the result of tile v goes: lane 32 hh + r ends up with features 8 hh .. 8 hh + 7 of the sample on lane 32 v + r, whose slot it learns by
+        // the same swap (~0: no record -- a slot behind n or a row of a finished tile)
+        const uint32_t own = (in_range && state >= 0) ? (uint32_t)j : ~0u;
+        const auto slot = __builtin_amdgcn_permlane32_swap(own, own, false, false);
+        __syncthreads();   // the staged weights; every wave of the workgroup arrives (none has returned)
+#pragma unroll
+        for (int v = 0; v < 2; v++) {
+            h8 X1[1];
+            mlp_density_half<1>(enc_wlds, B[v], X1);
+            const uint32_t sj = slot[v];
+            if (sj != ~0u) feat[(int64_t)(sj >> 5) * 64 + (lane & 32) + (sj & 31u)] = *reinterpret_cast<const uint4*>(&X1[0]);
+            asm volatile("" ::: "memory");   // one tile at a time: the second chain starts behind the first one's store (32 accumulator registers, not 64)
+        }
     }
 }
 
@@ -565,11 +630,11 @@ __device__ __forceinline__ f16v mlp_mfma(const h8& a, const h8& b, const f16v& c
 #ifndef NRC_MLP_WAVES
 #define NRC_MLP_WAVES 2   // workgroups per CU the register budget is set for (= waves per SIMD); A/B builds: -DNRC_MLP_WAVES=3
 #endif
-// the two networks' weights as LDS-resident A fragments (24 KB per workgroup): slot f of wlds[f][lane]
-enum { MLP_F_D0 = 0, MLP_F_DO = 4, MLP_F_C0 = 8, MLP_F_C1 = 12, MLP_F_CO = 20, MLP_N_FRAG = 24 };
-__device__ __forceinline__ void mlp_stage_weights(h8 (*wlds)[64], const __half* __restrict__ Wd, const __half* __restrict__ Wc) {
+// the two networks' weights as LDS-resident A fragments (24 KB per workgroup): slot f of wlds[f][lane] (MLP_F_*, above k_grid_encode)
+// n_frag: the leading fragments to stage (MLP_F_DO + 2: the density net alone, Wc is not read)
+__device__ __forceinline__ void mlp_stage_weights(h8 (*wlds)[64], const __half* __restrict__ Wd, const __half* __restrict__ Wc, int n_frag) {
     const int lane = threadIdx.x & 63, r = lane & 31, hh = lane >> 5;
-    for (int f = threadIdx.x >> 6; f < MLP_N_FRAG; f += 4) {
+    for (int f = threadIdx.x >> 6; f < n_frag; f += 4) {
         h8 v;
         if (f < MLP_F_DO) v = load_w_frag<false>(Wd, 32, 64, (f - MLP_F_D0) >> 1, (f - MLP_F_D0) & 1, r, hh);
         else if (f < MLP_F_C0) v = load_w_head_frag(Wd + 64 * 32, 64, 16, (f - MLP_F_DO) & 1, lane);     // 16-row head: two 16x16x32 k-steps (slots F_DO + 2, + 3 unused)
@@ -581,28 +646,25 @@ __device__ __forceinline__ void mlp_stage_weights(h8 (*wlds)[64], const __half* 
         wlds[f][lane] = v;
     }
 }
-// The MFMA chain of NT tiles of 32 samples: density net -> 16-row head -> colour net -> rgb head.  B: first-layer B fragments (fragment-major
-// features), X0: colour-net k-step 0 (SH of the direction).  Out, on lane r < 32 of tile u (sample r): h0[u] = fp16 density feature 0 and
-// rgb[u] = fp16 sigmoid of the colour head -- the values the packed records hold.
-// PRE: the caller's rows share their directions (one ray tile per wave), so it ran the colour net's k-step 0 once (mlp_sh_step) and passes the
-// accumulators P instead of X0; the k-step-1 MFMA takes P as its C operand, which is what it took from the k-step-0 MFMA in front of it: the same
-// instructions on the same operands, 4 of the 32 32x32x16 MFMAs and two LDS fragment reads per row fewer.  P is only read.
-template <int NT, bool PRE>
-__device__ __forceinline__ void mlp_chain_from(const h8 (*wlds)[64], const h8 (&B)[NT][2], const h8 (*X0)/*[NT], !PRE*/, const f16v (*P)[2]/*[NT][2], PRE*/,
-                                               _Float16 (&h0)[NT], _Float16 (&rgbh)[NT][3]) {
-    const int lane = threadIdx.x & 63;
+// The MFMA chain of NT tiles of 32 samples: density net -> 16-row head -> colour net -> rgb head, as two halves that meet in X1, the fp16 head output in
+// natural order as head_join leaves it (lane 32 hh + r: density features 8 hh .. 8 hh + 7 of the sample in column r).  mlp_chain_from is their
+// composition and what k_ngp_mlp, k_nwie_fwd and the 64-byte form of k_ngp_mlp_composite run; the density-encoder form of k_grid_encode runs the
+// density half on its own samples, stores X1, and k_ngp_mlp_composite<true> runs the colour half from there.
 #define D0(mt, s) wlds[MLP_F_D0 + 2 * (mt) + (s)][lane]
 #define DO(s) wlds[MLP_F_DO + (s)][lane]
 #define C0(mt, s) wlds[MLP_F_C0 + 2 * (mt) + (s)][lane]
 #define C1(mt, s) wlds[MLP_F_C1 + 4 * (mt) + (s)][lane]
 #define CO(s) wlds[MLP_F_CO + (s)][lane]
-    h8 X[NT][2], H[NT][4];
+// density half.  B: first-layer B fragments (fragment-major features).  Reads the fragments MLP_F_D0 .. MLP_F_DO + 1 of wlds only.
+template <int NT>
+__device__ __forceinline__ void mlp_density_half(const h8 (*wlds)[64], const h8 (&B)[NT][2], h8 (&X1)[NT]) {
+    const int lane = threadIdx.x & 63;
+    h8 H[NT][4];
     f16v acc[NT][2];
     h8 HB[NT][2][2];      // head operands: [sample block][k-step] (head_split)
     f4v o[NT][2];         // head accumulators, one per 16-sample block
 #pragma unroll
     for (int u = 0; u < NT; u++) {
-        if constexpr (!PRE) X[u][0] = X0[u];
         acc[u][0] = zero16(); acc[u][1] = zero16();
         o[u][0] = f4v{0.f, 0.f, 0.f, 0.f}; o[u][1] = o[u][0];
     }
@@ -632,9 +694,24 @@ __device__ __forceinline__ void mlp_chain_from(const h8 (*wlds)[64], const h8 (&
             for (int nb = 0; nb < 2; nb++) o[u][nb] = NRC_MFMA16(w, HB[u][nb][s], o[u][nb]);
     }
 #pragma unroll
+    for (int u = 0; u < NT; u++) X1[u] = head_join(o[u][0], o[u][1]);  // colour-net k-step 1 = fp16(h), natural order, back on the sample's lanes
+}
+// colour half.  X1: the density half's output, X0: colour-net k-step 0 (SH of the direction).  Out, on lane r < 32 of tile u (sample r): h0[u] = fp16
+// density feature 0 and rgb[u] = fp16 sigmoid of the colour head -- the values the packed records hold.
+// PRE: the caller's rows share their directions (one ray tile per wave), so it ran the colour net's k-step 0 once (mlp_sh_step) and passes the
+// accumulators P instead of X0; the k-step-1 MFMA takes P as its C operand, which is what it took from the k-step-0 MFMA in front of it: the same
+// instructions on the same operands, 4 of the 32 32x32x16 MFMAs and two LDS fragment reads per row fewer.  P is only read.
+template <int NT, bool PRE>
+__device__ __forceinline__ void mlp_colour_half(const h8 (*wlds)[64], const h8 (&X1)[NT], const h8 (*X0)/*[NT], !PRE*/, const f16v (*P)[2]/*[NT][2], PRE*/,
+                                                _Float16 (&h0)[NT], _Float16 (&rgbh)[NT][3]) {
+    const int lane = threadIdx.x & 63;
+    h8 H[NT][4];
+    f16v acc[NT][2];
+    h8 HB[NT][2][2];
+    f4v o[NT][2];
+#pragma unroll
     for (int u = 0; u < NT; u++) {
-        X[u][1] = head_join(o[u][0], o[u][1]);  // colour-net k-step 1 = fp16(h), natural order, back on the sample's lanes
-        h0[u] = X[u][1][0];              // fp16 density feature 0 (lane half 0, element 0)
+        h0[u] = X1[u][0];              // fp16 density feature 0 (lane half 0, element 0)
         if constexpr (!PRE) { acc[u][0] = zero16(); acc[u][1] = zero16(); }
     }
 #pragma unroll
@@ -644,8 +721,8 @@ __device__ __forceinline__ void mlp_chain_from(const h8 (*wlds)[64], const h8 (&
             const h8 w = C0(mt, s);
 #pragma unroll
             for (int u = 0; u < NT; u++) {
-                if constexpr (PRE) acc[u][mt] = mlp_mfma(w, X[u][1], P[u][mt]);   // C = the tile's k-step 0, D = this row's accumulator: no copy of P
-                else acc[u][mt] = mlp_mfma(w, X[u][s], acc[u][mt]);
+                if constexpr (PRE) acc[u][mt] = mlp_mfma(w, X1[u], P[u][mt]);   // C = the tile's k-step 0, D = this row's accumulator: no copy of P
+                else acc[u][mt] = mlp_mfma(w, s == 0 ? X0[u] : X1[u], acc[u][mt]);
             }
         }
 #pragma unroll
@@ -689,10 +766,17 @@ __device__ __forceinline__ void mlp_chain_from(const h8 (*wlds)[64], const h8 (&
 #pragma unroll
         for (int c = 0; c < 3; c++) rgbh[u][c] = (_Float16)fast_sigmoid(rgb[c]);
     }
+}
 #undef D0
 #undef DO
 #undef C1
 #undef CO
+template <int NT, bool PRE>
+__device__ __forceinline__ void mlp_chain_from(const h8 (*wlds)[64], const h8 (&B)[NT][2], const h8 (*X0)/*[NT], !PRE*/, const f16v (*P)[2]/*[NT][2], PRE*/,
+                                               _Float16 (&h0)[NT], _Float16 (&rgbh)[NT][3]) {
+    h8 X1[NT];
+    mlp_density_half<NT>(wlds, B, X1);
+    mlp_colour_half<NT, PRE>(wlds, X1, X0, P, h0, rgbh);
 }
 // the form of k_ngp_mlp and k_nwie_fwd: every row brings its own directions
 template <int NT>
@@ -955,6 +1039,9 @@ struct ImageCfg { int width, height, tiles_x; int64_t tile_begin; float esf, dt_
 // from the chunk's longest-first list through an atomic counter (a plain work queue: a wave never waits for another one).  A tile whose rays have
 // all finished (saturated or out of samples) requests no further rows.  Features: the chunk's fragment-major records (row - first row of the
 // chunk); t: the count pass's arena in place (sample k of local tile lt in arena row lt * arena_rows + k).
+// DENS: `feat` holds the density-encoder form's records (k_grid_encode<SRC_TILED, true>: 1 KB per 32-sample tile, the lane's 16-byte vector IS X1), and
+// a row runs the colour half of the chain alone: one feature load per lane and tile instead of two, the same prefetch depth, the same compositor.
+template <bool DENS>
 __global__ void __launch_bounds__(256, NRC_MLP_WAVES) k_ngp_mlp_composite(const uint4* __restrict__ feat, const h8* __restrict__ ray_sh,
                                                                           const __half* __restrict__ Wd, const __half* __restrict__ Wc,
                                                                           const float* __restrict__ ts, int arena_rows, const int32_t* __restrict__ ray_cnt,
@@ -989,30 +1076,45 @@ __global__ void __launch_bounds__(256, NRC_MLP_WAVES) k_ngp_mlp_composite(const 
             mlp_sh_step<NT>(wlds, X0, P);
         }
         const float* tcol = ts + (((int64_t)lt * arena_rows) << 6) + lane;
-        const uint4* fcol = feat + (int64_t)(rb - row0) * (NT * 128) + r;   // 32-sample tile 2 (row - row0) + u at fcol + (2 k + u) * 128
+        // 32-sample tile 2 (row - row0) + u at fcol + (2 k + u) * 128 (DENS: the tile's 1 KB record at fcol + (2 k + u) * 64, this lane's vector included)
+        const uint4* fcol = DENS ? feat + (int64_t)(rb - row0) * (NT * 64) + lane : feat + (int64_t)(rb - row0) * (NT * 128) + r;
         const int rot0 = (2 * (rb - row0)) & 3;
-        uint4 nb[NT][2];
+        uint4 nb[NT][DENS ? 1 : 2];
         float nt_ = 0.f;
         auto fetch = [&](int k) {   // row k of the tile: features of both halves, this lane's t
 #pragma unroll
             for (int u = 0; u < NT; u++) {
-                const uint4* fp = fcol + (int64_t)(2 * k + u) * 128;
-                const int rot = (rot0 + 2 * k + u) & 3;
-                nb[u][0] = fp[((hh + rot) & 3) * 32];
-                nb[u][1] = fp[((2 + hh + rot) & 3) * 32];
+                if constexpr (DENS) {
+                    nb[u][0] = fcol[(int64_t)(2 * k + u) * 64];
+                } else {
+                    const uint4* fp = fcol + (int64_t)(2 * k + u) * 128;
+                    const int rot = (rot0 + 2 * k + u) & 3;
+                    nb[u][0] = fp[((hh + rot) & 3) * 32];
+                    nb[u][1] = fp[((2 + hh + rot) & 3) * 32];
+                }
             }
             nt_ = tcol[(int64_t)k << 6];
         };
         if (R > 0) fetch(0);
         // one row of prefetch: the next row's loads are issued before this row's chain
         for (int k = 0; k < R && __any(acc.alive); k++) {
-            h8 B[NT][2];
+            h8 B[NT][DENS ? 1 : 2];   // (DENS: X1 of the tile)
 #pragma unroll
-            for (int u = 0; u < NT; u++) { B[u][0] = *reinterpret_cast<const h8*>(&nb[u][0]); B[u][1] = *reinterpret_cast<const h8*>(&nb[u][1]); }
+            for (int u = 0; u < NT; u++) {
+                B[u][0] = *reinterpret_cast<const h8*>(&nb[u][0]);
+                if constexpr (!DENS) B[u][1] = *reinterpret_cast<const h8*>(&nb[u][1]);
+            }
             const float t = nt_;
             if (k + 1 < R) fetch(k + 1);
             _Float16 h0[NT], rgbh[NT][3];
-            mlp_chain<NT>(wlds, B, P, h0, rgbh);
+            if constexpr (DENS) {
+                h8 X1[NT];
+#pragma unroll
+                for (int u = 0; u < NT; u++) X1[u] = B[u][0];
+                mlp_colour_half<NT, true>(wlds, X1, nullptr, P, h0, rgbh);
+            } else {
+                mlp_chain<NT>(wlds, B, P, h0, rgbh);
+            }
             // fp16 outputs exactly as the packed records hold them, (h0, r) and (g, b); sample 32 u + r sits on lane r of tile u
             uint32_t w01[NT], w23[NT];
 #pragma unroll
@@ -1230,9 +1332,11 @@ static YPairView ypair_view_of(const void* view, const GridCfg& g, int n_levels)
     if (!yv.ptr || yv.levels <= 0) { yv.ptr = nullptr; yv.levels = 0; }
     return yv;
 }
+// density_weights: the density-encoder form (k_grid_encode<SRC_TILED, true>): `feat` receives 32 B per slot, the density net's output
 template <int SRC>
 static void launch_encode(const QueryIn& in, int64_t base, int64_t n, const void* table, const GridCfg& g, uint4* feat, hipStream_t s,
-                          const BlockView& bv = BlockView{}, const VertexView& vv = VertexView{}, const YPairView& yv = YPairView{}) {
+                          const BlockView& bv = BlockView{}, const VertexView& vv = VertexView{}, const YPairView& yv = YPairView{},
+                          const void* density_weights = nullptr) {
     // levels whose cells are larger than a wave's footprint: narrow gathers (see grid_level_features_narrow)
     int narrow = 0;
     while (narrow < NRC_MAX_LEVELS && !g.hashed[narrow] && g.size[narrow] > 8) narrow++;
@@ -1258,6 +1362,14 @@ static void launch_encode(const QueryIn& in, int64_t base, int64_t n, const void
     // (nrc_ngp_set_encoder_shape; the remapping permutes whole blocks of 1024 slots: the launch covers whole blocks)
     const int lane_shape = (3 << 4) | 1;
     const int lanes = (SRC == SRC_TILED && (base & 1023) == 0) ? (g_enc_shape_override ? g_enc_shape_override : lane_shape) : 0;
+    if constexpr (SRC == SRC_TILED) {
+        if (density_weights) {
+            hipLaunchKernelGGL((k_grid_encode<SRC_TILED, true>), dim3((unsigned)(lanes ? 4 * nrc_cdiv(n, 1024) : nrc_cdiv(n, 256))), dim3(256),
+                               (MLP_F_DO + 2) * 64 * sizeof(h8), s, in, base, n, (const __half2*)table, g, feat, narrow, lvl_range, lanes,
+                               g_enc_xcd_run_override ? g_enc_xcd_run_override : NRC_ENC_XCD_RUN, bv, vv, yv, (const __half*)density_weights);
+            return;
+        }
+    }
     hipLaunchKernelGGL(k_grid_encode<SRC>, dim3((unsigned)(lanes ? 4 * nrc_cdiv(n, 1024) : nrc_cdiv(n, 256)), rows), dim3(256), 0, s, in, base, n, (const __half2*)table, g, feat,
                        narrow, lvl_range, lanes, g_enc_xcd_run_override ? g_enc_xcd_run_override : NRC_ENC_XCD_RUN, bv, vv, yv);
 }
@@ -1657,11 +1769,29 @@ static int64_t frame_chunks(int64_t n_rows, int64_t budget, int32_t max_samples)
     return n_rows <= budget ? 1 : nrc_cdiv(n_rows, budget - max_samples);
 }
 static int64_t round256(int64_t b) { return (b + 255) / 256 * 256; }
+// Which kernel pair the single-pass frame runs.  1: the encoder runs the density net and hands 32 B per slot to k_ngp_mlp_composite<true>; 0: 64 B of
+// grid features per slot and the whole chain in k_ngp_mlp_composite<false>.  Same pictures, bit for bit (tests/test_gpu_frame_density_encoder.py).
+// nrc_ngp_set_frame_density_encoder: -1 = NRC_FRAME_DENSITY_ENCODER; per host thread like the encoder's shape.  Chunks of more than 2^24 rows keep the
+// 64-byte pair (the encoder passes a record's slot between lanes as 32 bits).
+#ifndef NRC_FRAME_DENSITY_ENCODER
+#define NRC_FRAME_DENSITY_ENCODER 1   // measured against the parent's 64-byte pair: frame 7.13 -> 6.61 ms, k_ngp_mlp_composite 1.52 -> 1.02 ms, encoder +0.04 ms -- LABBOOK R31
+#endif
+static thread_local int g_frame_density_override = -1;
+static bool frame_density_pair(int64_t feat_rows) {
+    const int want = g_frame_density_override >= 0 ? g_frame_density_override : NRC_FRAME_DENSITY_ENCODER;
+    return want != 0 && feat_rows <= (int64_t(1) << 24);
+}
+int nrc_ngp_set_frame_density_encoder(int32_t mode) {
+    if (mode < -1 || mode > 1) return NRC_ERR_INVALID;
+    g_frame_density_override = mode;
+    return NRC_OK;
+}
 int64_t nrc_ngp_render_frame_ws_bytes(int64_t n_rows, int64_t n_ray_tiles, int32_t max_samples, int64_t row_budget) {
     const int64_t budget = frame_budget(row_budget);
     if (n_rows < 0 || n_ray_tiles < 0 || max_samples < 1 || budget < 2 * (int64_t)max_samples) return NRC_ERR_INVALID;
     const int64_t chunks = frame_chunks(n_rows, budget, max_samples);
     const int64_t feat_rows = n_rows < budget ? n_rows : budget;
+    // (the feature part is sized for the 64-byte pair whichever pair is set: a workspace sized once serves both, the density-encoder pair uses its first half)
     return round256((feat_rows > 0 ? feat_rows : 1) * 64 * 64) + round256(n_ray_tiles * 2048) + round256(n_ray_tiles * 4) + round256(chunks * 20);
 }
 
@@ -1689,7 +1819,8 @@ int nrc_ngp_render_frame(const float* ts_arena, int32_t* row_tile, const float* 
     const int64_t feat_rows = n_rows < budget ? n_rows : budget;
     char* wsp = (char*)workspace;
     uint4* feat = (uint4*)wsp;
-    wsp += round256((feat_rows > 0 ? feat_rows : 1) * 64 * 64);
+    const bool dens = frame_density_pair(feat_rows);
+    wsp += round256((feat_rows > 0 ? feat_rows : 1) * 64 * 64);   // (dens: the records fill the first half)
     h8* ray_sh = (h8*)wsp;
     wsp += round256(n_ray_tiles * 2048);
     int32_t* order = (int32_t*)wsp;
@@ -1722,11 +1853,15 @@ int nrc_ngp_render_frame(const float* ts_arena, int32_t* row_tile, const float* 
     for (int64_t c = 0; c < chunks; c++) {
         if (n_rows > 0) {
             in.chunk_rows = chunk_tab + 4 * c + 2;
-            launch_encode<SRC_TILED>(in, 0, feat_rows * 64, table_f16, g, feat, s, bv, vv, yv);
+            launch_encode<SRC_TILED>(in, 0, feat_rows * 64, table_f16, g, feat, s, bv, vv, yv, dens ? density_weights_f16 : nullptr);
             NRC_STAGE(s, "k_grid_encode");
         }
-        hipLaunchKernelGGL(k_ngp_mlp_composite, dim3((unsigned)mlp_blocks), dim3(256), 0, s, feat, ray_sh, (const __half*)density_weights_f16,
-                           (const __half*)color_weights_f16, ts_arena, (int)max_samples, ray_cnt, tile_off, order, chunk_tab + 4 * c, queue + c, ic, rgb, alpha, depth);
+        if (dens)
+            hipLaunchKernelGGL(k_ngp_mlp_composite<true>, dim3((unsigned)mlp_blocks), dim3(256), 0, s, feat, ray_sh, (const __half*)density_weights_f16,
+                               (const __half*)color_weights_f16, ts_arena, (int)max_samples, ray_cnt, tile_off, order, chunk_tab + 4 * c, queue + c, ic, rgb, alpha, depth);
+        else
+            hipLaunchKernelGGL(k_ngp_mlp_composite<false>, dim3((unsigned)mlp_blocks), dim3(256), 0, s, feat, ray_sh, (const __half*)density_weights_f16,
+                               (const __half*)color_weights_f16, ts_arena, (int)max_samples, ray_cnt, tile_off, order, chunk_tab + 4 * c, queue + c, ic, rgb, alpha, depth);
         NRC_STAGE(s, "k_ngp_mlp");   // (k_ngp_mlp_composite: the stage keeps the MLP kernel's name, where the in-frame ruler looks for it)
     }
     NRC_LAUNCH_CHECK();

@@ -26,7 +26,10 @@ def short(name):
             base += '<' + ', '.join(re.findall(r'L[ib](\d+)E', t.group(1))) + '>'
         return base
     name = re.sub(r'\(anonymous namespace\)::', '', name).replace('void ', '')
-    return name.split('(')[0]
+    name = name.split('(')[0]
+    if name.startswith(('k_grid_encode<', 'k_ngp_mlp_composite<')):   # their bool template argument as the mangled form above spells it: 1 / 0
+        name = name.replace('true', '1').replace('false', '0')
+    return name
 
 
 import os
@@ -131,7 +134,12 @@ for k in sorted(acc):
     lines.append('')
     key = k
     if k.startswith('k_grid_encode') or k.startswith('k_ngp_mlp'):
-        key = re.sub(r'<1(, \d+)?>', '<SRC_TILED>', re.sub(r'<0(, \d+)?>', '<SRC_ARRAYS>', k))
+        if k.startswith('k_ngp_mlp_composite'):   # <DENS>: the 64-byte form keeps the name it had before it was a template
+            key = 'k_ngp_mlp_composite<DENS>' if k.endswith('<1>') else 'k_ngp_mlp_composite'
+        elif k.startswith('k_grid_encode<1, 1'):   # <SRC, DENS>: the density-encoder form of the single-pass frame beside the 64-byte form
+            key = 'k_grid_encode<SRC_TILED, DENS>'
+        else:
+            key = re.sub(r'<1(, \d+)?>', '<SRC_TILED>', re.sub(r'<0(, \d+)?>', '<SRC_ARRAYS>', k))
     summary[key] = {**{n: round(v, 1) for n, v in c.items()}, **derived}
 (OUT / f'{ROUND}_pmc_summary.md').write_text('\n'.join(lines))
 import hashlib
