@@ -60,7 +60,8 @@ enum {
  * group 24, nrc_adam_step_rows_multi -- the visibility-masked Adam step, a new entry in a translation unit of its own; group 25,
  * nrc_ngp_set_encoder_ypair_levels / _ypair_view, nrc_ngp_ypair_view_bytes, nrc_ngp_build_ypair_view -- the y-pair view of the leading hashed levels, read
  * only by a call that was handed one; group 26, nrc_ngp_set_frame_density_encoder -- the single-pass frame's kernel pair (the workspace of
- * nrc_ngp_render_frame is what it was, the pictures are the same bits). */
+ * nrc_ngp_render_frame is what it was, the pictures are the same bits); group 27, nrc_gs_preprocess_antialias_band / nrc_gs_backward_antialias_band /
+ * nrc_gs_filter3d -- anti-aliased splats and the 3-D smoothing filter: instances and a kernel of their own, no existing launch changes. */
 #define NRC_ABI_VERSION 22
 /* library identification; also used by the loader's symbol check */
 int nrc_abi_version(void);
@@ -1396,6 +1397,54 @@ int nrc_gs_backward_absgrad_band(int32_t P, int32_t D, int32_t M, int32_t W, int
 int nrc_adam_step_rows_multi(int32_t n_tensors, float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
                              const int32_t* row_widths, int64_t n_rows, const void* visible, int32_t visible_kind, const float* lrs, const float* bc1,
                              const float* bc2, float beta1, float beta2, float eps, float weight_decay, int32_t adam_w_mode, nrc_stream_t stream);
+
+/* =====================================================================================================
+ * Group 27 -- anti-aliased splats and the 3-D smoothing filter of Mip-Splatting (csrc/gs_raster.hip: k_preprocess<., true>, k_preprocess_bw<0 / 1, true>;
+ *            csrc/gs_densify.hip: k_filter3d).  Upstream diff_gaussian_rasterization carries the first as the `antialiasing` field of
+ *            GaussianRasterizationSettings (gsplat: rasterize_mode="antialiased"): the 0.3-pixel dilation of the projected 2-D covariance adds energy, and
+ *            a model trained at one resolution dilates and brightens at another unless that energy is taken back.  Added under ABI version 22 without a bump
+ *            (additive, like groups 23-26: no earlier signature, record slot or default launch changes).
+ *
+ *   With (a0, b, c0) the projected covariance BEFORE the dilation, a = a0 + 0.3, c = c0 + 0.3, det0 = a0 c0 - b^2, det1 = a c - b^2:
+ *            comp = sqrt(max(0.000025, det0 / det1))                                                       (upstream's h_convolution_scaling, floor included)
+ *   nrc_gs_preprocess_antialias_band : nrc_gs_preprocess_band, except that the opacity in conic_opacity[4 i + 3] and in the splat record is o comp (o after the
+ *            sigmoid with raw_parameters).  Radii, tile rectangles, depths, conic, colour, lists and counts are bit for bit those of nrc_gs_preprocess_band, so
+ *            every blend pass (colour, depth and alpha, features, contributions, their backwards) takes the compensated opacity without a change.
+ *   nrc_gs_backward_antialias_band : nrc_gs_backward_absgrad_band (dL_ddepth_alpha and dL_dmean2D_abs stay optional as there) for a forward made by
+ *            nrc_gs_preprocess_antialias_band.  With g = dL/d(o comp) (slot [3] of the gradient record): dL_dopacity = g comp (times o (1 - o) with
+ *            raw_parameters), and where det0 / det1 > 0.000025, with k = g o / (2 comp),
+ *                dL/da0 += k (c0 det1 - c det0) / det1^2    dL/dc0 += k (a0 det1 - a det0) / det1^2    dL/db += k (-2 b) (det1 - det0) / det1^2
+ *            in front of the chain to cov3D, scales, rotations and means; at or below the floor nothing is added.  `opacities` is REQUIRED here also without
+ *            raw_parameters (the activated values the forward read).  dL_dmean2D and dL_dmean2D_abs are those of nrc_gs_backward_absgrad_band.
+ *            pose_partials / dL_dcamera: the camera backward has no anti-aliased form -- dL_dcamera != NULL returns NRC_ERR_UNSUPPORTED before any HIP call;
+ *            there is no anti-aliased form of nrc_gs_backward_rest_step either.
+ *   nrc_gs_filter3d : filter_3D (P) f32 from means3D (P, 3) and V views, `views` (V, 20) f32 on the device: the world-to-camera matrix row-major (16; p_cam =
+ *            m[:3, :3] p + m[:3, 3]), fx, fy, W, H.  View v sees Gaussian i iff z > 0.2 and the pixel (x / z fx + W / 2, y / z fy + H / 2) lies in
+ *            [-0.15 W, 1.15 W] x [-0.15 H, 1.15 H]; filter_3D[i] = sqrt(0.2) min over the seeing views of z / fx (f64 arithmetic on the promoted inputs, rounded
+ *            once).  A Gaussian no view sees gets the largest value among the seen ones (0 when none is seen).  Two launches, no float atomics, the same
+ *            bits on every call.  workspace: 4 bytes on the device.  NRC_ERR_INVALID before any HIP call: P < 0 or > 2^30, V < 1, a null views / workspace,
+ *            with P > 0 a null means3D / filter_3D.  P == 0: NRC_OK, nothing is launched.
+ * ===================================================================================================== */
+int nrc_gs_preprocess_antialias_band(int32_t P, int32_t D, int32_t M, int32_t W, int32_t H, const float* means3D, const float* shs,
+                      const float* shs_rest, int32_t raw_parameters, const float* colors_precomp, const float* opacities, const float* scales, float scale_modifier,
+                      const float* rotations, const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix,
+                      const float* campos, const float* camera_dev, float tan_fovx, float tan_fovy, int32_t* radii, float* depths,
+                      float* points_xy, float* conic_opacity, float* rgb, uint8_t* clamped, float* cov3D, uint32_t* tiles_touched,
+                      uint32_t* tile_counts, uint32_t* ranges, uint32_t* tile_fill, uint32_t* bin_hist, int64_t span_capacity,
+                      int64_t instance_capacity, float* splat_records, int64_t* num_rendered, int64_t* count_mailbox, int64_t mailbox_ticket,
+                      int32_t tile_row_begin, int32_t n_tile_rows, uint8_t* band_mask, nrc_stream_t stream);
+int nrc_gs_backward_antialias_band(int32_t P, int32_t D, int32_t M, int32_t W, int32_t H, const float* bg, const float* means3D, const float* shs,
+                    const float* shs_rest, int32_t raw_parameters, const float* opacities, const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
+                    const float* cov3D_precomp, const float* viewmatrix, const float* projmatrix, const float* campos,
+                    const float* camera_dev, float tan_fovx, float tan_fovy, const int32_t* radii, const float* points_xy, const float* conic_opacity,
+                    const float* rgb, const uint8_t* clamped, const float* cov3D, const int32_t* point_list,
+                    const uint32_t* ranges, const float* splat_records, const uint32_t* tile_order, const uint32_t* n_contrib,
+                    const float* final_T, const float* dL_dpix,
+                    float* dL_dmean2D, float* dL_dconic, float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D,
+                    float* dL_dcov3D, float* dL_dsh, float* dL_dsh_rest, float* dL_dscale, float* dL_drot, float* grad_records,
+                    int32_t records_clear, int32_t tile_row_begin, int32_t n_tile_rows, const float* dL_ddepth_alpha, float* pose_partials,
+                    float* dL_dcamera, float* dL_dmean2D_abs, nrc_stream_t stream);
+int nrc_gs_filter3d(const float* means3D, int64_t P, const float* views, int32_t V, float* filter_3D, void* workspace, nrc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -282,9 +282,83 @@ int run_plan(F flags, int64_t P, int* src, int* kind, int* aux, int* counts, voi
     return NRC_OK;
 }
 
+// ---- the 3-D smoothing filter of Mip-Splatting (compute_3D_filter), group 27 ------------------------------------------------
+// One thread per Gaussian walks the V views; the views' blocks (20 floats: w2c row-major 4 x 4, fx, fy, W, H) are staged once per workgroup in LDS,
+// F3D_CHUNK views at a time.  A view sees a Gaussian iff z > 0.2 and the pixel x / z fx + W / 2, y / z fy + H / 2 lies in the frame widened by 15 % on every side;
+// filter_3D = sqrt(0.2) min over the seeing views of z / fx.  The arithmetic is f64 on the promoted f32 inputs (the view tests are decisions, and z is a sum that
+// cancels for Gaussians near a camera plane; one rounding to f32 at the end): 200 views x 1 M Gaussians are ~4 GFLOP of f64, well under a millisecond of this chip.
+// A Gaussian no view sees is marked -1 and receives, in the second launch, the largest filter among the seen ones: the maximum travels as the bit pattern of a
+// non-negative float through an INTEGER atomicMax (exact and order-independent: the result is the same bits on every call), 0 when no Gaussian is seen at all.
+constexpr int F3D_BLOCK = 256;
+constexpr int F3D_CHUNK = 64;
+constexpr int F3D_VIEW_FLOATS = 20;
+
+__global__ void __launch_bounds__(F3D_BLOCK) k_filter3d(int64_t P, int V, const float* __restrict__ means3D, const float* __restrict__ views,
+                                                        float* __restrict__ filter_3D, unsigned* __restrict__ max_bits) {
+    __shared__ float s_views[F3D_CHUNK * F3D_VIEW_FLOATS];
+    __shared__ unsigned s_max;
+    const int64_t i = (int64_t)blockIdx.x * F3D_BLOCK + threadIdx.x;
+    const bool live = i < P;
+    if (threadIdx.x == 0) s_max = 0u;
+    double x = 0., y = 0., z = 0.;
+    if (live) { x = (double)means3D[3 * i]; y = (double)means3D[3 * i + 1]; z = (double)means3D[3 * i + 2]; }
+    double dmin = 0.;
+    bool seen = false;
+    for (int v0 = 0; v0 < V; v0 += F3D_CHUNK) {
+        const int nv = min(F3D_CHUNK, V - v0);
+        __syncthreads();   // (the previous chunk has been read)
+        for (int k = threadIdx.x; k < nv * F3D_VIEW_FLOATS; k += F3D_BLOCK) s_views[k] = views[(int64_t)v0 * F3D_VIEW_FLOATS + k];
+        __syncthreads();
+        if (live) {
+            for (int v = 0; v < nv; v++) {
+                const float* c = s_views + v * F3D_VIEW_FLOATS;   // every lane reads the same word: an LDS broadcast
+                const double zc = (double)c[8] * x + (double)c[9] * y + (double)c[10] * z + (double)c[11];
+                if (!(zc > 0.2)) continue;
+                const double xc = (double)c[0] * x + (double)c[1] * y + (double)c[2] * z + (double)c[3];
+                const double yc = (double)c[4] * x + (double)c[5] * y + (double)c[6] * z + (double)c[7];
+                const double fx = (double)c[16], fy = (double)c[17], W = (double)c[18], H = (double)c[19];
+                const double px = xc / zc * fx + 0.5 * W, py = yc / zc * fy + 0.5 * H;
+                if (px >= -0.15 * W && px <= 1.15 * W && py >= -0.15 * H && py <= 1.15 * H) {
+                    const double d = zc / fx;
+                    dmin = seen ? fmin(dmin, d) : d;
+                    seen = true;
+                }
+            }
+        }
+    }
+    float f = -1.f;
+    if (seen) {
+        f = (float)(0.44721359549995793 * dmin);   // sqrt(0.2), correctly rounded
+        if (!(f >= 0.f)) f = 0.f;                   // (a non-positive focal length: never a marker, never a NaN in the maximum)
+        atomicMax(&s_max, __float_as_uint(f));
+    }
+    if (live) filter_3D[i] = f;
+    __syncthreads();
+    if (threadIdx.x == 0 && s_max != 0u) atomicMax(max_bits, s_max);
+}
+
+__global__ void __launch_bounds__(F3D_BLOCK) k_filter3d_unseen(int64_t P, float* __restrict__ filter_3D, const unsigned* __restrict__ max_bits) {
+    const int64_t i = (int64_t)blockIdx.x * F3D_BLOCK + threadIdx.x;
+    if (i < P && filter_3D[i] < 0.f) filter_3D[i] = __uint_as_float(*max_bits);
+}
+
 }  // namespace
 
 extern "C" {
+
+int nrc_gs_filter3d(const float* means3D, int64_t P, const float* views, int32_t V, float* filter_3D, void* workspace, nrc_stream_t stream) {
+    NRC_ENTER();
+    if (P < 0 || P > (int64_t)1 << 30 || V < 1 || !views || !workspace) return NRC_ERR_INVALID;
+    if (P == 0) return NRC_OK;
+    if (!means3D || !filter_3D) return NRC_ERR_INVALID;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(workspace, 0, sizeof(unsigned), s) != hipSuccess) return NRC_ERR_LAUNCH;
+    const unsigned blocks = (unsigned)nrc_cdiv(P, F3D_BLOCK);
+    hipLaunchKernelGGL(k_filter3d, dim3(blocks), dim3(F3D_BLOCK), 0, s, P, (int)V, means3D, views, filter_3D, reinterpret_cast<unsigned*>(workspace));
+    hipLaunchKernelGGL(k_filter3d_unseen, dim3(blocks), dim3(F3D_BLOCK), 0, s, P, filter_3D, reinterpret_cast<const unsigned*>(workspace));
+    NRC_LAUNCH_CHECK();
+    return NRC_OK;
+}
 
 int nrc_gs_densify_stats(const float* viewspace_grad, int32_t ld, const int32_t* radii, int64_t P, float* grad_accum, int32_t* n_observations,
                          nrc_stream_t stream) {

@@ -196,6 +196,10 @@ __device__ __forceinline__ void write_splat_record(float4 (&rec)[4], float X, fl
     rec[2] = make_float4(ta, da, ba, yoff); rec[3] = make_float4(col[0], col[1], col[2], z);
 }
 // one Gaussian; sh_row = its SH coefficients (LDS copy, see k_preprocess)
+// AA (group 27, upstream's `antialiasing`): the opacity that leaves is o * comp, comp = sqrt(max(0.000025, det(cov2D) / det(cov2D + 0.3 I))) -- the energy the
+// 0.3-pixel dilation adds is taken back (Mip-Splatting's 2-D filter, upstream's h_convolution_scaling).  Radius, rectangle, depth, conic and colour are those of
+// the default instance: a compile-time property, the default instances are compiled from the statements they always had.
+template <bool AA = false>
 __device__ __forceinline__ void preprocess_one(int i, const GsCam& cam, const float* __restrict__ means3D, const float* sh_row,
                                                const float* __restrict__ colors_precomp, const float* __restrict__ opacities,
                                                const float* __restrict__ scales, const float* __restrict__ rotations,
@@ -260,7 +264,18 @@ __device__ __forceinline__ void preprocess_one(int i, const GsCam& cam, const fl
     }
 #pragma unroll
     for (int k = 0; k < 3; k++) rgb[3 * i + k] = col[k];
-    const float opacity = cam.raw ? act_sigmoid(opacities[i]) : opacities[i];
+    float opacity = cam.raw ? act_sigmoid(opacities[i]) : opacities[i];
+    if constexpr (AA) {
+        // (a0, b, c0): the projected covariance before the dilation, as statements of their own; a0 + 0.3f and c0 + 0.3f are cov[0] and cov[2] bit for bit
+        // (no contraction in this file), so det below is det1
+        const float a0 = Mx[0] * sx[0] + Mx[1] * sx[1] + Mx[2] * sx[2];
+        const float b = Mx[0] * sy[0] + Mx[1] * sy[1] + Mx[2] * sy[2];
+        const float c0 = My[0] * sy[0] + My[1] * sy[1] + My[2] * sy[2];
+        const float a = a0 + 0.3f, c = c0 + 0.3f;
+        const float det0 = a0 * c0 - b * b, det1 = a * c - b * b;
+        const float rho = det0 / det1;
+        opacity = opacity * sqrtf(fmaxf(0.000025f, rho));
+    }
     if (want_record) write_splat_record(splat, pix[0], pix[1], conic[0], conic[1], conic[2], opacity, col, pv[2]);  // this thread's row of the LDS image
     depths[i] = pv[2]; radii[i] = my_radius;
     points_xy[2 * i] = pix[0]; points_xy[2 * i + 1] = pix[1];
@@ -286,7 +301,8 @@ __device__ __forceinline__ void preprocess_one(int i, const GsCam& cam, const fl
 #ifndef SHB_U
 #define SHB_U 16   // loads per trip: 8 / 12 / 16 -> k_preprocess 101 / 99 / 95-98 us at 1 M Gaussians (k_preprocess_bw indifferent)
 #endif
-template <bool TO_LDS, int SHB_U_ = SHB_U, bool BATCH_TAIL = true>
+// TAG: see sh_rows_copy
+template <bool TO_LDS, int SHB_U_ = SHB_U, bool BATCH_TAIL = true, int TAG = 0>
 __device__ __forceinline__ void sh_block_copy(float* s_sh, int pitch, int col0, int len, int count, float* g, int nthreads) {
     constexpr int U = SHB_U_;
     const int dq = nthreads / len, dr = nthreads - dq * len;
@@ -337,10 +353,12 @@ __device__ __forceinline__ void sh_block_copy(float* s_sh, int pitch, int col0, 
 }
 // SPLIT: the form is a compile-time property of the kernel instance (round 6: one kernel carrying both forms spilled scalar registers in the path of the
 // other -- the concatenated form of the bench frame lost 10 % to code it never runs)
-template <bool TO_LDS, int SHB_U_ = SHB_U, bool SPLIT = false>
+// TAG: the anti-aliased kernel instances (group 27) take instances of their own of the two copy templates.  Sharing them moved the default split-SH k_preprocess
+// from 98 to 100 VGPRs with not one statement of it changed (LABBOOK round 32): which caller an inlined body is cloned into and which it is moved into changed.
+template <bool TO_LDS, int SHB_U_ = SHB_U, bool SPLIT = false, int TAG = 0>
 __device__ __forceinline__ void sh_rows_copy(float* s_sh, int pitch, int row_len, int count, size_t first, float* sh, float* sh_rest, int nthreads) {
     if constexpr (!SPLIT) {
-        sh_block_copy<TO_LDS, SHB_U, false>(s_sh, pitch, 0, row_len, count, sh + first * row_len, nthreads);
+        sh_block_copy<TO_LDS, SHB_U, false, TAG>(s_sh, pitch, 0, row_len, count, sh + first * row_len, nthreads);
     } else {
         // the three dc floats per Gaussian ride along with the first trip of the `rest` block: their loads are issued in front of it and land in LDS
         // behind it (a separate one-trip copy was a dependent round trip of its own, per direction, in kernels that run a few waves per CU)
@@ -361,7 +379,7 @@ __device__ __forceinline__ void sh_rows_copy(float* s_sh, int pitch, int row_len
             for (int u = 0; u < 3; u++) { const int k = (int)threadIdx.x + u * nthreads; if (k < n3) dc[k] = dv[u]; }
         }
         const int rl = row_len - 3;
-        if (rl > 0) sh_block_copy<TO_LDS, SHB_U_>(s_sh, pitch, 3, rl, count, sh_rest + first * rl, nthreads);
+        if (rl > 0) sh_block_copy<TO_LDS, SHB_U_, true, TAG>(s_sh, pitch, 3, rl, count, sh_rest + first * rl, nthreads);
         if (TO_LDS) {
 #pragma unroll
             for (int u = 0; u < 3; u++) { const int k = (int)threadIdx.x + u * nthreads; if (k < n3) s_sh[doff[u]] = dv[u]; }
@@ -382,7 +400,7 @@ __device__ __forceinline__ void sh_rows_copy(float* s_sh, int pitch, int row_len
 #ifndef PRE_MAXM
 #define PRE_MAXM 16
 #endif
-template <bool SPLIT = false>
+template <bool SPLIT = false, bool AA = false>
 __global__ void __launch_bounds__(PRE_BLOCK) k_preprocess(int P, GsCam cam_arg, const float* __restrict__ pose, const float* __restrict__ means3D, const float* __restrict__ shs,
                                                           const float* __restrict__ shs_rest,
                                                           const float* __restrict__ colors_precomp, const float* __restrict__ opacities,
@@ -401,7 +419,7 @@ __global__ void __launch_bounds__(PRE_BLOCK) k_preprocess(int P, GsCam cam_arg, 
     for (int blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {
         const int first = blk * PRE_BLOCK, i = first + threadIdx.x;
         if (shs) {
-            sh_rows_copy<true, SHB_U, SPLIT>(s_sh, pitch, row_len, min(PRE_BLOCK, P - first), (size_t)first, const_cast<float*>(shs), const_cast<float*>(shs_rest), PRE_BLOCK);
+            sh_rows_copy<true, SHB_U, SPLIT, (AA ? 1 : 0)>(s_sh, pitch, row_len, min(PRE_BLOCK, P - first), (size_t)first, const_cast<float*>(shs), const_cast<float*>(shs_rest), PRE_BLOCK);
             __syncthreads();
         }
         // splat records leave through LDS: a lane storing its own record touches 64 cache lines per store instruction; from the LDS image (the SH
@@ -409,7 +427,7 @@ __global__ void __launch_bounds__(PRE_BLOCK) k_preprocess(int P, GsCam cam_arg, 
         // Rows of culled Gaussians hold zeros or stale bytes: no tile list ever names them.
         float4 rec[4] = {};
         if (i < P)
-            preprocess_one(i, cam, means3D, s_sh + threadIdx.x * pitch, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii, depths,
+            preprocess_one<AA>(i, cam, means3D, s_sh + threadIdx.x * pitch, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii, depths,
                            points_xy, conic_opacity, rgb, clamped, cov3D, tiles_touched, tile_counts, splat != nullptr, rec);
         if (splat) {
             float4* s_rec = reinterpret_cast<float4*>(s_sh);
@@ -1615,6 +1633,9 @@ __global__ void __launch_bounds__(256) k_render_bw(GsCam cam, const uint32_t* __
 
 // ------------------------------------------------------------------------------------------------ 7. preprocess backward
 // One visible Gaussian.  sh_row: this Gaussian's SH coefficients in LDS (3*M floats); each is replaced in place by its gradient.
+// AA (group 27): the forward blended o * comp (preprocess_one<true>), so slot r0.w is g = dL/d(o comp): dL/do = g comp, and above the floor of comp the gradient
+// reaches the undilated covariance (a0, b, c0) through comp = sqrt(det0 / det1) as well -- three terms added to dL_da / dL_dc / dL_db in front of the existing chain.
+template <bool AA = false>
 __device__ __forceinline__ void preprocess_bw_one(int i, const GsCam& cam, const float* __restrict__ means3D, float* sh_row, int use_sh,
                                                   const float* __restrict__ scales, const float* __restrict__ rotations, int use_scale_rot,
                                                   const uint8_t* __restrict__ clamped, const float* __restrict__ cov3D,
@@ -1637,12 +1658,14 @@ __device__ __forceinline__ void preprocess_bw_one(int i, const GsCam& cam, const
     }
     const float gcol[3] = {r0.x, r0.y, r0.z};
     {
-        float g_op = r0.w;
-        if (cam.raw && opacities) {  // dL/dlogit = dL/dopacity * o (1 - o)
-            const float o_act = act_sigmoid(opacities[i]);
-            g_op *= o_act * (1.f - o_act);
-        }
-        dL_dopacity[i] = g_op;
+        if constexpr (!AA) {
+            float g_op = r0.w;
+            if (cam.raw && opacities) {  // dL/dlogit = dL/dopacity * o (1 - o)
+                const float o_act = act_sigmoid(opacities[i]);
+                g_op *= o_act * (1.f - o_act);
+            }
+            dL_dopacity[i] = g_op;
+        }   // (AA: written below, once comp is known)
         dL_dmean2D[3 * i] = r1.x; dL_dmean2D[3 * i + 1] = r1.y; dL_dmean2D[3 * i + 2] = 0.f;
         if (dL_dconic) *reinterpret_cast<float4*>(dL_dconic + 4 * (size_t)i) = make_float4(r1.z, r1.w, 0.f, r2x);
         if (dL_dcolor) { dL_dcolor[3 * i] = gcol[0]; dL_dcolor[3 * i + 1] = gcol[1]; dL_dcolor[3 * i + 2] = gcol[2]; }
@@ -1658,18 +1681,44 @@ __device__ __forceinline__ void preprocess_bw_one(int i, const GsCam& cam, const
     xform43(mean, vm, t);
     proj_jac(t, fx, fy, cam.tan_fovx, cam.tan_fovy, vm, Mx, My, tc, &gmx, &gmy);
     sym_mul(c3, Mx, sx); sym_mul(c3, My, sy);
-    const float a = Mx[0] * sx[0] + Mx[1] * sx[1] + Mx[2] * sx[2] + 0.3f;
+    float a0 = 0.f, c0 = 0.f, a, c;   // AA: the projected covariance before the dilation
+    if constexpr (AA) {
+        a0 = Mx[0] * sx[0] + Mx[1] * sx[1] + Mx[2] * sx[2];
+        a = a0 + 0.3f;
+    } else a = Mx[0] * sx[0] + Mx[1] * sx[1] + Mx[2] * sx[2] + 0.3f;
     const float b = Mx[0] * sy[0] + Mx[1] * sy[1] + Mx[2] * sy[2];
-    const float c = My[0] * sy[0] + My[1] * sy[1] + My[2] * sy[2] + 0.3f;
+    if constexpr (AA) {
+        c0 = My[0] * sy[0] + My[1] * sy[1] + My[2] * sy[2];
+        c = c0 + 0.3f;
+    } else c = My[0] * sy[0] + My[1] * sy[1] + My[2] * sy[2] + 0.3f;
     const float gcx = r1.z, gcy = r1.w, gcz = r2x;
     const float denom = a * c - b * b;
     const float denom2inv = 1.0f / (denom * denom + 0.0000001f);
+    float aa_da = 0.f, aa_dc = 0.f, aa_db = 0.f;
+    if constexpr (AA) {
+        const float g = r0.w;   // dL/d(o comp)
+        const float o_act = cam.raw ? act_sigmoid(opacities[i]) : opacities[i];
+        const float det0 = a0 * c0 - b * b, det1 = denom;
+        const float rho = det0 / det1;
+        const float comp = sqrtf(fmaxf(0.000025f, rho));
+        float g_op = g * comp;
+        if (cam.raw) g_op *= o_act * (1.f - o_act);   // dL/dlogit = dL/dopacity * o (1 - o)
+        dL_dopacity[i] = g_op;
+        if (rho > 0.000025f) {   // at or below the floor comp is a constant: nothing reaches the covariance
+            const float k = g * o_act / (2.f * comp);
+            const float det1sq = det1 * det1;
+            aa_da = k * (c0 * det1 - c * det0) / det1sq;
+            aa_dc = k * (a0 * det1 - a * det0) / det1sq;
+            aa_db = k * (-2.f * b) * (det1 - det0) / det1sq;
+        }
+    }
     float dL_da = 0, dL_db = 0, dL_dc = 0;
     float o[6] = {0, 0, 0, 0, 0, 0};
     if (denom2inv != 0) {
         dL_da = denom2inv * (-c * c * gcx + 2 * b * c * gcy + (denom - a * c) * gcz);
         dL_dc = denom2inv * (-a * a * gcz + 2 * a * b * gcy + (denom - a * c) * gcx);
         dL_db = denom2inv * 2 * (b * c * gcx - (denom + 2 * b * b) * gcy + a * b * gcz);
+        if constexpr (AA) { dL_da += aa_da; dL_dc += aa_dc; dL_db += aa_db; }
         o[0] = Mx[0] * Mx[0] * dL_da + Mx[0] * My[0] * dL_db + My[0] * My[0] * dL_dc;
         o[3] = Mx[1] * Mx[1] * dL_da + Mx[1] * My[1] * dL_db + My[1] * My[1] * dL_dc;
         o[5] = Mx[2] * Mx[2] * dL_da + Mx[2] * My[2] * dL_db + My[2] * My[2] * dL_dc;
@@ -1823,7 +1872,7 @@ struct RestAdam { float* p; float* m; float* v; float lr, beta1, beta2, eps, bc1
 #ifndef PBW_MAXM
 #define PBW_MAXM 16
 #endif
-template <int FORM>   // 0: one (P, M, 3) SH tensor; 1: dc + rest; 2: dc + rest with the Adam step of `rest` inside (RestAdam)
+template <int FORM, bool AA = false>   // 0: one (P, M, 3) SH tensor; 1: dc + rest; 2: dc + rest with the Adam step of `rest` inside (RestAdam); AA: FORM 0 and 1 only
 __global__ void __launch_bounds__(PBW_BLOCK) k_preprocess_bw(int P, GsCam cam_arg, const float* __restrict__ pose, const float* __restrict__ means3D, const float* __restrict__ shs,
                                                              const float* __restrict__ shs_rest, const float* __restrict__ opacities, int use_sh, const float* __restrict__ scales, const float* __restrict__ rotations,
                                                              int use_scale_rot, const int32_t* __restrict__ radii, const uint8_t* __restrict__ clamped,
@@ -1832,6 +1881,7 @@ __global__ void __launch_bounds__(PBW_BLOCK) k_preprocess_bw(int P, GsCam cam_ar
                                                              float* __restrict__ dL_dmean3D, float* __restrict__ dL_dcov3D, float* __restrict__ dL_dsh,
                                                              float* __restrict__ dL_dsh_rest, float* __restrict__ dL_dscale, float* __restrict__ dL_drot,
                                                              float* __restrict__ dL_dopacity, RestAdam ra, float* __restrict__ dL_dmean2D_abs) {
+    static_assert(!(AA && FORM == 2), "no anti-aliased form of the backward that steps `rest`");
     __shared__ float s_sh[PBW_BLOCK * (3 * PBW_MAXM + 1)];
     const GsCam cam = cam_with_pose(cam_arg, pose);
     const int first = blockIdx.x * PBW_BLOCK, i = first + threadIdx.x;
@@ -1841,12 +1891,12 @@ __global__ void __launch_bounds__(PBW_BLOCK) k_preprocess_bw(int P, GsCam cam_ar
     if (use_sh) {
         // 12 elements per trip here (k_preprocess: 16): with 16 this kernel's 204 VGPRs left the split-SH form of the training step at 168-179 us against
         // 133-138 with 12 or 8 (the concatenated form 139 -> 128; tools/exp_gs_pre.py, round 6)
-        sh_rows_copy<true, (FORM == 0 ? SHB_U : PBW_SHB_U), FORM != 0>(s_sh, pitch, row_len, count, (size_t)first, const_cast<float*>(shs), const_cast<float*>(shs_rest), PBW_BLOCK);
+        sh_rows_copy<true, (FORM == 0 ? SHB_U : PBW_SHB_U), FORM != 0, (AA ? 1 : 0)>(s_sh, pitch, row_len, count, (size_t)first, const_cast<float*>(shs), const_cast<float*>(shs_rest), PBW_BLOCK);
         __syncthreads();
     }
     float* sh_row = s_sh + threadIdx.x * pitch;
     if (visible) {
-        preprocess_bw_one(i, cam, means3D, sh_row, use_sh, scales, rotations, use_scale_rot, clamped, cov3D, grad_rec, dL_dmean2D, dL_dconic, dL_dcolor,
+        preprocess_bw_one<AA>(i, cam, means3D, sh_row, use_sh, scales, rotations, use_scale_rot, clamped, cov3D, grad_rec, dL_dmean2D, dL_dconic, dL_dcolor,
                           dL_dmean3D, dL_dcov3D, dL_dscale, dL_drot, opacities, dL_dopacity, dL_dmean2D_abs);
     } else if (i < P) {
         if (dL_dmean2D_abs) { dL_dmean2D_abs[3 * i] = 0.f; dL_dmean2D_abs[3 * i + 1] = 0.f; dL_dmean2D_abs[3 * i + 2] = 0.f; }
@@ -1869,7 +1919,7 @@ __global__ void __launch_bounds__(PBW_BLOCK) k_preprocess_bw(int P, GsCam cam_ar
     if (use_sh) {
         __syncthreads();
         if constexpr (FORM != 2) {
-            sh_rows_copy<false, (FORM == 0 ? SHB_U : PBW_SHB_U), FORM != 0>(s_sh, pitch, row_len, count, (size_t)first, dL_dsh, dL_dsh_rest, PBW_BLOCK);
+            sh_rows_copy<false, (FORM == 0 ? SHB_U : PBW_SHB_U), FORM != 0, (AA ? 1 : 0)>(s_sh, pitch, row_len, count, (size_t)first, dL_dsh, dL_dsh_rest, PBW_BLOCK);
         } else {
             // dc gradient rows as usual (3 floats per Gaussian), then Adam over the block's `rest` rows: element k of the contiguous (count, row_len - 3) block, gradient
             // from LDS (invisible Gaussians: zeros -- their moments decay and their parameters move like in the optimizer's own launch)
@@ -2268,7 +2318,7 @@ static int gs_preprocess_impl(int32_t P, int32_t D, int32_t M, int32_t W, int32_
                       float* points_xy, float* conic_opacity, float* rgb, uint8_t* clamped, float* cov3D, uint32_t* tiles_touched,
                       uint32_t* tile_counts, uint32_t* ranges, uint32_t* tile_fill, uint32_t* bin_hist, int64_t span_capacity,
                       int64_t instance_capacity, float* splat_records, int64_t* num_rendered, int64_t* count_mailbox, int64_t mailbox_ticket,
-                      int32_t yb0, int32_t n_rows, uint8_t* band_mask, nrc_stream_t stream) {
+                      int32_t yb0, int32_t n_rows, uint8_t* band_mask, nrc_stream_t stream, bool antialias = false) {
     GsCam cam;
     const int rc = make_cam(cam, W, H, D, M, viewmatrix_host, projmatrix_host, campos_host, camera_dev, tan_fovx, tan_fovy, scale_modifier, raw_parameters);
     if (rc != NRC_OK) return rc;
@@ -2298,8 +2348,11 @@ static int gs_preprocess_impl(int32_t P, int32_t D, int32_t M, int32_t W, int32_
         const int pre_blocks = (int)nrc_cdiv(P, PRE_BLOCK);
 #define GS_PRE_ARGS P, cam, camera_dev, means3D, shs, shs_rest, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii, depths, points_xy, conic_opacity, rgb, \
                     clamped, cov3D, tiles_touched, lds_path ? (uint32_t*)nullptr : tile_counts, (float4*)splat_records, lds_path ? w.hdr : (uint32_t*)nullptr
-        if (shs_rest) hipLaunchKernelGGL((k_preprocess<true>), dim3(pre_blocks), dim3(PRE_BLOCK), 0, s, GS_PRE_ARGS);
-        else hipLaunchKernelGGL((k_preprocess<false>), dim3(pre_blocks), dim3(PRE_BLOCK), 0, s, GS_PRE_ARGS);
+        if (!antialias) {
+            if (shs_rest) hipLaunchKernelGGL((k_preprocess<true>), dim3(pre_blocks), dim3(PRE_BLOCK), 0, s, GS_PRE_ARGS);
+            else hipLaunchKernelGGL((k_preprocess<false>), dim3(pre_blocks), dim3(PRE_BLOCK), 0, s, GS_PRE_ARGS);
+        } else if (shs_rest) hipLaunchKernelGGL((k_preprocess<true, true>), dim3(pre_blocks), dim3(PRE_BLOCK), 0, s, GS_PRE_ARGS);   // group 27: instances of their own
+        else hipLaunchKernelGGL((k_preprocess<false, true>), dim3(pre_blocks), dim3(PRE_BLOCK), 0, s, GS_PRE_ARGS);
         NRC_STAGE(s, "k_preprocess");
 #undef GS_PRE_ARGS
         if (lds_path) {
@@ -2465,7 +2518,7 @@ static int gs_backward_impl(int32_t P, int32_t D, int32_t M, int32_t W, int32_t 
                     float* dL_dmean2D, float* dL_dconic,
                     float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dsh_rest, float* dL_dscale,
                     float* dL_drot, float* grad_records, int32_t records_clear, nrc_stream_t stream, RestAdam ra, int32_t n_rows, const float* dL_ddepth_alpha,
-                    float* pose_partials = nullptr, float* dL_dcamera = nullptr, float* dL_dmean2D_abs = nullptr) {
+                    float* pose_partials = nullptr, float* dL_dcamera = nullptr, float* dL_dmean2D_abs = nullptr, bool antialias = false) {
     GsCam cam;
     const int rc = make_cam(cam, W, H, D, M, viewmatrix_host, projmatrix_host, campos_host, camera_dev, tan_fovx, tan_fovy, scale_modifier, raw_parameters);
     if (rc != NRC_OK) return rc;
@@ -2473,6 +2526,8 @@ static int gs_backward_impl(int32_t P, int32_t D, int32_t M, int32_t W, int32_t 
     const float bg[3] = {bg_host ? bg_host[0] : 0.f, bg_host ? bg_host[1] : 0.f, bg_host ? bg_host[2] : 0.f};
     if (dL_dcamera && (!pose_partials || ra.p)) return NRC_ERR_INVALID;   // (there is no camera gradient in the form that steps `rest`)
     if (dL_dmean2D_abs && ra.p) return NRC_ERR_INVALID;                   // (nor an absgrad form of it)
+    if (antialias && (ra.p || dL_dcamera)) return NRC_ERR_UNSUPPORTED;    // (no anti-aliased form of k_preprocess_bw<2> or of pose_bw_one)
+    if (antialias && P > 0 && !opacities) return NRC_ERR_INVALID;         // (dL/dcov2D through comp carries the opacity: activated values are read as well)
     if (P == 0) {
         if (dL_dcamera) {   // no Gaussians: the camera gradient is 35 zeros
             hipLaunchKernelGGL(k_pose_finish, dim3(1), dim3(POSE_FIN_GROUPS * POSE_SLAB), 0, (hipStream_t)stream, 0, (const float*)pose_partials, dL_dcamera);
@@ -2520,9 +2575,12 @@ static int gs_backward_impl(int32_t P, int32_t D, int32_t M, int32_t W, int32_t 
     }
 #define GS_PBW_ARGS P, cam, camera_dev, means3D, shs, shs_rest, opacities, use_sh, scales, rotations, use_sr, radii, clamped, cov3D, grad_records, dL_dmean2D, dL_dconic, dL_dcolor, \
                     dL_dmean3D, dL_dcov3D, dL_dsh, dL_dsh_rest, dL_dscale, dL_drot, dL_dopacity, ra, dL_dmean2D_abs
-    if (ra.p) hipLaunchKernelGGL(k_preprocess_bw<2>, dim3(nrc_cdiv(P, PBW_BLOCK)), dim3(PBW_BLOCK), 0, s, GS_PBW_ARGS);
-    else if (shs_rest) hipLaunchKernelGGL(k_preprocess_bw<1>, dim3(nrc_cdiv(P, PBW_BLOCK)), dim3(PBW_BLOCK), 0, s, GS_PBW_ARGS);
-    else hipLaunchKernelGGL(k_preprocess_bw<0>, dim3(nrc_cdiv(P, PBW_BLOCK)), dim3(PBW_BLOCK), 0, s, GS_PBW_ARGS);
+    if (!antialias) {
+        if (ra.p) hipLaunchKernelGGL(k_preprocess_bw<2>, dim3(nrc_cdiv(P, PBW_BLOCK)), dim3(PBW_BLOCK), 0, s, GS_PBW_ARGS);
+        else if (shs_rest) hipLaunchKernelGGL(k_preprocess_bw<1>, dim3(nrc_cdiv(P, PBW_BLOCK)), dim3(PBW_BLOCK), 0, s, GS_PBW_ARGS);
+        else hipLaunchKernelGGL(k_preprocess_bw<0>, dim3(nrc_cdiv(P, PBW_BLOCK)), dim3(PBW_BLOCK), 0, s, GS_PBW_ARGS);
+    } else if (shs_rest) hipLaunchKernelGGL((k_preprocess_bw<1, true>), dim3(nrc_cdiv(P, PBW_BLOCK)), dim3(PBW_BLOCK), 0, s, GS_PBW_ARGS);   // group 27
+    else hipLaunchKernelGGL((k_preprocess_bw<0, true>), dim3(nrc_cdiv(P, PBW_BLOCK)), dim3(PBW_BLOCK), 0, s, GS_PBW_ARGS);
 #undef GS_PBW_ARGS
     NRC_STAGE(s, "k_preprocess_bw");
     NRC_LAUNCH_CHECK();
@@ -2624,6 +2682,42 @@ int nrc_gs_backward_absgrad_band(int32_t P, int32_t D, int32_t M, int32_t W, int
                             ranges, splat_records, tile_order, n_contrib, final_T, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
                             dL_dsh_rest, dL_dscale, dL_drot, grad_records, records_clear, stream, RestAdam{nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, 0.f, 1.f, 1.f}, n_tile_rows,
                             dL_ddepth_alpha, dL_dcamera ? pose_partials : nullptr, dL_dcamera, dL_dmean2D_abs);
+}
+
+/* group 27 (anti-aliased splats): nrc_gs_preprocess_band / nrc_gs_backward_absgrad_band through the AA instances of the two per-Gaussian kernels */
+int nrc_gs_preprocess_antialias_band(int32_t P, int32_t D, int32_t M, int32_t W, int32_t H, const float* means3D, const float* shs, const float* shs_rest,
+                      int32_t raw_parameters, const float* colors_precomp, const float* opacities, const float* scales, float scale_modifier,
+                      const float* rotations, const float* cov3D_precomp, const float* viewmatrix_host, const float* projmatrix_host,
+                      const float* campos_host, const float* camera_dev, float tan_fovx, float tan_fovy, int32_t* radii, float* depths,
+                      float* points_xy, float* conic_opacity, float* rgb, uint8_t* clamped, float* cov3D, uint32_t* tiles_touched,
+                      uint32_t* tile_counts, uint32_t* ranges, uint32_t* tile_fill, uint32_t* bin_hist, int64_t span_capacity,
+                      int64_t instance_capacity, float* splat_records, int64_t* num_rendered, int64_t* count_mailbox, int64_t mailbox_ticket,
+                      int32_t tile_row_begin, int32_t n_tile_rows, uint8_t* band_mask, nrc_stream_t stream) {
+    if (!gs_band_ok(H, tile_row_begin, n_tile_rows)) return NRC_ERR_INVALID;
+    NRC_ENTER();
+    return gs_preprocess_impl(P, D, M, W, H, means3D, shs, shs_rest, raw_parameters, colors_precomp, opacities, scales, scale_modifier, rotations, cov3D_precomp,
+                              viewmatrix_host, projmatrix_host, campos_host, camera_dev, tan_fovx, tan_fovy, radii, depths, points_xy, conic_opacity, rgb, clamped, cov3D,
+                              tiles_touched, tile_counts, ranges, tile_fill, bin_hist, span_capacity, instance_capacity, splat_records, num_rendered, count_mailbox,
+                              mailbox_ticket, tile_row_begin, n_tile_rows, band_mask, stream, true);
+}
+int nrc_gs_backward_antialias_band(int32_t P, int32_t D, int32_t M, int32_t W, int32_t H, const float* bg_host, const float* means3D, const float* shs,
+                    const float* shs_rest, int32_t raw_parameters, const float* opacities, const float* colors_precomp, const float* scales, float scale_modifier, const float* rotations,
+                    const float* cov3D_precomp, const float* viewmatrix_host, const float* projmatrix_host, const float* campos_host,
+                    const float* camera_dev, float tan_fovx, float tan_fovy, const int32_t* radii, const float* points_xy, const float* conic_opacity,
+                    const float* rgb, const uint8_t* clamped, const float* cov3D, const int32_t* point_list, const uint32_t* ranges,
+                    const float* splat_records, const uint32_t* tile_order, const uint32_t* n_contrib, const float* final_T, const float* dL_dpix,
+                    float* dL_dmean2D, float* dL_dconic,
+                    float* dL_dopacity, float* dL_dcolor, float* dL_dmean3D, float* dL_dcov3D, float* dL_dsh, float* dL_dsh_rest, float* dL_dscale,
+                    float* dL_drot, float* grad_records, int32_t records_clear, int32_t tile_row_begin, int32_t n_tile_rows, const float* dL_ddepth_alpha,
+                    float* pose_partials, float* dL_dcamera, float* dL_dmean2D_abs, nrc_stream_t stream) {
+    if (!gs_band_ok(H, tile_row_begin, n_tile_rows)) return NRC_ERR_INVALID;
+    if (dL_dcamera) return NRC_ERR_UNSUPPORTED;   // pose_bw_one has no anti-aliased form
+    NRC_ENTER();
+    return gs_backward_impl(P, D, M, W, H, bg_host, means3D, shs, shs_rest, raw_parameters, opacities, colors_precomp, scales, scale_modifier, rotations, cov3D_precomp,
+                            viewmatrix_host, projmatrix_host, campos_host, camera_dev, tan_fovx, tan_fovy, radii, points_xy, conic_opacity, rgb, clamped, cov3D, point_list,
+                            ranges, splat_records, tile_order, n_contrib, final_T, dL_dpix, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dmean3D, dL_dcov3D, dL_dsh,
+                            dL_dsh_rest, dL_dscale, dL_drot, grad_records, records_clear, stream, RestAdam{nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, 0.f, 1.f, 1.f}, n_tile_rows,
+                            dL_ddepth_alpha, nullptr, nullptr, dL_dmean2D_abs, true);
 }
 
 int nrc_gs_camera_block_backward(const float* c2w_dev, const float* proj_t_dev, const float* dL_dcamera, float* dL_dc2w_out, nrc_stream_t stream) {

@@ -38,6 +38,7 @@ class GaussianRasterizationSettings(NamedTuple):
     campos: torch.Tensor
     prefiltered: bool
     debug: bool
+    antialiasing: bool = False   # upstream's trailing field: anti-aliased splats (see GaussianRasterizer.forward)
 
 
 _CAMERA_BLOCKS: dict = {}
@@ -157,7 +158,7 @@ def _opt(t):
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, sh_rest=None, raw=False, rest_step=None, tile_rows=None,
-                depth_alpha=False, viewmatrix=None, projmatrix=None, campos=None, features=None, absgrad=False):
+                depth_alpha=False, viewmatrix=None, projmatrix=None, campos=None, features=None, absgrad=False, antialiasing=False):
         rs = raster_settings
         lib = _lib.load()
         band = check_tile_rows(tile_rows, rs.image_height)
@@ -181,6 +182,11 @@ class _RasterizeGaussians(torch.autograd.Function):
         if absgrad and features is not None:
             raise RuntimeError('absgrad together with features: the feature backward (nrc_gs_backward_features_band) forms its share of dL/dalpha in another kernel, '
                                'and |a + b| per pixel cannot be assembled from two kernels\' sums -- there is no absgrad form of it; render the features in a call of their own')
+        antialiasing = bool(antialiasing) or bool(getattr(rs, 'antialiasing', False))
+        if antialiasing and rest_step is not None:
+            raise RuntimeError(_AA_REST_STEP)
+        if antialiasing and viewmatrix is not None:
+            raise RuntimeError(_AA_CAMERA_GRAD)
         if band is not None and rest_step is not None:
             raise RuntimeError('rest_step together with tile_rows: the backward pass of a band holds this band\'s SHARE of the gradient only, and an Adam step '
                                'taken on a partial gradient is not the optimizer\'s step -- sum the shares over the bands first and step then')
@@ -244,6 +250,15 @@ class _RasterizeGaussians(torch.autograd.Function):
         def preprocess(cap_spans, cap_inst, box=None, ticket=0):
             hist_bytes = int(lib.nrc_gs_bin_hist_bytes(P, W, H, cap_spans))
             hist = torch.empty(hist_bytes // 4, dtype=i32, device=dev) if hist_bytes > 0 else None
+            if antialiasing:   # the anti-aliased instance of the per-Gaussian kernel (a whole frame = the band of all gy tile rows)
+                b0, bn = band if band is not None else (0, gy)
+                _lib.check(lib.nrc_gs_preprocess_antialias_band(
+                    P, D, M, W, H, _lib.ptr(means3D_c), _lib.ptr(sh_c), _lib.ptr(rest_c), int(raw), _lib.ptr(col_c), _lib.ptr(op_c), _lib.ptr(sc_c), float(rs.scale_modifier),
+                    _lib.ptr(rot_c), _lib.ptr(cov_c), None, None, None, _lib.ptr(cam_block), float(rs.tanfovx), float(rs.tanfovy), _lib.ptr(radii), _lib.ptr(depths),
+                    _lib.ptr(points_xy), _lib.ptr(conic_opacity), _lib.ptr(rgb), _lib.ptr(clamped), _lib.ptr(cov3D), _lib.ptr(tiles_touched),
+                    _lib.ptr(tile_counts), _lib.ptr(ranges), _lib.ptr(tile_fill), _lib.ptr(hist), cap_spans, cap_inst, _lib.ptr(splat), _lib.ptr(num_rendered),
+                    box if hist is not None else None, ticket, b0, bn, _lib.ptr(band_mask), st), 'gs_preprocess_antialias_band')
+                return hist
             if band is not None:
                 _lib.check(lib.nrc_gs_preprocess_band(
                     P, D, M, W, H, _lib.ptr(means3D_c), _lib.ptr(sh_c), _lib.ptr(rest_c), int(raw), _lib.ptr(col_c), _lib.ptr(op_c), _lib.ptr(sc_c), float(rs.scale_modifier),
@@ -366,6 +381,7 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.depth_alpha = depth_alpha
         # absgrad: the backward leaves sum_pixels |dL_pixel/dmean2D| on the tensor OBJECT the caller passed as means2D (weakly held: ctx must not keep it alive)
         ctx.absgrad = weakref.ref(means2D) if absgrad else None
+        ctx.antialiasing = antialiasing
         ctx.raster_settings = rs
         ctx.dims = (P, D, M, W, H)
         ctx.num_rendered = n_inst if fixed is None else -1
@@ -452,7 +468,23 @@ class _RasterizeGaussians(torch.autograd.Function):
             elif ctx.features_grad:
                 dfeat = torch.zeros(n1, C_f, dtype=f32, device=dev)
         dcam = None
-        if ctx.absgrad is not None:
+        if ctx.antialiasing:
+            # the anti-aliased instance of the per-Gaussian backward behind the same blend backward; the maps' gradients and the absgrad sums stay optional.  The
+            # activated opacities the forward read are handed over also without raw parameters: dL/dcov2D through comp carries them
+            b0, bn = ctx.band if ctx.band is not None else (0, (H + 15) // 16)
+            dabs = torch.empty(P, 3, dtype=f32, device=dev) if ctx.absgrad is not None else None
+            _lib.check(lib.nrc_gs_backward_antialias_band(
+                P, D, M, W, H, None, _lib.ptr(means3D), _lib.ptr(sh if has_sh else None), _lib.ptr(sh_rest if has_rest else None), int(raw),
+                _lib.ptr(opac), _lib.ptr(col if has_col else None),
+                _lib.ptr(sc if has_sr else None), float(rs.scale_modifier), _lib.ptr(rot if has_sr else None), _lib.ptr(cov if has_cov else None),
+                None, None, None, _lib.ptr(cam_block), float(rs.tanfovx), float(rs.tanfovy), _lib.ptr(radii), _lib.ptr(points_xy), _lib.ptr(conic_opacity),
+                _lib.ptr(rgb), _lib.ptr(clamped), _lib.ptr(cov3D), _lib.ptr(point_list), _lib.ptr(ranges), _lib.ptr(splat), _lib.ptr(tile_order), _lib.ptr(n_contrib), _lib.ptr(final_T),
+                _lib.ptr(g), _lib.ptr(dmean2D), None, _lib.ptr(dopacity), _lib.ptr(dcolor), _lib.ptr(dmean3D), _lib.ptr(dcov3D),
+                _lib.ptr(dsh), _lib.ptr(dsh_rest), _lib.ptr(dscale), _lib.ptr(drot), _lib.ptr(grad_records), int(records_clear), b0, bn, _lib.ptr(g_aux),
+                None, None, _lib.ptr(dabs) if dabs is not None and P > 0 else None, _lib.stream_of(g)), 'gs_backward_antialias_band')
+            if dabs is not None:
+                _leave_absgrad(ctx.absgrad(), dabs)
+        elif ctx.absgrad is not None:
             # the instances of the blend backward that also sum |dL_pixel/dmean2D| (slots [10], [11] of the records), with or without the maps and the camera gradient
             b0, bn = ctx.band if ctx.band is not None else (0, (H + 15) // 16)
             partials = None
@@ -469,14 +501,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                 _lib.ptr(g), _lib.ptr(dmean2D), None, _lib.ptr(dopacity), _lib.ptr(dcolor), _lib.ptr(dmean3D), _lib.ptr(dcov3D),
                 _lib.ptr(dsh), _lib.ptr(dsh_rest), _lib.ptr(dscale), _lib.ptr(drot), _lib.ptr(grad_records), int(records_clear), b0, bn, _lib.ptr(g_aux),
                 _lib.ptr(partials), _lib.ptr(dcam), _lib.ptr(dabs) if P > 0 else None, _lib.stream_of(g)), 'gs_backward_absgrad_band')
-            target = ctx.absgrad()
-            if target is not None:
-                # like .grad it accumulates: two bands rendered on one leaf sum to the frame
-                have = getattr(target, 'absgrad', None)
-                if torch.is_tensor(have) and have.shape == dabs.shape and have.dtype == f32 and have.device == dabs.device:
-                    have.add_(dabs)
-                else:
-                    target.absgrad = dabs
+            _leave_absgrad(ctx.absgrad(), dabs)
         elif ctx.camera is not None:
             # the same backward with two extra launches between the blend backward and the per-Gaussian backward: dL/d(viewmatrix | projmatrix | campos) as float[35]
             b0, bn = ctx.band if ctx.band is not None else (0, (H + 15) // 16)
@@ -544,7 +569,26 @@ class _RasterizeGaussians(torch.autograd.Function):
             + (() if feat is None else (cut(dfeat) if dfeat is not None else None,))
         if ctx.absgrad is not None:   # the call passed every input up to the flag: their positions are filled
             grads += (None,) * (19 - len(grads))
+        if ctx.antialiasing:          # (likewise: 20 inputs)
+            grads += (None,) * (20 - len(grads))
         return grads
+
+
+_AA_REST_STEP = ('antialiasing together with rest_step: the backward pass that steps the `rest` SH tensor (nrc_gs_backward_rest_step) has no anti-aliased form -- '
+                 'its per-Gaussian kernel does not carry the gradient through the opacity compensation; render without rest_step and let the optimizer take that step')
+_AA_CAMERA_GRAD = ('antialiasing together with camera_grad: the camera backward (nrc_gs_backward_pose_band) has no anti-aliased form -- the opacity compensation '
+                   'depends on the pose through the projected covariance, and that path is not built; render without camera_grad, or without antialiasing')
+
+
+def _leave_absgrad(target, dabs) -> None:
+    """`means2D.absgrad` of a backward with absgrad=True.  Like .grad it accumulates: two bands rendered on one leaf sum to the frame."""
+    if target is None:
+        return
+    have = getattr(target, 'absgrad', None)
+    if torch.is_tensor(have) and have.shape == dabs.shape and have.dtype == torch.float32 and have.device == dabs.device:
+        have.add_(dabs)
+    else:
+        target.absgrad = dabs
 
 
 def _check_features(features, P: int, dev) -> torch.Tensor:
@@ -573,12 +617,24 @@ def _camera_grads(camera, dcam, placeholders=False):
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, sh_rest=None, raw=False, rest_step=None, tile_rows=None,
-                        return_depth_alpha=False, camera_grad=False, features=None, absgrad=False):
+                        return_depth_alpha=False, camera_grad=False, features=None, absgrad=False, antialiasing=False):
     """`tile_rows` = (begin, n): render and differentiate the band of 16-pixel tile rows [begin, begin + n) only (see GaussianRasterizer.forward); None: the frame.
     `return_depth_alpha`: (image, radii, depth, alpha) instead of (image, radii) -- see GaussianRasterizer.forward.
     `camera_grad`: gradients to raster_settings.viewmatrix / projmatrix / campos, for those that require grad -- see GaussianRasterizer.forward.
     `features`: a (P, C) tensor blended by the colour's weights; appends feature_map (C, H, W) to the outputs -- see GaussianRasterizer.forward.
-    `absgrad`: the backward also leaves sum_pixels |dL_pixel/dmean2D| as means2D.absgrad -- see GaussianRasterizer.forward."""
+    `absgrad`: the backward also leaves sum_pixels |dL_pixel/dmean2D| as means2D.absgrad -- see GaussianRasterizer.forward.
+    `antialiasing` (or raster_settings.antialiasing): anti-aliased splats, the blended opacity is o * comp -- see GaussianRasterizer.forward."""
+    if antialiasing or getattr(raster_settings, 'antialiasing', False):
+        if rest_step is not None:
+            raise RuntimeError(_AA_REST_STEP)
+        if camera_grad:
+            raise RuntimeError(_AA_CAMERA_GRAD)
+        if absgrad and features is not None:
+            raise RuntimeError('absgrad together with features: the feature backward (nrc_gs_backward_features_band) forms its share of dL/dalpha in another kernel, '
+                               'and |a + b| per pixel cannot be assembled from two kernels\' sums -- there is no absgrad form of it; render the features in a call of their own')
+        return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, raster_settings, sh_rest, raw, None,
+                                         None if tile_rows is None else tuple(int(v) for v in tile_rows), bool(return_depth_alpha), None, None, None, features,
+                                         bool(absgrad), True)
     if absgrad:
         if rest_step is not None:
             raise RuntimeError('absgrad together with rest_step: the backward pass that steps the `rest` SH tensor (nrc_gs_backward_rest_step) takes the '
@@ -696,7 +752,7 @@ class GaussianRasterizer(torch.nn.Module):
             return z > 0.2
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, shs_rest=None,
-                raw_parameters=False, rest_step=None, tile_rows=None, return_depth_alpha=False, camera_grad=False, features=None, absgrad=False):
+                raw_parameters=False, rest_step=None, tile_rows=None, return_depth_alpha=False, camera_grad=False, features=None, absgrad=False, antialiasing=False):
         """The reference's call (Renderer.py:75-81) plus two keyword extensions for callers that own the model tensors: `shs_rest` -- `shs` is then
         (`rest_step`, round 6: an object whose take() returns (parameter, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, bc1, bc2) -- the backward pass then applies
         the optimizer's Adam step to shs_rest itself and returns no gradient for it: nerficg_amd.gaussian_splatting.RestStep)
@@ -734,7 +790,14 @@ class GaussianRasterizer(torch.nn.Module):
         those no pixel blended.  Like `.grad` it ACCUMULATES: a backward that finds an `absgrad` of the right shape adds to it (the bands of a partition rendered
         on one leaf sum to the frame's); delete or zero it between steps.  Outputs and every ordinary gradient are those of the call without the flag (same
         per-Gaussian sums; float atomics in another order); without the flag nothing changes.  Works with every parameter form above, with `tile_rows`,
-        `return_depth_alpha`, `camera_grad` and inside fixed_capacity (no host read is added); not together with `rest_step` or `features` (RuntimeError)."""
+        `return_depth_alpha`, `camera_grad` and inside fixed_capacity (no host read is added); not together with `rest_step` or `features` (RuntimeError).
+        `antialiasing=True` (or `antialiasing=True` in the settings, upstream's field; either turns it on): anti-aliased splats, the 2-D filter of Mip-Splatting.
+        The 0.3-pixel dilation of the projected covariance adds energy; the flag takes it back: the opacity that is blended is o * comp,
+        comp = sqrt(max(0.000025, det(cov2D) / det(cov2D + 0.3 I))) (gsplat's rasterize_mode="antialiased").  Radii, tile lists, conics and colours are bit for bit
+        those of the call without the flag, and the call equals, bit for bit, the call without the flag on the compensated opacities; the backward carries the
+        gradient through comp to the opacities and, above the floor, to scales, rotations, cov3D_precomp and means3D (`means2D.grad` and `means2D.absgrad` are
+        unchanged by it).  Works with every parameter form above, with `tile_rows`, `return_depth_alpha`, `features`, `absgrad`, contributions() and inside
+        fixed_capacity; not together with `rest_step` or `camera_grad` (RuntimeError)."""
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception('Please provide excatly one of either SHs or precomputed colors!')
         if ((scales is None or rotations is None) and cov3D_precomp is None) or ((scales is not None or rotations is not None) and cov3D_precomp is not None):
@@ -746,7 +809,7 @@ class GaussianRasterizer(torch.nn.Module):
         try:
             out = rasterize_gaussians(means3D, means2D, empty if shs is None else shs, empty if colors_precomp is None else colors_precomp, opacities,
                                       empty if scales is None else scales, empty if rotations is None else rotations,
-                                      empty if cov3D_precomp is None else cov3D_precomp, self.raster_settings, shs_rest, raw_parameters, rest_step, tile_rows, return_depth_alpha, camera_grad, features, absgrad)
+                                      empty if cov3D_precomp is None else cov3D_precomp, self.raster_settings, shs_rest, raw_parameters, rest_step, tile_rows, return_depth_alpha, camera_grad, features, absgrad, antialiasing)
         finally:
             _FRAME_STATE_SINK[0] = previous
         self._frame_state = sink[-1] if sink else None   # what contributions() runs on: references to tensors the forward created anyway

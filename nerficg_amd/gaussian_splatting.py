@@ -286,6 +286,22 @@ def mcmc_regulariser_grads(opacity_logits: torch.Tensor, log_scales: torch.Tenso
     return losses
 
 
+def filter_3d(positions: torch.Tensor, views: torch.Tensor) -> torch.Tensor:
+    """(P,) float32: nrc_gs_filter3d on positions (P, 3) and a (V, 20) float32 block of views on the same device -- per view the world-to-camera matrix row-major
+    (p_cam = m[:3, :3] p + m[:3, 3]), fx, fy, W, H.  See Gaussians.compute_3d_filter."""
+    from . import _lib
+    if not positions.is_cuda or views.device != positions.device:
+        raise RuntimeError('filter_3d: positions and views must be CUDA tensors on one device')
+    if positions.dim() != 2 or positions.shape[1] != 3 or views.dim() != 2 or views.shape[1] != 20 or views.shape[0] < 1:
+        raise RuntimeError(f'filter_3d: positions (P, 3) and views (V >= 1, 20) expected, got {tuple(positions.shape)} and {tuple(views.shape)}')
+    pos = positions.detach().to(torch.float32).contiguous()
+    blk = views.detach().to(torch.float32).contiguous()
+    out = torch.empty(pos.shape[0], dtype=torch.float32, device=pos.device)
+    ws = torch.empty(1, dtype=torch.int32, device=pos.device)
+    _lib.check(_lib.load().nrc_gs_filter3d(_lib.ptr(pos), pos.shape[0], _lib.ptr(blk), blk.shape[0], _lib.ptr(out), _lib.ptr(ws), _lib.stream_of(out)), 'gs_filter3d')
+    return out
+
+
 class Gaussians(torch.nn.Module):
     """Parameter store + activation accessors of GaussianSplatting/Model.py:18-87 (exp scales, normalised quaternions, sigmoid
     opacities, cat[dc, rest] SH features of shape (P, 16, 3)) and the training-time bookkeeping of Model.py:94-284: optimizer setup,
@@ -307,6 +323,7 @@ class Gaussians(torch.nn.Module):
         n, dev = positions.shape[0], positions.device
         self.densification_gradient_accum = torch.zeros((n, 1), dtype=torch.float32, device=dev)
         self.n_observations = torch.zeros((n, 1), dtype=torch.int32, device=dev)
+        self.filter_3D = None   # (P, 1) after compute_3d_filter(views); None again whenever the rows change
 
     @classmethod
     def from_point_cloud(cls, positions: torch.Tensor, colors: torch.Tensor | None = None, sh_degree: int = 3) -> 'Gaussians':
@@ -343,6 +360,51 @@ class Gaussians(torch.nn.Module):
     def get_features(self): return torch.cat((self._features_dc, self._features_rest), dim=1)
     @property
     def get_baked_covariances(self): return self._baked_covariances
+
+    # ---------------------------------------------------------------- the 3-D smoothing filter of Mip-Splatting
+    def _checked_filter_3d(self) -> torch.Tensor:
+        f = self.filter_3D
+        if f is None:
+            raise RuntimeError('the 3-D filter is not set: call compute_3d_filter(views) first (and again after every change of the number of Gaussians)')
+        if f.shape[0] != self._positions.shape[0]:
+            raise RuntimeError(f'filter_3D holds {f.shape[0]} rows, the model {self._positions.shape[0]} Gaussians: call compute_3d_filter(views) again')
+        return f
+
+    @property
+    def get_scales_with_3d_filter(self):
+        """sqrt(s^2 + f^2): the scales of the Gaussian convolved with the isotropic low-pass of width filter_3D (Mip-Splatting).  Plain differentiable torch."""
+        s = self.get_scales
+        return torch.sqrt(torch.square(s) + torch.square(self._checked_filter_3d()))
+
+    @property
+    def get_opacities_with_3d_filter(self):
+        """o sqrt(prod s^2 / prod (s^2 + f^2)): the opacity that keeps the Gaussian's integral under that convolution (Mip-Splatting).  Plain differentiable torch."""
+        s2 = torch.square(self.get_scales)
+        f2 = torch.square(self._checked_filter_3d())
+        return self.get_opacities * torch.sqrt(torch.prod(s2, dim=1) / torch.prod(s2 + f2, dim=1))[..., None]
+
+    @torch.no_grad()
+    def compute_3d_filter(self, views) -> torch.Tensor:
+        """Fills self.filter_3D, (P, 1): sqrt(0.2) times the smallest z / fx over the views that see the Gaussian -- the largest sampling rate any training view
+        has of it, as a Gaussian low-pass in world units (Mip-Splatting's compute_3D_filter; one kernel, nrc_gs_filter3d).  `views`: an iterable of
+        (PerspectiveCamera, c2w).  A view sees a Gaussian iff its view-space z > 0.2 and its pixel lies in the frame widened by 15 % on every side; a Gaussian
+        that no view sees gets the largest filter among the seen ones.  The published code divides the smallest z by the largest focal length of all views;
+        the per-view ratio z / fx used here equals it for equal focal lengths.  Any change of the number of Gaussians (prune_points, densify_and_prune,
+        relocate, add_new) sets filter_3D back to None: call this again, as Mip-Splatting does after every densification."""
+        pos = self._positions.detach().to(torch.float32).contiguous()
+        dev = pos.device
+        rows = []
+        for cam, c2w in views:
+            pose = torch.as_tensor(np.asarray(c2w.detach().cpu()) if torch.is_tensor(c2w) else np.asarray(c2w), dtype=torch.float64)
+            m = torch.eye(4, dtype=torch.float64)
+            m[:3, :4] = pose[:3, :4]
+            w2c = torch.linalg.inv(m)
+            rows.append(torch.cat([w2c.reshape(-1), torch.tensor([cam.focal_x, cam.focal_y, cam.width, cam.height], dtype=torch.float64)]))
+        if not rows:
+            raise RuntimeError('compute_3d_filter: at least one view is needed')
+        block = torch.stack(rows).to(device=dev, dtype=torch.float32).contiguous()
+        self.filter_3D = filter_3d(pos, block)[:, None]
+        return self.filter_3D
 
     def get_covariances(self, scale_modifier: float) -> torch.Tensor:
         """Model.py:84-86"""
@@ -416,6 +478,7 @@ class Gaussians(torch.nn.Module):
     def _adopt(self, tensors: dict[str, torch.Tensor]) -> None:
         for name, attr in self._GROUP_OF.items():
             setattr(self, attr, tensors[name])
+        self.filter_3D = None   # the rows changed: the caller computes the 3-D filter again
 
     # ---------------------------------------------------------------- densification (Model.py:152-246)
     def reset_opacities(self) -> None:
@@ -575,6 +638,7 @@ class Gaussians(torch.nn.Module):
         rows = adam_utils.gather_rows(tensors, drawn.to(torch.int32), n_dead)
         adam_utils.scatter_rows(rows, tensors, dead.to(torch.int32))
         self._drop_grads()
+        self.filter_3D = None   # rows moved: the caller computes the 3-D filter again
         return {'n_dead': n_dead, 'n_relocated': n_dead}
 
     @torch.no_grad()
@@ -719,8 +783,12 @@ class RestStep:
 
 def render_image_training(gaussians: Gaussians, cam: PerspectiveCamera, c2w: np.ndarray, fuse_rest_step: bool | None = None,
                           band: tuple[int, int] | None = None, depth_alpha: bool = False, camera_grad: bool | None = None,
-                          features: torch.Tensor | None = None, absgrad: bool = False) -> dict[str, torch.Tensor]:
-    """GaussianSplatting/Renderer.py:51-86.  absgrad: after backward() outputs['viewspace_points'].absgrad holds sum_pixels |dL_pixel/dmean2D| per Gaussian, (P, 3)
+                          features: torch.Tensor | None = None, absgrad: bool = False, antialiasing: bool = False) -> dict[str, torch.Tensor]:
+    """GaussianSplatting/Renderer.py:51-86.  antialiasing: anti-aliased splats (the rasterizer's `antialiasing`: the blended opacity is o * comp); the backward
+    that steps f_rest has no anti-aliased form: fuse_rest_step=None then resolves to "not fused", an explicit fuse_rest_step=True raises (RuntimeError), and
+    camera_grad is refused with it.  A model whose filter_3D is set (Gaussians.compute_3d_filter) is rendered with get_scales_with_3d_filter and
+    get_opacities_with_3d_filter through the activated-value path (autograd carries the gradients to the raw tensors; no fused f_rest step then either); a
+    filter of another length than the model raises.  absgrad: after backward() outputs['viewspace_points'].absgrad holds sum_pixels |dL_pixel/dmean2D| per Gaussian, (P, 3)
     with column 2 zero (the rasterizer's `absgrad`; Gaussians.add_densification_stats(..., use_absgrad=True) reads it).  The backward that steps f_rest has no
     absgrad form: fuse_rest_step=None then resolves to "not fused", an explicit fuse_rest_step=True raises (RuntimeError).  The same holds for a model set up with
     training_setup(sparse_adam=True): the in-backward f_rest step is dense over all rows, the masked step is Gaussians.optimizer_step(radii).  features: a (P, C) float32 tensor of the caller's (it is NOT carried through densification: the caller owns it); the
@@ -750,6 +818,18 @@ def render_image_training(gaussians: Gaussians, cam: PerspectiveCamera, c2w: np.
             raise RuntimeError('render_image_training: absgrad= together with the fused f_rest step -- the backward pass that steps f_rest takes the colour '
                                'gradient only (the rasterizer refuses absgrad with rest_step); leave fuse_rest_step off for frames that collect the abs-gradient')
         fuse = False
+    antialiasing = bool(antialiasing)
+    if antialiasing:
+        if fuse_rest_step is not None and fuse:
+            raise RuntimeError('render_image_training: antialiasing= together with the fused f_rest step -- the backward pass that steps f_rest has no anti-aliased '
+                               'form (the rasterizer refuses antialiasing with rest_step); leave fuse_rest_step off for anti-aliased frames')
+        fuse = False
+    filtered = getattr(gaussians, 'filter_3D', None) is not None
+    if filtered:
+        if fuse_rest_step is not None and fuse:
+            raise RuntimeError('render_image_training: fuse_rest_step=True on a model with a 3-D filter -- the filtered scales and opacities go through the '
+                               'activated-value path, which has no in-backward f_rest step; leave fuse_rest_step off')
+        fuse = False
     if band is not None and fuse:
         raise RuntimeError('render_image_training: band= together with the fused f_rest step -- the backward pass of a band holds that band\'s share of the '
                            'gradient only, and Adam applied to a partial gradient is not the optimizer\'s step; sum the shares over the bands and step then')
@@ -767,15 +847,21 @@ def render_image_training(gaussians: Gaussians, cam: PerspectiveCamera, c2w: np.
     # gradient -- a leaf of uninitialised memory receives the same .grad without a 12 MB fill and a 24 MB add per step
     viewspace_points = torch.empty_like(positions).requires_grad_(True)
     rasterizer = GaussianRasterizer(make_raster_settings(cam, c2w, gaussians.active_sh_degree, 1.0, positions.device))
-    if gaussians.baked:  # a baked model holds activated values
+    if filtered:  # the 3-D filter's activations are plain torch on top of the model's own: activated values into the kernels
+        image, radii, *aux = rasterizer(means3D=positions, means2D=viewspace_points, shs=gaussians.get_features_dc, shs_rest=gaussians.get_features_rest,
+                                        opacities=gaussians.get_opacities_with_3d_filter, scales=gaussians.get_scales_with_3d_filter, rotations=gaussians.get_rotations,
+                                        tile_rows=band, return_depth_alpha=depth_alpha, camera_grad=camera_grad, features=features, absgrad=absgrad,
+                                        antialiasing=antialiasing)
+    elif gaussians.baked:  # a baked model holds activated values
         image, radii, *aux = rasterizer(means3D=positions, means2D=viewspace_points, shs=gaussians.get_features_dc, shs_rest=gaussians.get_features_rest,
                                         opacities=gaussians.get_opacities, scales=gaussians.get_scales, rotations=gaussians.get_rotations, tile_rows=band,
-                                        return_depth_alpha=depth_alpha, camera_grad=camera_grad, features=features, absgrad=absgrad)
+                                        return_depth_alpha=depth_alpha, camera_grad=camera_grad, features=features, absgrad=absgrad, antialiasing=antialiasing)
     else:  # raw parameters straight into the kernels: no get_features concatenation, no separate exp / sigmoid / normalize passes (a25)
         rest_step = RestStep(gaussians) if fuse and not getattr(gaussians.optimizer, 'capturable', False) and not torch.cuda.is_current_stream_capturing() and torch.is_grad_enabled() and gaussians._features_rest.requires_grad and gaussians._features_rest.shape[1] > 0 and torch.is_tensor(c2w) else None
         image, radii, *aux = rasterizer(means3D=positions, means2D=viewspace_points, shs=gaussians._features_dc, shs_rest=gaussians._features_rest,
                                         opacities=gaussians._opacities, scales=gaussians._scales, rotations=gaussians._rotations, raw_parameters=True, rest_step=rest_step,
-                                        tile_rows=band, return_depth_alpha=depth_alpha, camera_grad=camera_grad, features=features, absgrad=absgrad)
+                                        tile_rows=band, return_depth_alpha=depth_alpha, camera_grad=camera_grad, features=features, absgrad=absgrad,
+                                        antialiasing=antialiasing)
     outputs = _TrainingOutputs({'rgb': image, 'viewspace_points': viewspace_points, 'radii': radii})
     if depth_alpha:
         outputs.update(_depth_alpha_outputs(aux[0], aux[1], True))
@@ -787,7 +873,7 @@ def render_image_training(gaussians: Gaussians, cam: PerspectiveCamera, c2w: np.
 
 
 def band_parallel_training_step(gaussians: Gaussians, cam: PerspectiveCamera, c2w, loss_fn, exchange=None, rank: int | None = None,
-                                world: int | None = None) -> dict[str, torch.Tensor]:
+                                world: int | None = None, antialiasing: bool = False) -> dict[str, torch.Tensor]:
     """The training render of ONE view split over the ranks as bands of tile rows, forward and backward, with the reference's one-view semantics:
 
         1. this rank renders its own band (parallel.tile_row_band of the frame's ceil(H / 16) tile rows);
@@ -800,12 +886,12 @@ def band_parallel_training_step(gaussians: Gaussians, cam: PerspectiveCamera, c2
     Afterwards every rank holds the single-GPU gradient and takes the single-GPU optimizer step: preprocess, depth sort, per-Gaussian backward and
     Adam are replicated, binning and the two blend kernels shrink with the band.  Returns the outputs of render_image_training with 'rgb' = the whole
     frame (detached), plus 'loss' and 'band'.  `exchange`: a parallel.UnionRowExchange(P, device) to reuse across steps of the same P.
-    The in-backward f_rest step (gaussians.fuse_rest_step) is refused: it would run on a partial gradient."""
+    The in-backward f_rest step (gaussians.fuse_rest_step) is refused: it would run on a partial gradient.  antialiasing: passed to render_image_training."""
     from . import parallel
     r, w = parallel.world_info()
     rank, world = (r if rank is None else int(rank)), (w if world is None else int(world))
     band = parallel.tile_row_band((cam.height + 15) // 16, rank, world)
-    out = render_image_training(gaussians, cam, c2w, band=band)
+    out = render_image_training(gaussians, cam, c2w, band=band, antialiasing=antialiasing)
     mask = out['band_mask']
     ex = exchange if exchange is not None else parallel.UnionRowExchange(mask.shape[0], mask.device)
     ex.begin(mask)          # the mask traffic runs beside the gather, the loss and the backward pass
@@ -845,8 +931,9 @@ class _TrainingOutputs(dict):
 @torch.no_grad()
 def render_image_inference(gaussians: Gaussians, cam: PerspectiveCamera, c2w: np.ndarray, scale_modifier: float = 1.0, to_chw: bool = False,
                            use_baked_covariance: bool = True, band: tuple[int, int] | None = None, depth_alpha: bool = False,
-                           features: torch.Tensor | None = None, _rasterizer_out: list | None = None):
-    """features: a (P, C) float32 tensor of the caller's; the outputs gain 'features', the map blended with the colour's weights (the rasterizer's `features`),
+                           features: torch.Tensor | None = None, _rasterizer_out: list | None = None, antialiasing: bool = False):
+    """antialiasing: anti-aliased splats (the rasterizer's `antialiasing`).  A model whose filter_3D is set is rendered with get_scales_with_3d_filter and
+    get_opacities_with_3d_filter (not from baked covariances, which do not hold the filter); a filter of another length than the model raises.  features: a (P, C) float32 tensor of the caller's; the outputs gain 'features', the map blended with the colour's weights (the rasterizer's `features`),
     (H, W, C) or (C, H, W) with to_chw.  depth_alpha: the outputs gain 'alpha' (1 - T of the blend) and 'depth' (accumulated view-space depth / (alpha + 1e-6)), (H, W, 1) or (1, H, W) with to_chw, as
     instant_ngp.render_image returns them.  band = (tile_row_begin, n_tile_rows): only that band of tile rows of the frame is rendered (zero elsewhere; parallel.gather_band_images composes the
     frame from the ranks' bands).  GaussianSplatting/Renderer.py:89-155 with the fused SH path (USE_FUSED_SH_CONVERSION = True, the shipped default); a baked model
@@ -855,16 +942,18 @@ def render_image_inference(gaussians: Gaussians, cam: PerspectiveCamera, c2w: np
     from .diff_gaussian_rasterization import GaussianRasterizer
     positions = gaussians.get_positions
     rasterizer = GaussianRasterizer(make_raster_settings(cam, c2w, gaussians.active_sh_degree, scale_modifier, positions.device))
-    covariances = gaussians.get_baked_covariances if (use_baked_covariance and gaussians.baked) else None
+    filtered = getattr(gaussians, 'filter_3D', None) is not None
+    covariances = gaussians.get_baked_covariances if (use_baked_covariance and gaussians.baked and not filtered) else None
     if covariances is not None and covariances.shape[0] != positions.shape[0]:
         covariances = None  # "Baked covariance requested but not available"
     if covariances is not None:
         image, _, *aux = rasterizer(means3D=positions, means2D=torch.empty_like(positions), shs=gaussians.get_features, opacities=gaussians.get_opacities,
-                                    cov3D_precomp=covariances, tile_rows=band, return_depth_alpha=depth_alpha, features=features)
+                                    cov3D_precomp=covariances, tile_rows=band, return_depth_alpha=depth_alpha, features=features, antialiasing=antialiasing)
     else:
         image, _, *aux = rasterizer(means3D=positions, means2D=torch.empty_like(positions), shs=gaussians.get_features,
-                                    opacities=gaussians.get_opacities, scales=gaussians.get_scales, rotations=gaussians.get_rotations, tile_rows=band,
-                                    return_depth_alpha=depth_alpha, features=features)
+                                    opacities=gaussians.get_opacities_with_3d_filter if filtered else gaussians.get_opacities,
+                                    scales=gaussians.get_scales_with_3d_filter if filtered else gaussians.get_scales, rotations=gaussians.get_rotations, tile_rows=band,
+                                    return_depth_alpha=depth_alpha, features=features, antialiasing=antialiasing)
     image.clamp_(0.0, 1.0)
     outputs = {'rgb': image if to_chw else image.permute(1, 2, 0)}
     if depth_alpha:
