@@ -61,7 +61,8 @@ enum {
  * nrc_ngp_set_encoder_ypair_levels / _ypair_view, nrc_ngp_ypair_view_bytes, nrc_ngp_build_ypair_view -- the y-pair view of the leading hashed levels, read
  * only by a call that was handed one; group 26, nrc_ngp_set_frame_density_encoder -- the single-pass frame's kernel pair (the workspace of
  * nrc_ngp_render_frame is what it was, the pictures are the same bits); group 27, nrc_gs_preprocess_antialias_band / nrc_gs_backward_antialias_band /
- * nrc_gs_filter3d -- anti-aliased splats and the 3-D smoothing filter: instances and a kernel of their own, no existing launch changes. */
+ * nrc_gs_filter3d -- anti-aliased splats and the 3-D smoothing filter: instances and a kernel of their own, no existing launch changes; group 28,
+ * nrc_bilagrid_* -- bilateral-grid colour correction (slice, total variation, their gradients), a translation unit of its own. */
 #define NRC_ABI_VERSION 22
 /* library identification; also used by the loader's symbol check */
 int nrc_abi_version(void);
@@ -1445,6 +1446,51 @@ int nrc_gs_backward_antialias_band(int32_t P, int32_t D, int32_t M, int32_t W, i
                     int32_t records_clear, int32_t tile_row_begin, int32_t n_tile_rows, const float* dL_ddepth_alpha, float* pose_partials,
                     float* dL_dcamera, float* dL_dmean2D_abs, nrc_stream_t stream);
 int nrc_gs_filter3d(const float* means3D, int64_t P, const float* views, int32_t V, float* filter_3D, void* workspace, nrc_stream_t stream);
+
+/* =====================================================================================================
+ * Group 28 -- bilateral-grid colour correction (csrc/bilateral_grid.hip): the learned per-image post-process of "Bilateral Guided Radiance Field Processing"
+ *            (Wang et al., SIGGRAPH 2024; gsplat: use_bilateral_grid).  Every training image owns a small 3-D grid of 3 x 4 colour transforms, sliced per pixel
+ *            by position and luminance and applied to the rendered image before the loss; a total-variation term on the grids is added.  Added under ABI
+ *            version 22 without a bump (additive, like groups 23-27).
+ *
+ *   grids (N, 12, L, Gh, Gw) f32, contiguous; channel c = 4 r + k is entry (r, k) of a 3 x 4 matrix.  The identity has channels 0, 5, 10 one, the rest zero.
+ *   For pixel (x, y) of an H x W image with colour p = (p0, p1, p2), sliced with grid n:
+ *            u = (x + 0.5) / W        v = (y + 0.5) / H        g = 0.299 p0 + 0.587 p1 + 0.114 p2
+ *            along each axis a, with coordinate t in {u, v, g} and extent n_a in {Gw, Gh, L}:
+ *                c_a = clamp(t, 0, 1) (n_a - 1);   i_a = min(floor(c_a), n_a - 2);   f_a = c_a - i_a        (n_a = 1: i_a = 0, f_a = 0, one vertex only)
+ *            A(r,k) = sum over the <= 8 corners of  w_z w_y w_x G[n, 4r+k, i_z+dz, i_y+dy, i_x+dx],   w = f or 1 - f
+ *            out_r  = A(r,0) p0 + A(r,1) p1 + A(r,2) p2 + A(r,3)
+ *   Gradients: to G[n]: w_z w_y w_x d_out_r (p_k or 1); every other grid gets exactly zero.  To p, the linear part: sum_r d_out_r A(r,k); through the guidance:
+ *            (0.299, 0.587, 0.114) (L - 1) sum_r d_out_r sum_k (dA(r,k)/dc_z) (p_k or 1), zero when g < 0 or g > 1; at g == 1 exactly (a white pixel) it takes the
+ *            last cell's slope, at g == 0 the first cell's.  u and v carry no gradient.  On interior inputs this is grid_sample(mode='bilinear',
+ *            align_corners=True, padding_mode='border') on the coordinates (2u - 1, 2v - 1, 2g - 1).
+ *   Total variation: TV(G) = (1/N) sum_{axis in z,y,x} sum (G[.., i+1, ..] - G[.., i, ..])^2 / count_axis, count_axis = 12 (n_axis - 1) (product of the other two
+ *            extents), the number of differences per grid along that axis; an axis of extent 1 contributes zero.
+ *
+ *   Pixels: element (y, x, channel ch) of rgb, out, d_out and d_rgb lies at (y W + x) pixel_stride + ch channel_stride floats -- (3, H, W) is (1, H W),
+ *            (H, W, 3) is (3, 1).  idx: the grid index n as a host integer, or, when idx_dev != NULL, an int32 on the device read by the kernels (a captured
+ *            iteration can change it; a device value outside [0, N) is clamped into it).
+ *   nrc_bilagrid_ws_floats   : floats of the workspace that nrc_bilagrid_slice_backward (with d_grids) and nrc_bilagrid_tv_forward need for these shapes
+ *            (H, W may be 0 for the TV term alone); the workspace is 16-byte aligned.
+ *   nrc_bilagrid_slice_forward : out from grids, rgb; affine (H, W, 12) f32, the sliced matrices, is written when non-NULL (16-byte aligned).  One launch.
+ *   nrc_bilagrid_slice_backward: d_rgb and / or d_grids (either may be NULL, not both; d_grids needs the workspace) from d_out.  d_grids (N, 12, L, Gh, Gw) is
+ *            written whole: slice n holds the gradient, every other slice zeros.  The grid gradient is summed in a fixed order (per wave, per workgroup, then
+ *            over the workgroups' partial windows in the workspace; no atomics): the same input gives the same bits on every call.  Two launches.
+ *   nrc_bilagrid_tv_forward  : tv[0] = TV(grids); double sums in a fixed order, two launches.
+ *   nrc_bilagrid_tv_backward : d_grids = upstream dTV/dG, the stencil (2 / (N count_axis)) (second difference) summed over the axes; upstream_dev: a device
+ *            scalar (NULL: 1).  One launch.
+ *   Nothing is read back and every size comes from the shapes: every call is capturable.  NRC_ERR_INVALID before any HIP call: a null pointer that is
+ *            required, N, L, Gh or Gw < 1 (or an extent above 4096), H or W < 0, idx outside [0, N) when given on the host, a stride < 1.  An empty image
+ *            (H == 0 or W == 0): NRC_OK; the forward launches nothing, the backward writes zeros into d_grids.
+ * ===================================================================================================== */
+int64_t nrc_bilagrid_ws_floats(int64_t N, int32_t L, int32_t Gh, int32_t Gw, int32_t H, int32_t W);
+int nrc_bilagrid_slice_forward(const float* grids, int64_t N, int32_t L, int32_t Gh, int32_t Gw, const float* rgb, int32_t H, int32_t W, int64_t pixel_stride,
+                               int64_t channel_stride, int64_t idx, const int32_t* idx_dev, float* out, float* affine, nrc_stream_t stream);
+int nrc_bilagrid_slice_backward(const float* grids, int64_t N, int32_t L, int32_t Gh, int32_t Gw, const float* rgb, const float* d_out, int32_t H, int32_t W,
+                                int64_t pixel_stride, int64_t channel_stride, int64_t idx, const int32_t* idx_dev, float* workspace, float* d_rgb,
+                                float* d_grids, nrc_stream_t stream);
+int nrc_bilagrid_tv_forward(const float* grids, int64_t N, int32_t L, int32_t Gh, int32_t Gw, float* workspace, float* tv, nrc_stream_t stream);
+int nrc_bilagrid_tv_backward(const float* grids, int64_t N, int32_t L, int32_t Gh, int32_t Gw, const float* upstream_dev, float* d_grids, nrc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -61,6 +61,10 @@ PER_FILE_FLAGS = {
     # the input gradient of the same block: the same matrix pipeline (no SLP vectoriser, as for nerf_net.hip); its f32 encoding backward is written in
     # explicit single-rounding operations, so the contraction setting has nothing to decide
     'nerf_input_grad.hip': ['-fno-slp-vectorize'],
+    # no FMA contraction: the written f32 sequence of the slice, its two gradients and the TV stencil is what the budget of tests/bilateral_grid_ref.py counts,
+    # rounding by rounding, and the host evaluates the kernels' own cell function to size the tile windows: both sides must round alike.  The kernels move
+    # 24 to 36 bytes per pixel and wait for them; a fused multiply-add would buy nothing
+    'bilateral_grid.hip': ['-ffp-contract=off'],
 }
 
 

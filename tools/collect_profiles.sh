@@ -37,6 +37,9 @@ prof() {
 # MODE=sparse_adam: group 24 (csrc/adam_rows.hip; no existing source changes) -- the bench command (all durations; no bench leg runs the masked step), one trace of
 # tools/bench_sparse_adam.py --profile (1 M Gaussians, ONE known mask: random 20 %) and three counter groups on the new launch, each a run of its own; then
 # tools/make_profile_summary.py ROUND adam_rows.hip (every other kernel's counters carried over).
+# MODE=bilagrid: group 28 (csrc/bilateral_grid.hip; no existing source changes) -- the bench command (all durations; no bench leg runs the colour correction), one
+# trace of tools/bench_bilateral_grid.py --profile (slice and TV, forward and backward, 1297 x 840, 200 grids) and three counter groups on the new launches, each a
+# run of its own; then tools/make_profile_summary.py ROUND bilateral_grid.hip (every other kernel's counters carried over).
 MODE=${1:-all}
 # the full bench command (bench.py --full --steps 20 --warmup 5, every leg): the per-kernel averages of the InstantNGP kernels must agree with the bench line
 [ "$MODE" != nerf_train ] && [ "$MODE" != nerf_input_grad ] && prof 900 $O/bench_stats.log --kernel-trace --stats --output-format csv -d $O/bench_stats -- python3 $R/bench.py --full --steps 20 --warmup 5
@@ -88,7 +91,14 @@ for set in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY S
   prof 300 $O/pmcgs_sparse_adam_$tag.log --pmc $set --kernel-trace --kernel-include-regex "k_adam_rows" --output-format csv -d $O/pmcgs_sparse_adam_$tag -- python3 $R/tools/bench_sparse_adam.py 21 --profile
 done
 fi
-if [ "$MODE" = nerf ] || [ "$MODE" = nerf_train ] || [ "$MODE" = nerf_rays ] || [ "$MODE" = nerf_input_grad ] || [ "$MODE" = gs_features ] || [ "$MODE" = gs_contrib ] || [ "$MODE" = sparse_adam ]; then
+if [ "$MODE" = bilagrid ]; then
+prof 300 $O/bilagrid_stats.log --kernel-trace --stats --output-format csv -d $O/bilagrid_stats -- python3 $R/tools/bench_bilateral_grid.py --profile
+for set in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_WAVE_CYCLES GRBM_GUI_ACTIVE"; do
+  tag=$(echo $set | tr ' ' '_' | cut -c1-32)
+  prof 300 $O/pmcgs_bilagrid_$tag.log --pmc $set --kernel-trace --kernel-include-regex "k_bilagrid" --output-format csv -d $O/pmcgs_bilagrid_$tag -- python3 $R/tools/bench_bilateral_grid.py --profile
+done
+fi
+if [ "$MODE" = nerf ] || [ "$MODE" = nerf_train ] || [ "$MODE" = nerf_rays ] || [ "$MODE" = nerf_input_grad ] || [ "$MODE" = gs_features ] || [ "$MODE" = gs_contrib ] || [ "$MODE" = sparse_adam ] || [ "$MODE" = bilagrid ]; then
 find $O -name "*.db" -delete; find $O -name "*_agent_info.csv" -delete; find $O -path "*_stats/*" -name "*kernel_trace.csv" -delete; du -sh $O; [ -f $O/bench_stats.log ] && tail -5 $O/bench_stats.log
 exit 0
 fi

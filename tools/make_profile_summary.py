@@ -72,6 +72,9 @@ if nistats:
 sastats = sorted(glob.glob(str(RAW / 'sparse_adam_stats' / '*' / '*kernel_stats.csv')), key=os.path.getmtime)   # tools/bench_sparse_adam.py --profile: the masked Adam launch, one known mask
 if sastats:
     shutil.copy(sastats[-1], OUT / f'{ROUND}_sparse_adam_kernel_stats.csv')
+bgstats = sorted(glob.glob(str(RAW / 'bilagrid_stats' / '*' / '*kernel_stats.csv')), key=os.path.getmtime)   # tools/bench_bilateral_grid.py --profile: slice and TV, forward and backward
+if bgstats:
+    shutil.copy(bgstats[-1], OUT / f'{ROUND}_bilateral_grid_kernel_stats.csv')
 # one accumulator per collection run: pmc_* = tools/bench_query.py (InstantNGP image pipeline), pmcgs_* = tools/bench_gs.py (3DGS frame),
 # pmctr_* = tools/bench_train.py (InstantNGP training iteration).  A kernel that appears in several of them (k_grid_encode runs in the image
 # pipeline with 8 Mi-slot launches and in training with 264 K samples) is reported from the run that is about it.
@@ -90,7 +93,7 @@ for k in names:
     for n, vals in src[k].items():
         acc[k][n] = vals
 keep = ('k_grid_encode', 'k_ngp_mlp', 'k_render', 'k_composite_image', 'k_preprocess', 'k_span_', 'k_item_', 'k_depth_keys', 'k_radix_', 'k_scan_tiles', 'k_march_wave',
-        'k_grid_bwd', 'k_nwie_', 'k_composite_train', 'k_gb_', 'k_train_', 'k_amp_', 'k_adam', 'k_nerf_', 'k_gs_contributions')
+        'k_grid_bwd', 'k_nwie_', 'k_composite_train', 'k_gb_', 'k_train_', 'k_amp_', 'k_adam', 'k_nerf_', 'k_gs_contributions', 'k_bilagrid')
 lines = [f'# rocprofv3 --pmc summary (MI355X, {ROUND})', '',
          'Collected by `tools/collect_profiles.sh` (one `--pmc` group per run, `--kernel-trace` only), averaged per kernel over all launches of',
          '`tools/bench_query.py` (InstantNGP 800x800 image pipeline), `tools/bench_gs.py` (3DGS, 1 M Gaussians, 1297x840) and `tools/bench_train.py`',
