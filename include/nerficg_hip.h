@@ -62,7 +62,9 @@ enum {
  * only by a call that was handed one; group 26, nrc_ngp_set_frame_density_encoder -- the single-pass frame's kernel pair (the workspace of
  * nrc_ngp_render_frame is what it was, the pictures are the same bits); group 27, nrc_gs_preprocess_antialias_band / nrc_gs_backward_antialias_band /
  * nrc_gs_filter3d -- anti-aliased splats and the 3-D smoothing filter: instances and a kernel of their own, no existing launch changes; group 28,
- * nrc_bilagrid_* -- bilateral-grid colour correction (slice, total variation, their gradients), a translation unit of its own. */
+ * nrc_bilagrid_* -- bilateral-grid colour correction (slice, total variation, their gradients), a translation unit of its own; group 29,
+ * nrc_ngp_density_frag_image -- the density net's weights as ready-made MFMA fragments, the 6 KB image that nrc_ngp_render_frame now writes into a
+ * new trailing part of its workspace (nrc_ngp_render_frame_ws_bytes grows by 6 144 bytes; signatures and pictures are what they were). */
 #define NRC_ABI_VERSION 22
 /* library identification; also used by the loader's symbol check */
 int nrc_abi_version(void);
@@ -734,11 +736,20 @@ int nrc_ngp_composite_image(const void* packed_f16, const float* ts, const int32
  *      the workspace's feature part.  Chunks of more than 2^24 rows run the 64-byte pair whatever is set.
  *  -1: the library's default (a compile-time constant).
  * The pictures are the same bit for bit: the same MFMAs on the same operands, only in another kernel.  A setting of the CALLING HOST THREAD, read by
- * nrc_ngp_render_frame alone: nrc_ngp_render_frame_ws_bytes is what it was (64 B per slot), so a workspace serves either pair
+ * nrc_ngp_render_frame alone: nrc_ngp_render_frame_ws_bytes does not depend on it (64 B per slot), so a workspace serves either pair
  * (InstantNGPRenderer sets the mode from FRAME_DENSITY_ENCODER in front of every frame).  No other entry point reads it: nrc_ngp_encode_samples /
- * nrc_ngp_mlp_samples, the layered and the fixed-capacity frames and all training paths keep the 64-byte features. */
+ * nrc_ngp_mlp_samples, the layered and the fixed-capacity frames and all training paths keep the 64-byte features.
+ * Group 29 -- the density net's fragment image.  The workspace ends with 6 144 bytes (rounded up to 256) that EVERY call of nrc_ngp_render_frame
+ * rewrites from density_weights_f16 (one extra workgroup of its first launch; nothing is cached from call to call, so weights that changed between
+ * two frames are followed) and that the density-encoder pair's encoder copies into LDS instead of building the fragments from the row-major weights
+ * in each of its workgroups.  Image slot f = 0 .. 5, lane l = 0 .. 63, 16-byte vector f * 64 + l, with W = density_weights_f16 (row-major: 64 x 32
+ * first layer, then the 16 x 64 head):
+ *   f < 4:   elements e = 0 .. 7 = W[(32 (f >> 1) + (l & 31)) * 32 + 16 (f & 1) + 8 (l >> 5) + e]
+ *   f = 4, 5: with m = l & 15, kg = l >> 4, ks = f - 4:  element e = W[2048 + 64 m + 32 ks + (e & 3) + 8 (2 (kg & 1) + (e >> 2)) + 4 (kg >> 1)]
+ * -- every one of the 3 072 weights exactly once.  nrc_ngp_density_frag_image runs the same builder on its own: image_out receives the 6 144 bytes. */
 int nrc_ngp_set_frame_density_encoder(int32_t mode);
 int64_t nrc_ngp_render_frame_ws_bytes(int64_t n_rows, int64_t n_ray_tiles, int32_t max_samples, int64_t row_budget);
+int nrc_ngp_density_frag_image(const void* density_weights_f16, void* image_out, nrc_stream_t stream);
 int nrc_ngp_render_frame(const float* ts_arena, int32_t* row_tile, const float* ray_od, int64_t n_rows, int64_t n_ray_tiles,
                          const float* xyz_min3, const float* xyz_size3, const void* density_weights_f16, const void* color_weights_f16,
                          const void* table_f16, int32_t n_levels, int32_t log2_hashmap_size, int32_t base_resolution, float per_level_scale,

@@ -334,7 +334,7 @@ __device__ __forceinline__ void fetch_dir(const QueryIn& in, int64_t i, float& d
 // channels (measured: 0.262 ms vs 0.22 ms per 2 Mi samples).  One lane per sample, all 16 levels.
 //
 // DENS (the single-pass frame's density-encoder form, SRC_TILED): the wave keeps the four groups of its 64 samples in registers and runs the DENSITY
-// net on them itself (mlp_density_half, weights Wd staged in LDS: 6 KB per workgroup) as two 32-sample MFMA tiles, tile v = the samples on lanes
+// net on them itself (mlp_density_half, its six A fragments copied from the frame's fragment image wimg into LDS: 6 KB per workgroup) as two 32-sample MFMA tiles, tile v = the samples on lanes
 // 32 v .. 32 v + 31 -- the columns of an MFMA are independent, so which sample sits in which column changes no bit.  What it stores is X1, the 16 fp16
 // density features, 32 B per sample instead of 64: the 16-byte vector
 //   feat[(j >> 5) * 64 + 32 hh + (j & 31)]   holds density features 8 hh .. 8 hh + 7 of slot j,
@@ -346,6 +346,17 @@ enum { MLP_F_D0 = 0, MLP_F_DO = 4, MLP_F_C0 = 8, MLP_F_C1 = 12, MLP_F_CO = 20, M
 __device__ __forceinline__ void mlp_stage_weights(h8 (*wlds)[64], const __half* __restrict__ Wd, const __half* __restrict__ Wc, int n_frag = MLP_N_FRAG);
 template <int NT>
 __device__ __forceinline__ void mlp_density_half(const h8 (*wlds)[64], const h8 (&B)[NT][2], h8 (&X1)[NT]);
+// The density net's six A fragments as a 6 KB IMAGE in global memory: image[f * 64 + lane] is the h8 that mlp_stage_weights puts into wlds[f][lane] for
+// f < MLP_F_DO + 2 -- every one of the 3 072 density weights once.  Built by ONE workgroup of 256 threads per frame (the workgroup behind the last ray
+// tile's of k_ray_sh) from the row-major weights; every workgroup of the density-encoder form then copies it into its LDS with coalesced 16-byte loads
+// (48 lines) instead of building the fragments itself (about 320 line lookups, the head fragment alone eight 2-byte loads per lane: LABBOOK R31.4, R34).
+enum { MLP_DENS_IMAGE_VECS = (MLP_F_DO + 2) * 64 };
+__device__ __forceinline__ void density_frag_image_build(const __half* __restrict__ Wd, h8* __restrict__ image) {
+    const int lane = threadIdx.x & 63;
+    for (int f = threadIdx.x >> 6; f < MLP_F_DO + 2; f += 4)
+        image[f * 64 + lane] = f < MLP_F_DO ? load_w_frag<false>(Wd, 32, 64, f >> 1, f & 1, lane & 31, lane >> 5)
+                                            : load_w_head_frag(Wd + 64 * 32, 64, 16, f - MLP_F_DO, lane);
+}
 #ifndef NRC_ENC_DENS_WAVES
 #define NRC_ENC_DENS_WAVES 7   // waves per SIMD the density-encoder form's register budget is set for (workgroups per CU: a workgroup is one wave per SIMD).
                                // 67 VGPRs, no scratch; without a budget the chain's accumulators go to AGPRs (68 + 32: 4 waves).  Measured, frame ms: 8 waves (64 VGPRs,
@@ -355,10 +366,14 @@ template <int SRC, bool DENS = false>
 __global__ void __launch_bounds__(256, DENS ? NRC_ENC_DENS_WAVES : 0) k_grid_encode(QueryIn in, int64_t base, int64_t n, const __half2* __restrict__ table, GridCfg g,
                                                          uint4* __restrict__ feat, int narrow_levels, int lvl_range, int lane_shape = 0, int xcd_run = 0,
                                                          BlockView bv = BlockView{}, VertexView vv = VertexView{}, YPairView yv = YPairView{},
-                                                         const __half* __restrict__ Wd = nullptr) {
+                                                         const h8* __restrict__ wimg = nullptr) {
     static_assert(!DENS || SRC == SRC_TILED, "the density-encoder form belongs to the tiled layout");
     extern __shared__ h8 enc_wlds[][64];   // DENS: (MLP_F_DO + 2) * 1 KB of dynamic LDS, none otherwise
-    if constexpr (DENS) mlp_stage_weights(enc_wlds, Wd, nullptr, MLP_F_DO + 2);   // (read behind the barrier in front of the chain, not in front of the gathers)
+    if constexpr (DENS) {   // the frame's fragment image (density_frag_image_build), 384 vectors over 256 threads; read behind the barrier in front of the chain.
+        // Measured against it (LABBOOK R34): the barrier directly behind this copy, frame -0.075 ms, inside three spreads of this placement's own runs; no LDS,
+        // every wave loading its fragments from the image at the point of use, frame +0.09 ms and 69 VGPRs
+        for (int i = threadIdx.x; i < MLP_DENS_IMAGE_VECS; i += 256) (&enc_wlds[0][0])[i] = wimg[i];
+    }
     int64_t bid = blockIdx.x;
     if constexpr (SRC == SRC_TILED) {
         // workgroups are dealt round-robin over the 8 XCDs; each XCD takes a CONTIGUOUS eighth of a range of slots instead of every eighth
@@ -603,7 +618,9 @@ __global__ void __launch_bounds__(256) k_build_ypair_view(const uint32_t* __rest
 // tile t (what nrc_ngp_render_write does next to its copy; here there is no copy and no second launch)
 __global__ void __launch_bounds__(256) k_ray_sh(const float* __restrict__ ray_od, int64_t n_ray_tiles, h8* __restrict__ ray_sh,
                                                 const int32_t* __restrict__ rows_tile_off = nullptr, int32_t* __restrict__ row_tile_out = nullptr,
-                                                int64_t n_rows = 0) {
+                                                int64_t n_rows = 0, const __half* __restrict__ Wd = nullptr, h8* __restrict__ frag_image = nullptr) {
+    // frag_image (the single-pass frame): the launch has ONE workgroup more than the ray tiles need, and that one writes the density net's fragment image
+    if (frag_image && blockIdx.x == gridDim.x - 1) { density_frag_image_build(Wd, frag_image); return; }
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n_ray_tiles * 64) return;
     const int64_t tile = i >> 6;
@@ -618,6 +635,8 @@ __global__ void __launch_bounds__(256) k_ray_sh(const float* __restrict__ ray_od
     ray_sh[(tile * 2) * 64 + lane] = lo;
     ray_sh[(tile * 2 + 1) * 64 + lane] = hi;
 }
+// the image builder on its own (nrc_ngp_density_frag_image: what the tests read back)
+__global__ void __launch_bounds__(256) k_density_frag_image(const __half* __restrict__ Wd, h8* __restrict__ image) { density_frag_image_build(Wd, image); }
 
 __device__ __forceinline__ float fast_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
 
@@ -1332,11 +1351,12 @@ static YPairView ypair_view_of(const void* view, const GridCfg& g, int n_levels)
     if (!yv.ptr || yv.levels <= 0) { yv.ptr = nullptr; yv.levels = 0; }
     return yv;
 }
-// density_weights: the density-encoder form (k_grid_encode<SRC_TILED, true>): `feat` receives 32 B per slot, the density net's output
+// density_frag_image: the density-encoder form (k_grid_encode<SRC_TILED, true>): `feat` receives 32 B per slot, the density net's output; the image is
+// the one density_frag_image_build wrote earlier on the same stream
 template <int SRC>
 static void launch_encode(const QueryIn& in, int64_t base, int64_t n, const void* table, const GridCfg& g, uint4* feat, hipStream_t s,
                           const BlockView& bv = BlockView{}, const VertexView& vv = VertexView{}, const YPairView& yv = YPairView{},
-                          const void* density_weights = nullptr) {
+                          const h8* density_frag_image = nullptr) {
     // levels whose cells are larger than a wave's footprint: narrow gathers (see grid_level_features_narrow)
     int narrow = 0;
     while (narrow < NRC_MAX_LEVELS && !g.hashed[narrow] && g.size[narrow] > 8) narrow++;
@@ -1363,10 +1383,10 @@ static void launch_encode(const QueryIn& in, int64_t base, int64_t n, const void
     const int lane_shape = (3 << 4) | 1;
     const int lanes = (SRC == SRC_TILED && (base & 1023) == 0) ? (g_enc_shape_override ? g_enc_shape_override : lane_shape) : 0;
     if constexpr (SRC == SRC_TILED) {
-        if (density_weights) {
+        if (density_frag_image) {
             hipLaunchKernelGGL((k_grid_encode<SRC_TILED, true>), dim3((unsigned)(lanes ? 4 * nrc_cdiv(n, 1024) : nrc_cdiv(n, 256))), dim3(256),
-                               (MLP_F_DO + 2) * 64 * sizeof(h8), s, in, base, n, (const __half2*)table, g, feat, narrow, lvl_range, lanes,
-                               g_enc_xcd_run_override ? g_enc_xcd_run_override : NRC_ENC_XCD_RUN, bv, vv, yv, (const __half*)density_weights);
+                               MLP_DENS_IMAGE_VECS * sizeof(h8), s, in, base, n, (const __half2*)table, g, feat, narrow, lvl_range, lanes,
+                               g_enc_xcd_run_override ? g_enc_xcd_run_override : NRC_ENC_XCD_RUN, bv, vv, yv, density_frag_image);
             return;
         }
     }
@@ -1759,7 +1779,8 @@ int nrc_ngp_render_layers(const float* ts, int32_t* row_tile, const float* ray_o
     return NRC_OK;
 }
 
-/* workspace of the single-pass frame: [features of the largest chunk][ray_sh][order: n_ray_tiles i32][chunk table: 4 i32 per chunk][queue: 1 i32 per chunk] */
+/* workspace of the single-pass frame: [features of the largest chunk][ray_sh][order: n_ray_tiles i32][chunk table: 4 i32 per chunk][queue: 1 i32 per chunk]
+   [the density net's fragment image: 6 KB, written by every frame (k_ray_sh's last workgroup) and read by the density-encoder form of k_grid_encode] */
 #ifndef NRC_FRAME_ROW_BUDGET
 #define NRC_FRAME_ROW_BUDGET (int64_t(1) << 21)   // rows of 64 slots per encode / MLP round of the single-pass frame (8 GiB of features; an 800x800 bench
                                                   // frame has ~1.2 Mi rows: ONE round).  Larger frames are cut into chunks of whole ray tiles.
@@ -1792,7 +1813,8 @@ int64_t nrc_ngp_render_frame_ws_bytes(int64_t n_rows, int64_t n_ray_tiles, int32
     const int64_t chunks = frame_chunks(n_rows, budget, max_samples);
     const int64_t feat_rows = n_rows < budget ? n_rows : budget;
     // (the feature part is sized for the 64-byte pair whichever pair is set: a workspace sized once serves both, the density-encoder pair uses its first half)
-    return round256((feat_rows > 0 ? feat_rows : 1) * 64 * 64) + round256(n_ray_tiles * 2048) + round256(n_ray_tiles * 4) + round256(chunks * 20);
+    return round256((feat_rows > 0 ? feat_rows : 1) * 64 * 64) + round256(n_ray_tiles * 2048) + round256(n_ray_tiles * 4) + round256(chunks * 20) +
+           round256(MLP_DENS_IMAGE_VECS * sizeof(h8));   // (the fragment image, whichever pair is set)
 }
 
 int nrc_ngp_render_frame(const float* ts_arena, int32_t* row_tile, const float* ray_od, int64_t n_rows, int64_t n_ray_tiles, const float* xyz_min3,
@@ -1827,6 +1849,8 @@ int nrc_ngp_render_frame(const float* ts_arena, int32_t* row_tile, const float* 
     wsp += round256(n_ray_tiles * 4);
     int32_t* chunk_tab = (int32_t*)wsp;
     int32_t* queue = chunk_tab + 4 * chunks;
+    wsp += round256(chunks * 20);
+    h8* wimg = (h8*)wsp;   // the density net's fragment image, rebuilt by every frame: weights that changed since the last one cannot go stale
     QueryIn in = {};
     in.ts = ts_arena; in.row_tile = row_tile; in.ray_od = ray_od; in.tile_off = tile_off; in.arena_rows = max_samples;
     for (int k = 0; k < 3; k++) { in.mn[k] = xyz_min3[k]; in.sz[k] = xyz_size3[k]; }
@@ -1844,8 +1868,9 @@ int nrc_ngp_render_frame(const float* ts_arena, int32_t* row_tile, const float* 
     const VertexView vv = vertex_view_of(vview, g, n_levels);
     const YPairView yv = ypair_view_of(yview, g, n_levels);
     NRC_STAGE(s, nullptr);
-    // SH of every ray + the ray tile of every row (for the encoder)
-    hipLaunchKernelGGL(k_ray_sh, dim3((unsigned)nrc_cdiv(n_ray_tiles * 64, 256)), dim3(256), 0, s, ray_od, n_ray_tiles, ray_sh, tile_off, row_tile, n_rows);
+    // SH of every ray + the ray tile of every row (for the encoder) + one workgroup more: the density net's fragment image
+    hipLaunchKernelGGL(k_ray_sh, dim3((unsigned)nrc_cdiv(n_ray_tiles * 64, 256) + 1u), dim3(256), 0, s, ray_od, n_ray_tiles, ray_sh, tile_off, row_tile, n_rows,
+                       (const __half*)density_weights_f16, wimg);
     NRC_STAGE(s, "k_ray_sh");
     hipLaunchKernelGGL(k_tile_chunks, dim3((unsigned)chunks), dim3(1024), 0, s, tile_off, n_ray_tiles, chunks > 1 ? budget - max_samples : n_rows + 1,
                        chunk_tab, order, queue);
@@ -1853,7 +1878,7 @@ int nrc_ngp_render_frame(const float* ts_arena, int32_t* row_tile, const float* 
     for (int64_t c = 0; c < chunks; c++) {
         if (n_rows > 0) {
             in.chunk_rows = chunk_tab + 4 * c + 2;
-            launch_encode<SRC_TILED>(in, 0, feat_rows * 64, table_f16, g, feat, s, bv, vv, yv, dens ? density_weights_f16 : nullptr);
+            launch_encode<SRC_TILED>(in, 0, feat_rows * 64, table_f16, g, feat, s, bv, vv, yv, dens ? wimg : nullptr);
             NRC_STAGE(s, "k_grid_encode");
         }
         if (dens)
@@ -1864,6 +1889,15 @@ int nrc_ngp_render_frame(const float* ts_arena, int32_t* row_tile, const float* 
                                (const __half*)color_weights_f16, ts_arena, (int)max_samples, ray_cnt, tile_off, order, chunk_tab + 4 * c, queue + c, ic, rgb, alpha, depth);
         NRC_STAGE(s, "k_ngp_mlp");   // (k_ngp_mlp_composite: the stage keeps the MLP kernel's name, where the in-frame ruler looks for it)
     }
+    NRC_LAUNCH_CHECK();
+    return NRC_OK;
+}
+
+/* group 29: the fragment image of nrc_ngp_render_frame's workspace on its own (6 144 bytes at image_out): the builder the frame runs, one workgroup */
+int nrc_ngp_density_frag_image(const void* density_weights_f16, void* image_out, nrc_stream_t stream) {
+    NRC_ENTER();
+    if (!density_weights_f16 || !image_out) return NRC_ERR_INVALID;
+    hipLaunchKernelGGL(k_density_frag_image, dim3(1), dim3(256), 0, (hipStream_t)stream, (const __half*)density_weights_f16, (h8*)image_out);
     NRC_LAUNCH_CHECK();
     return NRC_OK;
 }
