@@ -64,7 +64,10 @@ enum {
  * nrc_gs_filter3d -- anti-aliased splats and the 3-D smoothing filter: instances and a kernel of their own, no existing launch changes; group 28,
  * nrc_bilagrid_* -- bilateral-grid colour correction (slice, total variation, their gradients), a translation unit of its own; group 29,
  * nrc_ngp_density_frag_image -- the density net's weights as ready-made MFMA fragments, the 6 KB image that nrc_ngp_render_frame now writes into a
- * new trailing part of its workspace (nrc_ngp_render_frame_ws_bytes grows by 6 144 bytes; signatures and pictures are what they were). */
+ * new trailing part of its workspace (nrc_ngp_render_frame_ws_bytes grows by 6 144 bytes; signatures and pictures are what they were); group 30,
+ * nrc_ngp_set_frame_full_encoder / nrc_ngp_colour_frag_image -- the single-pass frame's third form (both nets inside the encoder, 8-byte records, one
+ * compositor launch) and the colour net's 14 KB fragment image, which the workspace now holds directly in front of the density image
+ * (nrc_ngp_render_frame_ws_bytes grows by 14 336 bytes; signatures and pictures are what they were). */
 #define NRC_ABI_VERSION 22
 /* library identification; also used by the loader's symbol check */
 int nrc_abi_version(void);
@@ -746,8 +749,25 @@ int nrc_ngp_composite_image(const void* packed_f16, const float* ts, const int32
  * first layer, then the 16 x 64 head):
  *   f < 4:   elements e = 0 .. 7 = W[(32 (f >> 1) + (l & 31)) * 32 + 16 (f & 1) + 8 (l >> 5) + e]
  *   f = 4, 5: with m = l & 15, kg = l >> 4, ks = f - 4:  element e = W[2048 + 64 m + 32 ks + (e & 3) + 8 (2 (kg & 1) + (e >> 2)) + 4 (kg >> 1)]
- * -- every one of the 3 072 weights exactly once.  nrc_ngp_density_frag_image runs the same builder on its own: image_out receives the 6 144 bytes. */
+ * -- every one of the 3 072 weights exactly once.  nrc_ngp_density_frag_image runs the same builder on its own: image_out receives the 6 144 bytes.
+ * Group 30 -- the full-encoder form, nrc_ngp_set_frame_full_encoder(mode): 1 = on, 0 = off, -1 = the library's default (a compile-time constant, 1).  A
+ * setting of the CALLING HOST THREAD, read by nrc_ngp_render_frame alone, and only where the density-encoder pair would run (mode 1 of group 26 and a
+ * chunk of at most 2^24 rows): with group 26 at 0 the frame is the 64-byte pair whatever is set here, with group 26 at 1 and this switch at 0 it is the
+ * 32-byte pair.  Where it is on and n_rows <= 8 x (rows of the largest chunk) and n_rows < 2^25, the encoder runs the density net AND the colour net on
+ * the samples it gathered for and stores the 8-byte record (h0, r, g, b) in fp16 of nrc_ngp_mlp_samples at the slot's ABSOLUTE place, record s of the
+ * workspace's feature part = slot s of the frame (a hole's record and the records behind n_rows * 64 are not written); ONE launch of the kernel of
+ * nrc_ngp_composite_image (arena_rows = max_samples) then composites every ray tile.  No MLP-composite kernel and no chunk table run in this form; larger
+ * frames keep the 32-byte pair.  Same pictures, bit for bit; the workspace size does not depend on the setting.
+ * The colour net's fragment image: 14 336 bytes directly in FRONT of the density image, rewritten by every call of nrc_ngp_render_frame (the same extra
+ * workgroup) from color_weights_f16 = W (row-major: 64 x 32 first layer, 64 x 64 second layer, 16 x 64 head).  Image slot f = 0 .. 13, lane l:
+ *   f < 4 (first layer, m-tile f >> 1, k-step f & 1):  element e = W[(32 (f >> 1) + (l & 31)) * 32 + 16 (f & 1) + 8 (l >> 5) + e]
+ *   4 <= f < 12 (second layer, g = f - 4, m-tile g >> 2, k-step g & 3, accumulator order):
+ *            element e = W[2048 + (32 (g >> 2) + (l & 31)) * 64 + 16 (g & 3) + 8 (e >> 2) + 4 (l >> 5) + (e & 3)]
+ *   f = 12, 13 (head, ks = f - 12, m = l & 15, kg = l >> 4):  element e = W[6144 + 64 m + 32 ks + (e & 3) + 8 (2 (kg & 1) + (e >> 2)) + 4 (kg >> 1)]
+ * -- every one of the 7 168 weights exactly once.  nrc_ngp_colour_frag_image runs the same builder on its own: image_out receives the 14 336 bytes. */
 int nrc_ngp_set_frame_density_encoder(int32_t mode);
+int nrc_ngp_set_frame_full_encoder(int32_t mode);
+int nrc_ngp_colour_frag_image(const void* color_weights_f16, void* image_out, nrc_stream_t stream);
 int64_t nrc_ngp_render_frame_ws_bytes(int64_t n_rows, int64_t n_ray_tiles, int32_t max_samples, int64_t row_budget);
 int nrc_ngp_density_frag_image(const void* density_weights_f16, void* image_out, nrc_stream_t stream);
 int nrc_ngp_render_frame(const float* ts_arena, int32_t* row_tile, const float* ray_od, int64_t n_rows, int64_t n_ray_tiles,

@@ -266,8 +266,9 @@ __global__ void __launch_bounds__(256) k_distortion_bw(const float* __restrict__
 // reference's order, with the inference early-out (volumerendering.cu:205-249: a ray dies after compositing the sample
 // that brings T <= threshold) and the finalisation of render_rays_inference (Renderer.py:133-138).  sigma = exp(h0)
 // (TruncExp), dt re-derived from t with the test kernel's step rule (raymarching.cu:370).  The step and the finalisation live in
-// ngp_image_step.h, shared with k_composite_layers and k_ngp_mlp_composite (the single-pass frame composites inside its MLP kernel; this
-// kernel serves the pipelined, fixed-capacity and compact-row frames).
+// ngp_image_step.h, shared with k_composite_layers and k_ngp_mlp_composite.  This kernel serves the single-pass frame's full-encoder form (the
+// default: one launch over the 8-byte records the encoder stored, t from the count pass's arena; its two kernel pairs composite inside
+// k_ngp_mlp_composite) and the pipelined, fixed-capacity and compact-row frames.
 __global__ void __launch_bounds__(256) k_composite_image(const __half* __restrict__ packed, const float* __restrict__ ts,
                                                          const int32_t* __restrict__ ray_cnt, const int32_t* __restrict__ tile_off,
                                                          int width, int height, int tiles_x, int64_t tile_begin, int64_t n_tiles,
@@ -651,6 +652,19 @@ void nrc_launch_composite_layers(const void* packed, const float* ts, const int3
                        next_k, tile_alive, rgb, alpha, depth, skipped_rows, arena_rows);
 }
 
+// the one launch of k_composite_image: nrc_ngp_composite_image below and the full-encoder form of nrc_ngp_render_frame (ngp_net.hip) both come through here
+void nrc_launch_composite_image(const void* packed_f16, const float* ts, const int32_t* ray_cnt, const int32_t* tile_off, int32_t width, int32_t height,
+                                int64_t tile_begin, int64_t n_tiles, int32_t cascades, float exp_step_factor, int32_t grid_size, int32_t max_samples,
+                                float T_threshold, const float* bg3_host, float* rgb, float* alpha, float* depth, int64_t row_capacity, int32_t arena_rows,
+                                hipStream_t stream) {
+    const int tiles_x = (width + NRC_TILE_W - 1) / NRC_TILE_W;
+    // calc_dt of the test kernel (raymarching.cu:11-13 with `cascades` in place of `scale`, :370)
+    const float dt_min = 1.73205080757f / max_samples, dt_max = 1.73205080757f * 2 * (float)cascades / grid_size;
+    hipLaunchKernelGGL(k_composite_image, dim3(nrc_cdiv(n_tiles, 4)), dim3(256), 0, stream, (const __half*)packed_f16, ts, ray_cnt,
+                       tile_off, (int)width, (int)height, tiles_x, tile_begin, n_tiles, exp_step_factor, dt_min, dt_max, T_threshold,
+                       bg3_host[0], bg3_host[1], bg3_host[2], rgb, alpha, depth, row_capacity > 0 ? row_capacity : INT64_MAX, (int)arena_rows);
+}
+
 extern "C" {
 
 int nrc_raymarching_train_bw(const float* dL_dxyzs, const float* dL_ddirs, const float* ts, const int64_t* rays_a, int64_t n_rays, int64_t n_samples,
@@ -840,12 +854,8 @@ int nrc_ngp_composite_image(const void* packed_f16, const float* ts, const int32
     if (n_tiles < 0 || tile_begin < 0 || width < 1 || height < 1 || !bg3_host || grid_size < 1 || max_samples < 1 || row_capacity < 0 || arena_rows < 0) return NRC_ERR_INVALID;
     if (n_tiles == 0) return NRC_OK;
     if (!ray_cnt || !tile_off || !rgb || !alpha || !depth) return NRC_ERR_INVALID;
-    const int tiles_x = (width + NRC_TILE_W - 1) / NRC_TILE_W;
-    // calc_dt of the test kernel (raymarching.cu:11-13 with `cascades` in place of `scale`, :370)
-    const float dt_min = 1.73205080757f / max_samples, dt_max = 1.73205080757f * 2 * (float)cascades / grid_size;
-    hipLaunchKernelGGL(k_composite_image, dim3(nrc_cdiv(n_tiles, 4)), dim3(256), 0, (hipStream_t)stream, (const __half*)packed_f16, ts, ray_cnt,
-                       tile_off, (int)width, (int)height, tiles_x, tile_begin, n_tiles, exp_step_factor, dt_min, dt_max, T_threshold,
-                       bg3_host[0], bg3_host[1], bg3_host[2], rgb, alpha, depth, row_capacity > 0 ? row_capacity : INT64_MAX, (int)arena_rows);
+    nrc_launch_composite_image(packed_f16, ts, ray_cnt, tile_off, width, height, tile_begin, n_tiles, cascades, exp_step_factor, grid_size, max_samples,
+                               T_threshold, bg3_host, rgb, alpha, depth, row_capacity, arena_rows, (hipStream_t)stream);
     NRC_LAUNCH_CHECK();
     return NRC_OK;
 }

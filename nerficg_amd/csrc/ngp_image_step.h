@@ -47,3 +47,10 @@ __device__ __forceinline__ void nrc_composite_finish(const NrcRayAcc& s, float b
     alpha_out[n] = al;
     depth_out[n] = Tr < 1.0f ? s.d / al : 0.0f;
 }
+
+// host side: the launch of k_composite_image (ngp_composite.hip), shared by nrc_ngp_composite_image and the full-encoder form of nrc_ngp_render_frame.
+// ts: compact rows, or with arena_rows > 0 the count pass's arena; row_capacity 0 = no bound.  The caller checks its arguments and the launch status.
+void nrc_launch_composite_image(const void* packed_f16, const float* ts, const int32_t* ray_cnt, const int32_t* tile_off, int32_t width, int32_t height,
+                                int64_t tile_begin, int64_t n_tiles, int32_t cascades, float exp_step_factor, int32_t grid_size, int32_t max_samples,
+                                float T_threshold, const float* bg3_host, float* rgb, float* alpha, float* depth, int64_t row_capacity, int32_t arena_rows,
+                                hipStream_t stream);

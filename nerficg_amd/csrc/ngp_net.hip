@@ -288,7 +288,7 @@ __device__ __forceinline__ float ray_point(float o, float t, float d, float mn) 
 }
 // 1: a sample; 0: a hole of the tiled layout (no sample in this slot); -1: a row of a finished tile (slab order): nothing of it is read or written
 template <int SRC, bool UNIFORM_ROW = true>
-__device__ __forceinline__ int fetch_pos(const QueryIn& in, int64_t i, float& px, float& py, float& pz) {
+__device__ __forceinline__ int fetch_pos(const QueryIn& in, int64_t i, float& px, float& py, float& pz, int32_t* rt_out = nullptr) {
     if constexpr (SRC == SRC_ARRAYS) {
         px = in.xyz01[3 * i]; py = in.xyz01[3 * i + 1]; pz = in.xyz01[3 * i + 2];
         if (in.normalise) {
@@ -301,6 +301,7 @@ __device__ __forceinline__ int fetch_pos(const QueryIn& in, int64_t i, float& px
         // one wave = one row of the tiled layout: the row's ray tile is wave-uniform and comes through the scalar cache (no vector round trip in
         // front of the six ray loads that depend on it)
         const int32_t rt = UNIFORM_ROW ? in.row_tile[__builtin_amdgcn_readfirstlane((int)(i >> 6))] : in.row_tile[i >> 6];
+        if (rt_out) *rt_out = rt;   // (the full-encoder form addresses its ray's SH fragment with it: no second load of row_tile)
         if (rt < 0) { px = py = pz = 0.f; return -1; }
         const float t = in.ts[ts_slot(in, i, rt)];
         if (t < 0.f) { px = py = pz = 0.f; return 0; }
@@ -357,22 +358,51 @@ __device__ __forceinline__ void density_frag_image_build(const __half* __restric
         image[f * 64 + lane] = f < MLP_F_DO ? load_w_frag<false>(Wd, 32, 64, f >> 1, f & 1, lane & 31, lane >> 5)
                                             : load_w_head_frag(Wd + 64 * 32, 64, 16, f - MLP_F_DO, lane);
 }
+// The colour net's fourteen A fragments as a 14 KB image: image[(f - MLP_F_C0) * 64 + lane] is the h8 that mlp_stage_weights puts into wlds[f][lane] for
+// MLP_F_C0 <= f < MLP_F_CO + 2 -- C0 x 4 (natural order), C1 x 8 (ACC order), CO x 2 (head): every one of the 7 168 colour weights the chain reads, once
+// (the head's rows 3 .. 15 included: its fragment holds all sixteen).  Built by the same extra workgroup of k_ray_sh, every frame; the full-encoder form
+// of k_grid_encode copies it into LDS slots MLP_F_C0 .. MLP_F_CO + 1.  In the frame's workspace it lies directly in front of the density image.
+enum { MLP_COL_IMAGE_VECS = (MLP_F_CO + 2 - MLP_F_C0) * 64 };
+__device__ __forceinline__ void colour_frag_image_build(const __half* __restrict__ Wc, h8* __restrict__ image) {
+    const int lane = threadIdx.x & 63, r = lane & 31, hh = lane >> 5;
+    for (int f = MLP_F_C0 + (threadIdx.x >> 6); f < MLP_F_CO + 2; f += 4) {
+        h8 v;
+        if (f < MLP_F_C1) v = load_w_frag<false>(Wc, 32, 64, (f - MLP_F_C0) >> 1, (f - MLP_F_C0) & 1, r, hh);
+        else if (f < MLP_F_CO) v = load_w_frag<true>(Wc + 64 * 32, 64, 64, (f - MLP_F_C1) >> 2, (f - MLP_F_C1) & 3, r, hh);
+        else v = load_w_head_frag(Wc + 64 * 32 + 64 * 64, 64, 16, (f - MLP_F_CO) & 1, lane);
+        image[(f - MLP_F_C0) * 64 + lane] = v;
+    }
+}
+template <int NT, bool PRE>
+__device__ __forceinline__ void mlp_colour_half(const h8 (*wlds)[64], const h8 (&X1)[NT], const h8 (*X0), const f16v (*P)[2], _Float16 (&h0)[NT],
+                                                _Float16 (&rgbh)[NT][3]);
 #ifndef NRC_ENC_DENS_WAVES
 #define NRC_ENC_DENS_WAVES 7   // waves per SIMD the density-encoder form's register budget is set for (workgroups per CU: a workgroup is one wave per SIMD).
                                // 67 VGPRs, no scratch; without a budget the chain's accumulators go to AGPRs (68 + 32: 4 waves).  Measured, frame ms: 8 waves (64 VGPRs,
                                // 20 B of scratch) 6.89, 7 waves 6.62, 7 waves' registers held to 6 / 5 waves by LDS padding 6.64 / 7.25 -- LABBOOK R31.2
 #endif
-template <int SRC, bool DENS = false>
+// FULL (the single-pass frame's full-encoder form, with DENS): behind each tile's density half the wave runs the COLOUR half too (mlp_colour_half<1, false>,
+// the per-row form of k_ngp_mlp) and stores the 8-byte record (h0, r, g, b) of k_ngp_mlp at the slot's ABSOLUTE place, packed[base + j] -- `feat` is that
+// array; k_composite_image composites it.  X0, the SH fragment of the sample in MFMA column r, is ray_sh[(rt * 2 + hh) * 64 + (slot & 63)] with rt and slot
+// those of the sample on lane 32 v + r: both reach lane 32 hh + r by a v_permlane32_swap.  LDS: the density image in slots 0 .. 5 and the colour image
+// (colour_frag_image_build, the 14 KB directly in FRONT of wimg) in slots MLP_F_C0 .. MLP_F_CO + 1, 22 KB per workgroup.  Holes store nothing: the
+// compositor stops at a ray's sample count.  The host keeps base + n below 2^32 (slots travel between lanes as 32 bits).
+template <int SRC, bool DENS = false, bool FULL = false>
 __global__ void __launch_bounds__(256, DENS ? NRC_ENC_DENS_WAVES : 0) k_grid_encode(QueryIn in, int64_t base, int64_t n, const __half2* __restrict__ table, GridCfg g,
                                                          uint4* __restrict__ feat, int narrow_levels, int lvl_range, int lane_shape = 0, int xcd_run = 0,
                                                          BlockView bv = BlockView{}, VertexView vv = VertexView{}, YPairView yv = YPairView{},
-                                                         const h8* __restrict__ wimg = nullptr) {
+                                                         const h8* __restrict__ wimg = nullptr, const h8* __restrict__ ray_sh = nullptr) {
     static_assert(!DENS || SRC == SRC_TILED, "the density-encoder form belongs to the tiled layout");
-    extern __shared__ h8 enc_wlds[][64];   // DENS: (MLP_F_DO + 2) * 1 KB of dynamic LDS, none otherwise
+    static_assert(!FULL || DENS, "the full-encoder form extends the density-encoder form");
+    extern __shared__ h8 enc_wlds[][64];   // DENS: (MLP_F_DO + 2) * 1 KB of dynamic LDS (FULL: (MLP_F_CO + 2) * 1 KB), none otherwise
     if constexpr (DENS) {   // the frame's fragment image (density_frag_image_build), 384 vectors over 256 threads; read behind the barrier in front of the chain.
         // Measured against it (LABBOOK R34): the barrier directly behind this copy, frame -0.075 ms, inside three spreads of this placement's own runs; no LDS,
         // every wave loading its fragments from the image at the point of use, frame +0.09 ms and 69 VGPRs
         for (int i = threadIdx.x; i < MLP_DENS_IMAGE_VECS; i += 256) (&enc_wlds[0][0])[i] = wimg[i];
+        if constexpr (FULL) {   // 896 vectors more, 3.5 per thread
+            const h8* cimg = wimg - MLP_COL_IMAGE_VECS;
+            for (int i = threadIdx.x; i < MLP_COL_IMAGE_VECS; i += 256) (&enc_wlds[MLP_F_C0][0])[i] = cimg[i];
+        }
     }
     int64_t bid = blockIdx.x;
     if constexpr (SRC == SRC_TILED) {
@@ -430,7 +460,9 @@ __global__ void __launch_bounds__(256, DENS ? NRC_ENC_DENS_WAVES : 0) k_grid_enc
     float px = 0.f, py = 0.f, pz = 0.f;
     if (blockIdx.y != 0) in.x01_out = nullptr;   // level groups split over workgroup rows: the first row writes the normalised positions
     int state = -1;
-    if (in_range) state = remapped ? fetch_pos<SRC, false>(in, base + j, px, py, pz) : fetch_pos<SRC>(in, base + j, px, py, pz);
+    int32_t my_rt = 0;   // FULL: the sample's ray tile
+    if (in_range) state = remapped ? fetch_pos<SRC, false>(in, base + j, px, py, pz, FULL ? &my_rt : nullptr)
+                                   : fetch_pos<SRC>(in, base + j, px, py, pz, FULL ? &my_rt : nullptr);
     if constexpr (!DENS) {
         if (state < 0) return;   // a row of a finished tile (slab order): the MLP kernel skips it too, nothing reads its features
     }
@@ -511,15 +543,30 @@ __global__ void __launch_bounds__(256, DENS ? NRC_ENC_DENS_WAVES : 0) k_grid_enc
         }
         // where the result of tile v goes: lane 32 hh + r ends up with features 8 hh .. 8 hh + 7 of the sample on lane 32 v + r, whose slot it learns by
         // the same swap (~0: no record -- a slot behind n or a row of a finished tile)
-        const uint32_t own = (in_range && state >= 0) ? (uint32_t)j : ~0u;
+        // (FULL: the ABSOLUTE slot, and none for a hole either)
+        const uint32_t own = FULL ? (state > 0 ? (uint32_t)(base + j) : ~0u) : ((in_range && state >= 0) ? (uint32_t)j : ~0u);
         const auto slot = __builtin_amdgcn_permlane32_swap(own, own, false, false);
+        h8 X0[2][1];
+        if constexpr (FULL) {   // both tiles' SH fragments, in flight across the barrier.  A lane without a sample reads a fragment of ray tile 0: in bounds, unused
+            const uint32_t rt_own = state > 0 ? (uint32_t)my_rt : 0u;
+            const auto rts = __builtin_amdgcn_permlane32_swap(rt_own, rt_own, false, false);
+#pragma unroll
+            for (int v = 0; v < 2; v++) X0[v][0] = ray_sh[((int64_t)rts[v] * 2 + (lane >> 5)) * 64 + (slot[v] & 63u)];
+        }
         __syncthreads();   // the staged weights; every wave of the workgroup arrives (none has returned)
 #pragma unroll
         for (int v = 0; v < 2; v++) {
             h8 X1[1];
             mlp_density_half<1>(enc_wlds, B[v], X1);
             const uint32_t sj = slot[v];
-            if (sj != ~0u) feat[(int64_t)(sj >> 5) * 64 + (lane & 32) + (sj & 31u)] = *reinterpret_cast<const uint4*>(&X1[0]);
+            if constexpr (FULL) {
+                _Float16 h0[1], rgbh[1][3];
+                mlp_colour_half<1, false>(enc_wlds, X1, X0[v], nullptr, h0, rgbh);
+                const h4 rec = {h0[0], rgbh[0][0], rgbh[0][1], rgbh[0][2]};   // (h0, r), (g, b): the record of k_ngp_mlp, on lane r < 32 the sample of column r
+                if (lane < 32 && sj != ~0u) reinterpret_cast<h4*>(feat)[sj] = rec;
+            } else {
+                if (sj != ~0u) feat[(int64_t)(sj >> 5) * 64 + (lane & 32) + (sj & 31u)] = *reinterpret_cast<const uint4*>(&X1[0]);
+            }
             asm volatile("" ::: "memory");   // one tile at a time: the second chain starts behind the first one's store (32 accumulator registers, not 64)
         }
     }
@@ -618,9 +665,15 @@ __global__ void __launch_bounds__(256) k_build_ypair_view(const uint32_t* __rest
 // tile t (what nrc_ngp_render_write does next to its copy; here there is no copy and no second launch)
 __global__ void __launch_bounds__(256) k_ray_sh(const float* __restrict__ ray_od, int64_t n_ray_tiles, h8* __restrict__ ray_sh,
                                                 const int32_t* __restrict__ rows_tile_off = nullptr, int32_t* __restrict__ row_tile_out = nullptr,
-                                                int64_t n_rows = 0, const __half* __restrict__ Wd = nullptr, h8* __restrict__ frag_image = nullptr) {
+                                                int64_t n_rows = 0, const __half* __restrict__ Wd = nullptr, h8* __restrict__ frag_image = nullptr,
+                                                const __half* __restrict__ Wc = nullptr, h8* __restrict__ colour_image = nullptr) {
     // frag_image (the single-pass frame): the launch has ONE workgroup more than the ray tiles need, and that one writes the density net's fragment image
-    if (frag_image && blockIdx.x == gridDim.x - 1) { density_frag_image_build(Wd, frag_image); return; }
+    // and, behind it, the colour net's (colour_image)
+    if (frag_image && blockIdx.x == gridDim.x - 1) {
+        density_frag_image_build(Wd, frag_image);
+        if (colour_image) colour_frag_image_build(Wc, colour_image);
+        return;
+    }
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n_ray_tiles * 64) return;
     const int64_t tile = i >> 6;
@@ -637,6 +690,7 @@ __global__ void __launch_bounds__(256) k_ray_sh(const float* __restrict__ ray_od
 }
 // the image builder on its own (nrc_ngp_density_frag_image: what the tests read back)
 __global__ void __launch_bounds__(256) k_density_frag_image(const __half* __restrict__ Wd, h8* __restrict__ image) { density_frag_image_build(Wd, image); }
+__global__ void __launch_bounds__(256) k_colour_frag_image(const __half* __restrict__ Wc, h8* __restrict__ image) { colour_frag_image_build(Wc, image); }
 
 __device__ __forceinline__ float fast_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
 
@@ -1351,12 +1405,13 @@ static YPairView ypair_view_of(const void* view, const GridCfg& g, int n_levels)
     if (!yv.ptr || yv.levels <= 0) { yv.ptr = nullptr; yv.levels = 0; }
     return yv;
 }
+// full_ray_sh (with density_frag_image): the full-encoder form (k_grid_encode<SRC_TILED, true, true>), see the kernel
 // density_frag_image: the density-encoder form (k_grid_encode<SRC_TILED, true>): `feat` receives 32 B per slot, the density net's output; the image is
 // the one density_frag_image_build wrote earlier on the same stream
 template <int SRC>
 static void launch_encode(const QueryIn& in, int64_t base, int64_t n, const void* table, const GridCfg& g, uint4* feat, hipStream_t s,
                           const BlockView& bv = BlockView{}, const VertexView& vv = VertexView{}, const YPairView& yv = YPairView{},
-                          const h8* density_frag_image = nullptr) {
+                          const h8* density_frag_image = nullptr, const h8* full_ray_sh = nullptr) {
     // levels whose cells are larger than a wave's footprint: narrow gathers (see grid_level_features_narrow)
     int narrow = 0;
     while (narrow < NRC_MAX_LEVELS && !g.hashed[narrow] && g.size[narrow] > 8) narrow++;
@@ -1383,6 +1438,12 @@ static void launch_encode(const QueryIn& in, int64_t base, int64_t n, const void
     const int lane_shape = (3 << 4) | 1;
     const int lanes = (SRC == SRC_TILED && (base & 1023) == 0) ? (g_enc_shape_override ? g_enc_shape_override : lane_shape) : 0;
     if constexpr (SRC == SRC_TILED) {
+        if (density_frag_image && full_ray_sh) {   // the full-encoder form: `feat` receives the 8-byte records at their absolute slots, the colour image lies in front of the density image
+            hipLaunchKernelGGL((k_grid_encode<SRC_TILED, true, true>), dim3((unsigned)(lanes ? 4 * nrc_cdiv(n, 1024) : nrc_cdiv(n, 256))), dim3(256),
+                               (MLP_F_CO + 2) * 64 * sizeof(h8), s, in, base, n, (const __half2*)table, g, feat, narrow, lvl_range, lanes,
+                               g_enc_xcd_run_override ? g_enc_xcd_run_override : NRC_ENC_XCD_RUN, bv, vv, yv, density_frag_image, full_ray_sh);
+            return;
+        }
         if (density_frag_image) {
             hipLaunchKernelGGL((k_grid_encode<SRC_TILED, true>), dim3((unsigned)(lanes ? 4 * nrc_cdiv(n, 1024) : nrc_cdiv(n, 256))), dim3(256),
                                MLP_DENS_IMAGE_VECS * sizeof(h8), s, in, base, n, (const __half2*)table, g, feat, narrow, lvl_range, lanes,
@@ -1780,7 +1841,8 @@ int nrc_ngp_render_layers(const float* ts, int32_t* row_tile, const float* ray_o
 }
 
 /* workspace of the single-pass frame: [features of the largest chunk][ray_sh][order: n_ray_tiles i32][chunk table: 4 i32 per chunk][queue: 1 i32 per chunk]
-   [the density net's fragment image: 6 KB, written by every frame (k_ray_sh's last workgroup) and read by the density-encoder form of k_grid_encode] */
+   [the colour net's fragment image: 14 KB][the density net's fragment image: 6 KB] -- both images written by every frame (k_ray_sh's last workgroup); the
+   density-encoder form of k_grid_encode reads the second, the full-encoder form both.  The density image stays the LAST 6 144 bytes. */
 #ifndef NRC_FRAME_ROW_BUDGET
 #define NRC_FRAME_ROW_BUDGET (int64_t(1) << 21)   // rows of 64 slots per encode / MLP round of the single-pass frame (8 GiB of features; an 800x800 bench
                                                   // frame has ~1.2 Mi rows: ONE round).  Larger frames are cut into chunks of whole ray tiles.
@@ -1807,6 +1869,24 @@ int nrc_ngp_set_frame_density_encoder(int32_t mode) {
     g_frame_density_override = mode;
     return NRC_OK;
 }
+// The third form, where the density pair would be chosen: the encoder runs BOTH nets and stores the 8-byte record (h0, r, g, b) of every sample at its
+// absolute slot -- in the feature part of the workspace, whose 64 B per slot of the largest chunk hold 8 x feat_rows rows of records --, and ONE launch of
+// k_composite_image composites them: no k_ngp_mlp_composite, no k_tile_chunks.  Same pictures, bit for bit (tests/test_gpu_frame_full_encoder.py).
+// Frames of more rows than that (more than eight row budgets) keep the 32-byte pair, and so do frames of 2^25 rows or more (a slot is passed between
+// lanes as 32 bits).  nrc_ngp_set_frame_full_encoder: -1 = NRC_FRAME_FULL_ENCODER; per host thread.
+#ifndef NRC_FRAME_FULL_ENCODER
+#define NRC_FRAME_FULL_ENCODER 1   // measured against the 32-byte pair, five alternations: frame 6.36 -> 5.72 ms (median gain 0.64 ms, the pair's own spread 0.10) -- LABBOOK R35
+#endif
+static thread_local int g_frame_full_override = -1;
+static bool frame_full_encoder(int64_t n_rows, int64_t feat_rows) {
+    const int want = g_frame_full_override >= 0 ? g_frame_full_override : NRC_FRAME_FULL_ENCODER;
+    return want != 0 && frame_density_pair(feat_rows) && n_rows <= 8 * feat_rows && n_rows < (int64_t(1) << 25);
+}
+int nrc_ngp_set_frame_full_encoder(int32_t mode) {
+    if (mode < -1 || mode > 1) return NRC_ERR_INVALID;
+    g_frame_full_override = mode;
+    return NRC_OK;
+}
 int64_t nrc_ngp_render_frame_ws_bytes(int64_t n_rows, int64_t n_ray_tiles, int32_t max_samples, int64_t row_budget) {
     const int64_t budget = frame_budget(row_budget);
     if (n_rows < 0 || n_ray_tiles < 0 || max_samples < 1 || budget < 2 * (int64_t)max_samples) return NRC_ERR_INVALID;
@@ -1814,7 +1894,7 @@ int64_t nrc_ngp_render_frame_ws_bytes(int64_t n_rows, int64_t n_ray_tiles, int32
     const int64_t feat_rows = n_rows < budget ? n_rows : budget;
     // (the feature part is sized for the 64-byte pair whichever pair is set: a workspace sized once serves both, the density-encoder pair uses its first half)
     return round256((feat_rows > 0 ? feat_rows : 1) * 64 * 64) + round256(n_ray_tiles * 2048) + round256(n_ray_tiles * 4) + round256(chunks * 20) +
-           round256(MLP_DENS_IMAGE_VECS * sizeof(h8));   // (the fragment image, whichever pair is set)
+           round256(MLP_COL_IMAGE_VECS * sizeof(h8)) + round256(MLP_DENS_IMAGE_VECS * sizeof(h8));   // (the two fragment images, whichever form is set)
 }
 
 int nrc_ngp_render_frame(const float* ts_arena, int32_t* row_tile, const float* ray_od, int64_t n_rows, int64_t n_ray_tiles, const float* xyz_min3,
@@ -1850,7 +1930,11 @@ int nrc_ngp_render_frame(const float* ts_arena, int32_t* row_tile, const float* 
     int32_t* chunk_tab = (int32_t*)wsp;
     int32_t* queue = chunk_tab + 4 * chunks;
     wsp += round256(chunks * 20);
-    h8* wimg = (h8*)wsp;   // the density net's fragment image, rebuilt by every frame: weights that changed since the last one cannot go stale
+    static_assert(MLP_COL_IMAGE_VECS * sizeof(h8) % 256 == 0, "the colour image ends where the density image begins");
+    h8* cimg = (h8*)wsp;   // the colour net's fragment image, directly in front of ...
+    wsp += round256(MLP_COL_IMAGE_VECS * sizeof(h8));
+    h8* wimg = (h8*)wsp;   // ... the density net's: both rebuilt by every frame, weights that changed since the last one cannot go stale
+    const bool full = frame_full_encoder(n_rows, feat_rows);
     QueryIn in = {};
     in.ts = ts_arena; in.row_tile = row_tile; in.ray_od = ray_od; in.tile_off = tile_off; in.arena_rows = max_samples;
     for (int k = 0; k < 3; k++) { in.mn[k] = xyz_min3[k]; in.sz[k] = xyz_size3[k]; }
@@ -1868,10 +1952,22 @@ int nrc_ngp_render_frame(const float* ts_arena, int32_t* row_tile, const float* 
     const VertexView vv = vertex_view_of(vview, g, n_levels);
     const YPairView yv = ypair_view_of(yview, g, n_levels);
     NRC_STAGE(s, nullptr);
-    // SH of every ray + the ray tile of every row (for the encoder) + one workgroup more: the density net's fragment image
+    // SH of every ray + the ray tile of every row (for the encoder) + one workgroup more: the two nets' fragment images
     hipLaunchKernelGGL(k_ray_sh, dim3((unsigned)nrc_cdiv(n_ray_tiles * 64, 256) + 1u), dim3(256), 0, s, ray_od, n_ray_tiles, ray_sh, tile_off, row_tile, n_rows,
-                       (const __half*)density_weights_f16, wimg);
+                       (const __half*)density_weights_f16, wimg, (const __half*)color_weights_f16, cimg);
     NRC_STAGE(s, "k_ray_sh");
+    if (full) {
+        // one encoder launch over every row (the records need no chunks: 8 B per slot, absolute slots), then one compositor launch over every ray tile
+        if (n_rows > 0) {
+            launch_encode<SRC_TILED>(in, 0, n_rows * 64, table_f16, g, feat, s, bv, vv, yv, wimg, ray_sh);
+            NRC_STAGE(s, "k_grid_encode");
+        }
+        nrc_launch_composite_image(feat, ts_arena, ray_cnt, tile_off, width, height, tile_begin, n_ray_tiles, cascades, exp_step_factor, grid_size, max_samples,
+                                   T_threshold, bg3_host, rgb, alpha, depth, 0, max_samples, s);
+        NRC_STAGE(s, "k_composite_image");
+        NRC_LAUNCH_CHECK();
+        return NRC_OK;
+    }
     hipLaunchKernelGGL(k_tile_chunks, dim3((unsigned)chunks), dim3(1024), 0, s, tile_off, n_ray_tiles, chunks > 1 ? budget - max_samples : n_rows + 1,
                        chunk_tab, order, queue);
     NRC_STAGE(s, "k_tile_chunks");
@@ -1889,6 +1985,15 @@ int nrc_ngp_render_frame(const float* ts_arena, int32_t* row_tile, const float* 
                                (const __half*)color_weights_f16, ts_arena, (int)max_samples, ray_cnt, tile_off, order, chunk_tab + 4 * c, queue + c, ic, rgb, alpha, depth);
         NRC_STAGE(s, "k_ngp_mlp");   // (k_ngp_mlp_composite: the stage keeps the MLP kernel's name, where the in-frame ruler looks for it)
     }
+    NRC_LAUNCH_CHECK();
+    return NRC_OK;
+}
+
+/* group 30: the colour net's fragment image on its own (14 336 bytes at image_out): the builder the frame runs, one workgroup */
+int nrc_ngp_colour_frag_image(const void* color_weights_f16, void* image_out, nrc_stream_t stream) {
+    NRC_ENTER();
+    if (!color_weights_f16 || !image_out) return NRC_ERR_INVALID;
+    hipLaunchKernelGGL(k_colour_frag_image, dim3(1), dim3(256), 0, (hipStream_t)stream, (const __half*)color_weights_f16, (h8*)image_out);
     NRC_LAUNCH_CHECK();
     return NRC_OK;
 }

@@ -148,6 +148,7 @@ class InstantNGPRenderer:
     COUNT_MAILBOX = True       # fused image path: the row count reaches the host through a mapped host mailbox (False: device-to-host copy)
     POSE_ENCODER_SHAPE = True  # fused image path: the encoder's brick of samples per wave follows the camera's axes (False: the fixed 8 x 2 x 4 default)
     ARENA_IN_PLACE = True      # fused image path, single pass: the query / compositing kernels read the samples from the count pass's arena (False: copied to compact rows first)
+    FRAME_FULL_ENCODER = -1  # single pass from the arena, where the density-encoder pair would run: the encoder runs both nets and stores 8-byte records, one compositor launch behind it (1), the 32-byte pair (0), the library's default (-1)
     FRAME_DENSITY_ENCODER = -1  # single pass from the arena: the encoder runs the density net and hands over 32 B per slot (1), 64 B of grid features (0), the library's default (-1)
     FRAME_ROW_BUDGET = 0       # single pass from the arena: rows per encode / MLP round (chunks of whole ray tiles; 0 = the library's default, one round at 800x800)
 
@@ -486,12 +487,13 @@ class InstantNGPRenderer:
         """argument list of nrc_ngp_render_frame (the single pass from the arena: MLP and compositing in one kernel) with the row count (index 3)
         still open; its workspace follows the sample buffers' capacity"""
         m, lib, cam, vp, g = self.model, _lib.load(), fc['camera'], ctypes.c_void_p, fc['grid']
-        budget, pair = int(self.FRAME_ROW_BUDGET), int(self.FRAME_DENSITY_ENCODER)
+        budget, pair, full = int(self.FRAME_ROW_BUDGET), int(self.FRAME_DENSITY_ENCODER), int(self.FRAME_FULL_ENCODER)
         _lib.check(lib.nrc_ngp_set_frame_density_encoder(pair), 'ngp_set_frame_density_encoder')
-        if ws.get('fws_key') != (ws['cap'], budget, pair):
+        _lib.check(lib.nrc_ngp_set_frame_full_encoder(full), 'ngp_set_frame_full_encoder')
+        if ws.get('fws_key') != (ws['cap'], budget, pair, full):
             ws['fws'] = None
             ws['fws'] = torch.empty(int(lib.nrc_ngp_render_frame_ws_bytes(ws['cap'], nt, self.MAX_SAMPLES, budget)), dtype=torch.uint8, device=ws['ray_od'].device)
-            ws['fws_key'] = (ws['cap'], budget, pair)
+            ws['fws_key'] = (ws['cap'], budget, pair, full)
         ws['block_view'] = self._block_view_ptr()
         return [_lib.ptr(ws['ts_prov']), _lib.ptr(ws['row_tile']), _lib.ptr(ws['ray_od']), 0, nt, ctypes.cast(fc['mn'], vp), ctypes.cast(fc['sz'], vp),
                 _lib.ptr(m.encoding_xyz._half_params()), _lib.ptr(m.color_mlp_with_encoding._half_params()), _lib.ptr(m.encoding_xyz._table16()),
@@ -507,6 +509,7 @@ class InstantNGPRenderer:
         if self.POSE_ENCODER_SHAPE:
             lib.nrc_ngp_set_encoder_shape(*fc['enc_shape'])
         lib.nrc_ngp_set_frame_density_encoder(ws['fws_key'][2])   # (the pair `args` was marshalled for)
+        lib.nrc_ngp_set_frame_full_encoder(ws['fws_key'][3])
         self._frame_entry(lib.nrc_ngp_render_frame, args, 'ngp_render_frame', ws['block_view'])
 
     def _fused_composite(self, fc: dict, ws: dict, out: dict, tile_begin: int, nt: int, row_capacity: int = 0, arena: bool = False) -> None:

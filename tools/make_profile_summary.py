@@ -139,10 +139,10 @@ for k in sorted(acc):
     if k.startswith('k_grid_encode') or k.startswith('k_ngp_mlp'):
         if k.startswith('k_ngp_mlp_composite'):   # <DENS>: the 64-byte form keeps the name it had before it was a template
             key = 'k_ngp_mlp_composite<DENS>' if k.endswith('<1>') else 'k_ngp_mlp_composite'
-        elif k.startswith('k_grid_encode<1, 1'):   # <SRC, DENS>: the density-encoder form of the single-pass frame beside the 64-byte form
+        elif k.startswith('k_grid_encode<1, 1'):   # <SRC, DENS, FULL>: the encoder of the single-pass frame (density-encoder or full-encoder form, whichever the frame ran) beside the 64-byte form
             key = 'k_grid_encode<SRC_TILED, DENS>'
         else:
-            key = re.sub(r'<1(, \d+)?>', '<SRC_TILED>', re.sub(r'<0(, \d+)?>', '<SRC_ARRAYS>', k))
+            key = re.sub(r'<1(, \d+)*>', '<SRC_TILED>', re.sub(r'<0(, \d+)*>', '<SRC_ARRAYS>', k))   # (<SRC, DENS, FULL> of the 64-byte forms: 0, 0)
     summary[key] = {**{n: round(v, 1) for n, v in c.items()}, **derived}
 (OUT / f'{ROUND}_pmc_summary.md').write_text('\n'.join(lines))
 import hashlib
